@@ -485,8 +485,8 @@ class FilterXfCache:
     CHUNK_BYTES = int(float(os.environ.get("MTLSSL_XF_REFRESH_CHUNK_MB", "48")) * (1 << 20))
 
     def _tables(self):
-        """Device pointer tables per chunk, rebuilt only when the set of entries changed."""
-        if getattr(self, "_tab_n", -1) != len(self.entries):
+        """Device pointer tables per chunk, rebuilt only when the set of entries (or the chunk size) changed."""
+        if getattr(self, "_tab_n", None) != (len(self.entries), self.CHUNK_BYTES):
             chunks, cur, cur_bytes = [], [], 0
             for e in self.entries.values():
                 nb = e["U"].numel() * 4
@@ -507,7 +507,7 @@ class FilterXfCache:
                     u=torch.tensor([e["U"].data_ptr() for e in es], dtype=torch.int64, device=dev),
                     ck=torch.tensor([e["d"].C * e["d"].K for e in es], dtype=torch.int64, device=dev),
                     flip=torch.tensor([int(e["mode"] == 1) for e in es], dtype=i32, device=dev)))
-            self._tab_n = len(self.entries)
+            self._tab_n = (len(self.entries), self.CHUNK_BYTES)
         return self._tab
 
     def refresh(self, stream=None):

@@ -36,6 +36,17 @@ def gradients(tag, grads, ref, losses=None, ref_losses=None):
     return l2
 
 
+def dot_err(y, ref, scale):
+    """max |y - ref| in units of 2^-24 * scale, where scale is the sum over the reduction of |a*b| (plus the magnitude of
+    any addend the epilogue brings) — the natural unit of an fp32 dot product. `y` is the kernel's result (any device),
+    `ref` / `scale` float64 CPU tensors of its shape. An output with scale 0 must be exactly 0 (e.g. the input pixels a
+    strided convolution never reads)."""
+    yd = y.double().cpu()
+    live = scale > 0
+    assert bool((yd[~live] == 0).all())
+    return float(((yd - ref).abs()[live] / (scale[live] * 2.0 ** -24)).max())
+
+
 def against_float64(tag, Oracle, hp, values, host_batch, seed, step, boxes, num, grads, cap=1e-3, outliers=12, worst=1e-2,
                     feat=None, d_feat=None, median_cap=3e-4, g32=None):
     """The gradient claim against the better yardstick: the same graph evaluated by the oracle in float64 AND in

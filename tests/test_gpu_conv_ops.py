@@ -2,6 +2,7 @@
 losses and the optimizer, each against the torch-CPU fp32 oracle (autograd for backward).
 Tolerance 1e-3 relative fp32 (BASELINE.json north_star); in practice ~1e-6."""
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -81,7 +82,7 @@ CONV_CASES = [
 def test_conv_fwd_dgrad_wgrad(ops, case):
     N, H, W, C, K, R, stride, dil, padding = case
     R, S = R if isinstance(R, tuple) else (R, R)
-    g = torch.Generator().manual_seed(hash(case) % 2**31)
+    g = torch.Generator().manual_seed(zlib.crc32(repr(case).encode()))
     x = torch.randn(N, H, W, C, generator=g)
     w = torch.randn(R, S, C, K, generator=g) / np.sqrt(R * S * C)
     bias = torch.randn(K, generator=g)
@@ -138,7 +139,7 @@ def test_every_direct_tile_matches_oracle(ops, case, tile):
     0-3: operands staged through registers; 12-15: staged by LDS-DMA) pinned through the plan registry, all three
     modes with their epilogues."""
     N, H, W, C, K, R, stride, dil, padding = case
-    g = torch.Generator().manual_seed(hash(case) % 2**31)
+    g = torch.Generator().manual_seed(zlib.crc32(repr(case).encode()))
     x = torch.randn(N, H, W, C, generator=g)
     w = torch.randn(R, R, C, K, generator=g) / np.sqrt(R * R * C)
     bias = torch.randn(K, generator=g)
@@ -237,7 +238,7 @@ def test_strided_output_side_is_bit_identical_to_dense(ops, case):
     the forward touches nothing outside its slice. Every algorithm family the Inception-ResNet-v2 branches end in."""
     N, H, W, C, K, R, stride, dil, padding, alg, CC, c0 = case
     R, S = R if isinstance(R, tuple) else (R, R)
-    g = torch.Generator().manual_seed(hash(case) % 2**31)
+    g = torch.Generator().manual_seed(zlib.crc32(repr(case).encode()))
     x = torch.randn(N, H, W, C, generator=g).cuda()
     w = (torch.randn(R, S, C, K, generator=g) / np.sqrt(R * S * C)).cuda()
     bias = torch.randn(K, generator=g).cuda()

@@ -1,0 +1,392 @@
+"""Every (problem, mode) of the committed plan table (mtl_ssl_amd/conv_plans.json: the 150 distinct convolution layers of
+the four shipped configurations) at its full production size, on the plan production picks — the pinned code where the
+table pins one, the library's planner (split-K main + tail + fold, the LDS-DMA engine, the Winograd variants, the padded
+/ VALU forms) where it says -1 — against a float64 reference built on the CPU.
+
+The reference never shortens a reduction; it samples outputs instead: ~256 flat output rows of the forward (all K
+channels each) and input rows of the dgrad (all C channels), tile boundaries and image corners included, and every
+(r, s) tap of a channel block of the filter gradient summed over all N*OH*OW pixels. Errors are measured in units of
+2^-24 * (sum |a*b| + |the epilogue's addends|) (tests/parity_report.py dot_err): at most 8 for a direct plan, 400 for a
+Winograd plan. The nonlinear epilogues (ReLU, the ReLU mask) must be exact functions of the linear result, bit for bit.
+The same list then runs through the production Winograd filter cache (ops.FilterXfCache) and the kept input transform,
+and on the split-bf16 fp32 engine. Only the modes the table lists for a problem run: those are the calls the model
+makes. Workspaces stay NaN-poisoned (conftest: MTLSSL_POISON_WS)."""
+import ctypes
+import json
+import os
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+from tests import parity_report
+from tests.parity_report import dot_err
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROWS = 256                      # sampled rows of a forward output / dgrad input
+CH = 16                         # sampled channels per side of the filter-gradient block
+DIRECT_BOUND, WINO_BOUND = 8.0, 400.0       # the constants of tests/test_gpu_split_engine.py
+MODE_NAMES = ("fwd", "dgrad", "wgrad")
+
+
+def _load():
+    plans = json.load(open(os.path.join(ROOT, "mtl_ssl_amd", "conv_plans.json")))["plans"]
+    probs = {}
+    for key, val in plans.items():
+        v = tuple(int(t) for t in key.split(","))
+        probs.setdefault(v[1:], {})[v[0]] = val
+    return sorted(probs.items())
+
+
+PROBLEMS = _load()              # [(N, H, W, C, K, R, S, OH, OW, stride, dilation, pad_t, pad_l), {mode: table value}]
+_RUN = {}                       # (problem, mode) -> {"cfg", "family", "err", "split"}
+
+
+def _pid(prob):
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    return "%dx%dx%dx%d-k%d-%dx%d-o%dx%d-s%dd%dp%d%d" % (N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl)
+
+
+@pytest.fixture(scope="module")
+def ops():
+    import __graft_entry__ as g
+    g.build()
+    from mtl_ssl_amd import ops
+    assert torch.cuda.is_available()
+    assert ops.POISON_WS, "the suite runs with NaN-poisoned workspaces (tests/conftest.py)"
+    prev = ops.set_fp32_engine(0)
+    ops.reset_tuning(use_plan_db=True, autotune=False)
+    yield ops
+    ops.set_fp32_engine(prev)
+    ops.reset_tuning()
+    _report()
+
+
+def _desc(prob):
+    from mtl_ssl_amd.lib import ConvDesc
+    return ConvDesc(*prob, 0)
+
+
+def _cfg(d, mode):
+    from mtl_ssl_amd.lib import lib
+    return lib().conv2d_tile_config(ctypes.byref(d), mode)
+
+
+def _family(ops, d, mode):
+    from mtl_ssl_amd.lib import lib
+    return ops.conv_class(_cfg(d, mode), lib().conv2d_executed_macs(ctypes.byref(d), mode, 1))
+
+
+def _is_wino(ops, cfg):
+    return cfg >= 0 and ops.plan_code_algorithm(cfg) in (1, 2)
+
+
+def _rows(n_img, hs, ws, rng, n=ROWS):
+    """Flat rows (img * hs + y) * ws + x to compare: 0 and M-1, both sides of the first two and the last boundary of
+    every 64 / 128 / 256-row tile, the corners of the first and the last image, then random rows up to n."""
+    M = n_img * hs * ws
+    if M <= n:
+        return np.arange(M)
+    pick = {0, M - 1}
+    for b in (64, 128, 256):
+        for j in {1, 2, (M - 1) // b}:
+            pick.update(r for r in (j * b - 1, j * b, j * b + 1) if 0 <= r < M)
+    for im in (0, n_img - 1):
+        for y in (0, hs - 1):
+            for x in (0, ws - 1):
+                pick.add((im * hs + y) * ws + x)
+    rest = np.setdiff1d(np.arange(M), np.fromiter(pick, np.int64)) if M < 4 * n else None
+    while len(pick) < n:
+        pick.update(rng.choice(rest, n - len(pick), replace=False) if rest is not None
+                    else rng.integers(0, M, n - len(pick)))
+    return np.array(sorted(pick), np.int64)
+
+
+def _channels(c, rng, n=CH):
+    pick = {v for v in (0, 63, 64, 127, 128, 255, 256, c - 1) if v < c}
+    if c <= n:
+        return np.arange(c)
+    rest = np.setdiff1d(np.arange(c), np.fromiter(pick, np.int64))
+    pick.update(rng.choice(rest, max(n - len(pick), 0), replace=False))
+    return np.array(sorted(pick), np.int64)
+
+
+def _gather(t, n, y, x, valid):
+    """t[n, y, x, :] for index arrays of one shape (clamped in range first), zero where not valid -> float64 CPU."""
+    assert n.min() >= 0 and n.max() < t.shape[0]
+    yc, xc = np.clip(y, 0, t.shape[1] - 1), np.clip(x, 0, t.shape[2] - 1)
+    idx = [torch.from_numpy(np.array(a)).to(t.device) for a in (n, yc, xc)]
+    g = t[idx[0], idx[1], idx[2]].double().cpu()
+    return g * torch.from_numpy(valid)[..., None].double()
+
+
+def _fwd_reference(prob, x, w64, rows):
+    """Forward outputs of flat rows m = (n*OH + oy)*OW + ox: (sum, sum |a*b|), each [rows, K] float64."""
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    n, oy, ox = rows // (OH * OW), rows // OW % OH, rows % OW
+    iy = (oy[:, None] * st - pt + np.arange(R)[None, :] * dil)[:, :, None] + np.zeros((1, 1, S), np.int64)
+    ix = (ox[:, None] * st - pl + np.arange(S)[None, :] * dil)[:, None, :] + np.zeros((1, R, 1), np.int64)
+    valid = (iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)
+    a = _gather(x, np.broadcast_to(n[:, None, None], iy.shape), iy, ix, valid).reshape(len(rows), R * S * C)
+    b = w64.reshape(R * S * C, K)
+    return a @ b, a.abs() @ b.abs()
+
+
+def _dgrad_reference(prob, dy, w64, rows):
+    """Input gradient of flat input rows m = (n*H + iy)*W + ix: a tap (r, s) contributes where iy + pad_t - r*dil is a
+    non-negative multiple of the stride whose quotient is an output row (the same along x)."""
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    n, iy, ix = rows // (H * W), rows // W % H, rows % W
+    ny = iy[:, None] + pt - np.arange(R)[None, :] * dil
+    nx = ix[:, None] + pl - np.arange(S)[None, :] * dil
+    vy = (ny >= 0) & (ny % st == 0) & (ny // st < OH)
+    vx = (nx >= 0) & (nx % st == 0) & (nx // st < OW)
+    oy = (ny // st)[:, :, None] + np.zeros((1, 1, S), np.int64)
+    ox = (nx // st)[:, None, :] + np.zeros((1, R, 1), np.int64)
+    valid = vy[:, :, None] & vx[:, None, :]
+    a = _gather(dy, np.broadcast_to(n[:, None, None], oy.shape), oy, ox, valid).reshape(len(rows), R * S * K)
+    b = w64.permute(0, 1, 3, 2).reshape(R * S * K, C)
+    return a @ b, a.abs() @ b.abs()
+
+
+def _wgrad_reference(prob, x_sub, dy_sub):
+    """sum over all N*OH*OW pixels of x[tap] * dy for a channel block: [R, S, c_sub, k_sub] (sum, sum |a*b|)."""
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    hi_y = max((OH - 1) * st - pt + (R - 1) * dil - (H - 1), 0)
+    hi_x = max((OW - 1) * st - pl + (S - 1) * dil - (W - 1), 0)
+    xp = torch.nn.functional.pad(x_sub, (0, 0, pl, hi_x, pt, hi_y))       # zeros where a tap reads the padding
+    g = dy_sub.reshape(-1, dy_sub.shape[-1])
+    ref = torch.empty(R, S, x_sub.shape[-1], g.shape[1], dtype=torch.float64)
+    mag = torch.empty_like(ref)
+    for r in range(R):
+        for s in range(S):
+            a = xp[:, r * dil:r * dil + (OH - 1) * st + 1:st, s * dil:s * dil + (OW - 1) * st + 1:st, :]
+            assert a.shape[1:3] == (OH, OW)
+            a = a.reshape(-1, a.shape[-1])
+            ref[r, s], mag[r, s] = a.t() @ g, a.abs().t() @ g.abs()
+    return ref, mag
+
+
+def _bound(ops, cfg):
+    return WINO_BOUND if _is_wino(ops, cfg) else DIRECT_BOUND
+
+
+def test_parametrization_covers_the_whole_table():
+    assert len(PROBLEMS) == 150
+    assert sum(len(m) for _, m in PROBLEMS) == 359
+    assert len({p for p, _ in PROBLEMS}) == len(PROBLEMS)
+
+
+@pytest.mark.parametrize("prob,modes", PROBLEMS, ids=[_pid(p) for p, _ in PROBLEMS])
+def test_production_plan_matches_float64(ops, prob, modes):
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    d = _desc(prob)
+    seed = zlib.crc32(repr(prob).encode())
+    rng = np.random.default_rng(seed)
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    x = rand(N, H, W, C) * 2 - 0.6                                      # post-ReLU-like: mostly positive
+    w = (rand(R, S, C, K) - 0.5) * (2.0 / np.sqrt(R * S * C))
+    dy = rand(N, OH, OW, K) - 0.5                                       # zero-mean
+    w64 = w.double().cpu()
+    epi_f = ops.EPI_BIAS | ops.EPI_RESIDUAL
+    epi_d = ops.EPI_RESIDUAL | ops.EPI_ACCUM
+    out = {}                    # mode -> native outputs, reused by the split-engine pass
+    refs = {}                   # mode -> [(got -> tensor to compare, ref, mag)]
+
+    def call(mode, **kw):
+        if mode == 0:
+            return ops.conv2d_fwd(d, x, w, bias, res, epi_f, **kw)
+        if mode == 1:
+            dx = prev.clone()
+            ops.conv2d_dgrad(d, dy, w, resd, None, epi_d, out=dx, **kw)
+            return dx
+        dw, db = dw_old.clone(), db_old.clone()
+        ops.conv2d_wgrad(d, x, dy, dw, out_scale=scale, dbias=db, beta=1.0, **kw)
+        return dw, db
+
+    if 0 in modes:
+        bias, res = rand(K) - 0.5, rand(N, OH, OW, K) - 0.5
+        rows = _rows(N, OH, OW, rng)
+        rows_t = torch.from_numpy(rows).cuda()
+        ref, mag = _fwd_reference(prob, x, w64, rows)
+        addend = [bias.double().cpu()[None, :], res.reshape(-1, K)[rows_t].double().cpu()]
+        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
+        refs[0] = [(lambda y, r=rows_t: y.reshape(-1, K)[r], ref, mag)]
+    if 1 in modes:
+        resd, prev, mask = rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5
+        rows = _rows(N, H, W, rng)
+        rows_t = torch.from_numpy(rows).cuda()
+        ref, mag = _dgrad_reference(prob, dy, w64, rows)
+        addend = [t.reshape(-1, C)[rows_t].double().cpu() for t in (resd, prev)]
+        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
+        refs[1] = [(lambda dx, r=rows_t: dx.reshape(-1, C)[r], ref, mag)]
+    if 2 in modes:
+        scale, dw_old, db_old = rand(K) + 0.5, rand(R, S, C, K) - 0.5, rand(K) - 0.5
+        cs, ks = _channels(C, rng), _channels(K, rng)
+        cs_t, ks_t = torch.from_numpy(cs).cuda(), torch.from_numpy(ks).cuda()
+        dy_sub = dy[..., ks_t].double().cpu()
+        ref, mag = _wgrad_reference(prob, x[..., cs_t].double().cpu(), dy_sub)
+        s64, dw0 = scale[ks_t].double().cpu(), dw_old[:, :, cs_t][..., ks_t].double().cpu()
+        db0 = db_old[ks_t].double().cpu()
+        refs[2] = [(lambda o: o[0][:, :, cs_t][..., ks_t], dw0 + s64 * ref, dw0.abs() + s64.abs() * mag),
+                   (lambda o: o[1][ks_t], db0 + dy_sub.sum((0, 1, 2)), db0.abs() + dy_sub.abs().sum((0, 1, 2)))]
+
+    for mode, pinned in sorted(modes.items()):
+        o = out[mode] = call(mode)
+        cfg = _cfg(d, mode)
+        # (a) the table takes effect: the first call of the mode applied the pinned code
+        if pinned >= 0:
+            assert cfg == pinned, ("plan table entry not applied", mode, pinned, cfg)
+        for t in (o if mode == 2 else (o,)):
+            assert bool(torch.isfinite(t).all()), ("non-finite output (a poisoned workspace leaked?)", mode, cfg)
+        errs = [dot_err(sel(o), ref, mag) for sel, ref, mag in refs[mode]]
+        lims = [_bound(ops, cfg)] + [DIRECT_BOUND] * (len(errs) - 1)      # the bias gradient is a plain column sum
+        _RUN[(prob, mode)] = dict(cfg=cfg, family=_family(ops, d, mode), err=errs[0], split=None)
+        assert all(e <= lim for e, lim in zip(errs, lims)), (MODE_NAMES[mode], cfg, errs, lims)
+
+    # the nonlinear epilogues are exact functions of the linear result (the split-K fold sums in a fixed order)
+    if 0 in modes:
+        y = ops.conv2d_fwd(d, x, w, bias, res, epi_f | ops.EPI_RELU)
+        assert torch.equal(y, torch.relu(out[0])), ("forward ReLU epilogue", _cfg(d, 0))
+    if 1 in modes:
+        dx = prev.clone()
+        ops.conv2d_dgrad(d, dy, w, resd, mask, epi_d | ops.EPI_MASK, out=dx)
+        assert torch.equal(dx, torch.where(mask > 0, out[1], torch.zeros_like(dx))), ("dgrad mask epilogue", _cfg(d, 1))
+
+    # (c) production Winograd path: the filter cache and the kept input transform change no bit
+    for mode in (0, 1):
+        if mode in modes and _is_wino(ops, _cfg(d, mode)):
+            cache = ops.FilterXfCache()
+            assert torch.equal(call(mode, xf_cache=cache), out[mode]), ("filter cache", mode, _cfg(d, mode))
+            assert len(cache.entries) == 1
+            assert torch.equal(call(mode, xf_cache=cache), out[mode]), ("filter cache, second use", mode)
+    if 0 in modes and 2 in modes and ops._shared_input_variant(d) >= 0:
+        keep = {}
+        assert torch.equal(call(0, keep_input_xf=keep), out[0])
+        dw, db = call(2, input_xf=keep[x.data_ptr()])
+        assert torch.equal(dw, out[2][0]) and torch.equal(db, out[2][1]), "kept input transform"
+
+    # (d) the split-bf16 engine on the same calls: native bits where it declines, the native accuracy where it engages
+    assert ops.set_fp32_engine(1) == 0
+    try:
+        for mode in sorted(modes):
+            o = call(mode)
+            same = torch.equal(o[0], out[mode][0]) if mode == 2 else torch.equal(o, out[mode])
+            if same:
+                continue
+            assert not _split_declines(ops, prob, mode, _cfg(d, mode)), ("split engine ran on a small problem", mode)
+            sel, ref, mag = refs[mode][0]
+            e = dot_err(sel(o), ref, mag)
+            rec = _RUN[(prob, mode)]
+            rec["split"] = e
+            assert e <= 1.25 * max(rec["err"], 1.0) + 2.5, (MODE_NAMES[mode], rec, e)
+    finally:
+        ops.set_fp32_engine(0)
+
+
+def _split_declines(ops, prob, mode, cfg):
+    """Problems the split-bf16 engine must leave to the native one (csrc/conv_split.h split_tile_for /
+    split_wgrad_plan): a stride-1 direct forward or dgrad with fewer than 192 tiles of 256 x 256 (or an output narrower
+    than 256, counted with the GEMM width padded to 16), a filter gradient with C or K below 256."""
+    N, H, W, C, K, R, S, OH, OW, stride = prob[:10]
+    if mode == 2:
+        return C < 256 or K < 256
+    rows, cols = (N * OH * OW, K) if mode == 0 else (N * H * W, C)
+    cols = -(-cols // 16) * 16
+    return stride == 1 and not _is_wino(ops, cfg) and (cols < 256 or -(-rows // 256) * -(-cols // 256) < 192)
+
+
+def _winograd_entries(ops):
+    """(problem, mode) of every forward / dgrad the table plans as Winograd."""
+    out = []
+    for prob, modes in PROBLEMS:
+        d = _desc(prob)
+        for mode in (0, 1):
+            if mode in modes:
+                ops._autotune(d, mode, None)          # the plan of the first call (the on-line tuner is off)
+                if _is_wino(ops, _cfg(d, mode)):
+                    out.append((prob, mode))
+    return out
+
+
+def test_filter_cache_refresh_follows_weight_changes(ops, monkeypatch):
+    """All Winograd forward / dgrad entries of the table in ONE cache (both variants, both modes), the weights changed
+    in place, refreshed by the batched transform (ops.FilterXfCache.refresh): once on the current stream in the default
+    chunks, once on a side stream in many small chunks. After each refresh every cached call gives the uncached bits."""
+    entries = _winograd_entries(ops)
+    assert len(entries) >= 4
+    g = torch.Generator(device="cuda").manual_seed(11)
+    weights = {}
+    for prob, _ in entries:
+        R, S, C, K = prob[5], prob[6], prob[3], prob[4]
+        weights.setdefault(prob, torch.empty(R, S, C, K, device="cuda"))
+
+    def new_weights():
+        for prob, w in weights.items():
+            w.copy_((torch.rand(w.shape, device="cuda", generator=g) - 0.5) * (2.0 / np.sqrt(9 * prob[3])))
+
+    def check_all(cache, tag):
+        for prob, mode in entries:
+            d, w = _desc(prob), weights[prob]
+            gi = torch.Generator(device="cuda").manual_seed(zlib.crc32(repr((prob, mode)).encode()))
+            shape = (prob[0], prob[1], prob[2], prob[3]) if mode == 0 else (prob[0], prob[7], prob[8], prob[4])
+            u = torch.rand(shape, device="cuda", generator=gi) - 0.3
+            if mode == 0:
+                a, b = ops.conv2d_fwd(d, u, w, xf_cache=cache), ops.conv2d_fwd(d, u, w)
+            else:
+                a, b = ops.conv2d_dgrad(d, u, w, xf_cache=cache), ops.conv2d_dgrad(d, u, w)
+            assert torch.equal(a, b), (tag, _pid(prob), mode, _cfg(d, mode))
+
+    new_weights()
+    cache = ops.FilterXfCache()
+    check_all(cache, "first use")
+    kinds = {(e["variant"], e["mode"]) for e in cache.entries.values()}
+    assert len(cache.entries) == len(entries) and {v for v, _ in kinds} == {0, 1} and {m for _, m in kinds} == {0, 1}
+
+    new_weights()
+    cache.refresh()
+    check_all(cache, "refresh on the current stream")
+
+    new_weights()
+    n_default = len(cache._tables())
+    monkeypatch.setattr(ops.FilterXfCache, "CHUNK_BYTES", 1 << 20)
+    n_chunks = len(cache._tables())
+    assert n_chunks > max(n_default, 3), (n_chunks, n_default)
+    side = torch.cuda.Stream()
+    cache.refresh(stream=side)
+    check_all(cache, "refresh on a side stream in %d chunks" % n_chunks)
+    torch.cuda.synchronize()
+    parity_report.add("plan table, Winograd filter cache: %d forward / dgrad entries (%d variant/mode kinds) equal to "
+                      "the uncached calls bit for bit after first use, a refresh on the current stream and one on a side "
+                      "stream in %d chunks" % (len(entries), len(kinds), n_chunks))
+
+
+def _report():
+    if not _RUN:
+        return
+    fams = {}
+    for (prob, mode), r in _RUN.items():
+        f = fams.setdefault(r["family"], dict(n=0, modes=[0, 0, 0], err=[0.0, 0.0, 0.0], split=[None, None, None], eng=0))
+        f["n"] += 1
+        f["modes"][mode] += 1
+        f["err"][mode] = max(f["err"][mode], r["err"])
+        if r["split"] is not None:
+            f["eng"] += 1
+            f["split"][mode] = max(f["split"][mode] or 0.0, r["split"])
+    pinned = sum(1 for prob, m in PROBLEMS for mode, v in m.items() if v >= 0 and (prob, mode) in _RUN)
+    parity_report.add("plan table at full size: %d (problem, mode) pairs of %d problems ran (%d pinned, %d on the "
+                      "planner's choice); per family (fwd / dgrad / wgrad):" % (
+                          len(_RUN), len({p for p, _ in _RUN}), pinned, len(_RUN) - pinned))
+    fmt = lambda v: "-" if v is None else "%.2f" % v
+    for name, f in sorted(fams.items()):
+        parity_report.add("    %-32s %3d pairs (%d / %d / %d); worst error in 2^-24*sum|ab| units native %s, split-bf16 "
+                          "%s (engaged on %d)" % (
+                              name, f["n"], f["modes"][0], f["modes"][1], f["modes"][2],
+                              " / ".join("%.2f" % v for v in f["err"]), " / ".join(fmt(v) for v in f["split"]), f["eng"]))
+    engaged = [key for key, r in _RUN.items() if r["split"] is not None]
+    parity_report.add("    split-bf16 engine engaged on %d of %d (problem, mode) pairs (%d problems); native bits on the rest" % (
+        len(engaged), len(_RUN), len({p for p, _ in engaged})))

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.parity_report import dot_err as _err
+
 pytestmark = pytest.mark.gpu
 
 
@@ -27,14 +29,6 @@ def _both(ops, fn):
     b = fn()
     assert ops.set_fp32_engine(0) == 1
     return a, b
-
-
-def _err(y, ref, scale):
-    """max |y - ref| in units of 2^-24 * (sum over the reduction of |a*b|) — the natural unit of an fp32 dot product."""
-    yd = y.double().cpu()
-    live = scale > 0
-    assert bool((yd[~live] == 0).all())                 # e.g. the input pixels a strided convolution never reads
-    return float(((yd - ref).abs()[live] / (scale[live] * 2.0 ** -24)).max())
 
 
 CASES = [

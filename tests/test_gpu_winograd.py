@@ -3,6 +3,8 @@ mtlssl_conv2d_{fwd,dgrad,wgrad}: each GEMM tile of the transformed-domain produc
 plan registry, against the torch-CPU fp32 oracle and against the direct implicit-GEMM path.
 Tolerance 1e-3 relative fp32 (BASELINE.json north_star); asserted at 1e-4, in practice ~1e-5."""
 
+import zlib
+
 import numpy as np
 import pytest
 import torch
@@ -54,7 +56,7 @@ def test_winograd_matches_oracle_and_direct(ops, case, tile):
     """tile 0-3: the GEMM stack on the register-staged engine; 12-15: the same tile shapes on the LDS-DMA engine."""
     (N, H, W, C, K), variant = case
     wino_cfg = (ops.WINO_CFG0 if variant == "f43" else ops.WINO7_CFG0) + tile
-    g = torch.Generator().manual_seed(hash(case[0]) % 2**31)
+    g = torch.Generator().manual_seed(zlib.crc32(repr(case[0]).encode()))
     x = torch.randn(N, H, W, C, generator=g)
     w = torch.randn(3, 3, C, K, generator=g) / np.sqrt(9 * C)
     bias = torch.randn(K, generator=g)
