@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 8
+#define MTLSSL_ABI_VERSION 9
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -446,6 +446,23 @@ int mtlssl_resize_bilinear_fwd(const float* x, float* y, int N, int H, int W, in
                                int OW, mtlssl_stream_t stream);
 int mtlssl_resize_bilinear_bwd(const float* dy, float* dx, int N, int H, int W, int C, int OH,
                                int OW, mtlssl_stream_t stream);
+
+/* Input-pipeline image preparation (the reference's queue runners: decode -> core/preprocessor.py:239-345
+ * random_horizontal_flip -> core/preprocessor.py:1408-1411 tf.image.resize_images), after the host has decoded B
+ * uint8 HWC RGB images into one buffer: out [B,OH,OW,3] float32 (0..255) = bilinear legacy resize of the image,
+ * mirrored left-right first when `flip` is set; the plain cast (+ flip) when H == OH and W == OW. sy / sx are the
+ * scales float32(H / OH) and float32(W / OW) computed by the caller (mtl_ssl_amd.preprocessor.resize_bilinear_legacy
+ * rounds the double quotient once), so host and device agree to the bit. `desc` (device memory) holds B entries;
+ * image n's pixels are pixels[desc[n].offset, + H*W*3). B <= 65535. */
+typedef struct {
+  int64_t offset;            /* byte offset of the image in `pixels` */
+  int32_t H, W;              /* source size, >= 1 */
+  int32_t flip;              /* nonzero: mirror left-right before the resize */
+  float sy, sx;              /* float32(H / OH), float32(W / OW) */
+  int32_t pad;
+} mtlssl_image_desc;         /* 32 bytes */
+int mtlssl_prepare_images(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW, float* out,
+                          mtlssl_stream_t stream);
 
 /* ------------------------------------------------------------------ loss family
  * Fused loss + gradient. Every loss is a weighted sum of per-row terms; `row_loss_out[rows]`

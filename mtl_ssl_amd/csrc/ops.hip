@@ -604,6 +604,19 @@ __global__ void __launch_bounds__(256)
 
 // ------------------------------------------------------------------------------ bilinear resize
 // tf.image.resize_images(BILINEAR, align_corners=False), TF 1.7: src = dst * in/out.
+// The source taps of output coordinate o along an axis of n inputs at scale s (no half-pixel offset, the upper
+// neighbour clamped to the edge) and the blend of the four taps: shared by k_resize_fwd and k_prepare_images, and
+// restated on the host by preprocessor.resize_bilinear_legacy, so that the three cannot drift apart.
+__device__ __forceinline__ void resize_taps(int o, float s, int n, int& i0, int& i1, float& l) {
+  float f = (float)o * s;
+  i0 = (int)floorf(f);
+  i1 = min(i0 + 1, n - 1);
+  l = f - (float)i0;
+}
+__device__ __forceinline__ float resize_blend(float tl, float tr, float bl, float br, float yl, float xl) {
+  float top = tl + (tr - tl) * xl, bot = bl + (br - bl) * xl;
+  return top + (bot - top) * yl;
+}
 __global__ void k_resize_fwd(const float* x, float* y, int H, int W, int C, int OH, int OW,
                              float sy, float sx, int64_t total) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -613,15 +626,47 @@ __global__ void k_resize_fwd(const float* x, float* y, int H, int W, int C, int 
   int ox = t % OW; t /= OW;
   int oy = t % OH;
   int n = t / OH;
-  float fy = (float)oy * sy, fx = (float)ox * sx;
-  int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
-  int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
-  float yl = fy - (float)y0, xl = fx - (float)x0;
+  int y0, y1, x0, x1;
+  float yl, xl;
+  resize_taps(oy, sy, H, y0, y1, yl);
+  resize_taps(ox, sx, W, x0, x1, xl);
   const float* xb = x + (int64_t)n * H * W * C;
   float tl = xb[((int64_t)y0 * W + x0) * C + c], tr = xb[((int64_t)y0 * W + x1) * C + c];
   float bl = xb[((int64_t)y1 * W + x0) * C + c], br = xb[((int64_t)y1 * W + x1) * C + c];
-  float top = tl + (tr - tl) * xl, bot = bl + (br - bl) * xl;
-  y[i] = top + (bot - top) * yl;
+  y[i] = resize_blend(tl, tr, bl, br, yl, xl);
+}
+// Input-pipeline image preparation: B uint8 HWC RGB images, each at its own H x W, packed in one buffer ->
+// float32 [B, OH, OW, 3] = resize_bilinear_legacy(flip(float32(img))). The flip comes first (the legacy resize
+// is not mirror-symmetric), so a flipped image reads mirrored source columns. One thread per output pixel
+// writes its 3 channels (a wave stores 768 contiguous bytes); blockIdx.y is the image, so the descriptor load
+// is wave-uniform. Memory-bound: ~12 B written and <= 12 B read per pixel.
+__global__ void k_prepare_images(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
+                                 int OH, int OW, float* __restrict__ out) {
+  const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (p >= (int64_t)OH * OW) return;
+  const int n = blockIdx.y;
+  const mtlssl_image_desc d = desc[n];
+  const int H = d.H, W = d.W;
+  const uint8_t* src = pixels + d.offset;
+  const int oy = (int)(p / OW), ox = (int)(p % OW);
+  float* o = out + ((int64_t)n * OH * OW + p) * 3;
+  if (H == OH && W == OW) {                              // the host's early return: the plain cast (+ flip)
+    const uint8_t* s = src + ((int64_t)oy * W + (d.flip ? W - 1 - ox : ox)) * 3;
+    o[0] = (float)s[0]; o[1] = (float)s[1]; o[2] = (float)s[2];
+    return;
+  }
+  int y0, y1, x0, x1;
+  float yl, xl;
+  resize_taps(oy, d.sy, H, y0, y1, yl);
+  resize_taps(ox, d.sx, W, x0, x1, xl);
+  y0 = min(y0, H - 1); x0 = min(x0, W - 1);              // in range already (o * in/out < in); a guard for the reads
+  if (d.flip) { x0 = W - 1 - x0; x1 = W - 1 - x1; }      // columns of the mirrored image
+  const uint8_t* r0 = src + (int64_t)y0 * W * 3;
+  const uint8_t* r1 = src + (int64_t)y1 * W * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    o[c] = resize_blend((float)r0[x0 * 3 + c], (float)r0[x1 * 3 + c], (float)r1[x0 * 3 + c], (float)r1[x1 * 3 + c],
+                        yl, xl);
 }
 // Gradient of the resize as a GATHER (one thread per input element sums, in a fixed order, the output pixels
 // whose two source rows / columns include it): no float atomics, run-to-run bit-identical. The candidate
@@ -1275,6 +1320,15 @@ int mtlssl_resize_bilinear_fwd(const float* x, float* y, int N, int H, int W, in
   hipLaunchKernelGGL(k_resize_fwd, dim3(cdiv(total, 256)), dim3(256), 0, S(stream), x, y, H, W, C,
                      OH, OW, (float)H / (float)OH, (float)W / (float)OW, total);
   return check_launch("resize_fwd");
+}
+int mtlssl_prepare_images(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW, float* out,
+                          mtlssl_stream_t stream) {
+  MTLSSL_REQUIRE(B >= 0 && B <= 65535 && OH > 0 && OW > 0, "prepare_images: bad geometry");
+  if (!B) return MTLSSL_OK;
+  const int64_t pix = (int64_t)OH * OW;
+  hipLaunchKernelGGL(k_prepare_images, dim3((unsigned)cdiv(pix, 256), (unsigned)B), dim3(256), 0, S(stream), pixels,
+                     desc, OH, OW, out);
+  return check_launch("prepare_images");
 }
 int mtlssl_resize_bilinear_bwd(const float* dy, float* dx, int N, int H, int W, int C, int OH,
                                int OW, mtlssl_stream_t stream) {

@@ -32,12 +32,15 @@ def main(argv=None):
     ap.add_argument("--eval_training_data", default="false")
     ap.add_argument("--run_once", default="true")
     ap.add_argument("--logtostderr", action="store_true")
+    ap.add_argument("--input_pipeline", choices=("async", "host"), default="async",
+                    help="async: decode workers + on-device resize (mtl_ssl_amd.input_pipeline); host: the serial "
+                         "generator input_reader.batches (the same images, bit for bit)")
     f = ap.parse_args(sys.argv[1:] if argv is None else argv)
     import torch
     import __graft_entry__ as ge
     ge.build()
-    from . import checkpoint, config, evaluation, input_reader, model_builder
-    from .train import record_paths
+    from . import checkpoint, config, evaluation, model_builder
+    from .train import record_batches, record_paths
     cfg = config.parse_pipeline_config(open(f.pipeline_config_path).read())
     ec = cfg.get("eval_config", config.Msg("EvalConfig"))
     use_train = str(f.eval_training_data).lower() in ("1", "true")
@@ -60,7 +63,9 @@ def main(argv=None):
     rz = cfg.model.faster_rcnn.image_resizer
     ev = evaluation.CocoDetectionEvaluator(K) if coco else evaluation.PascalDetectionEvaluator(K, 0.5)
     n_img = 0
-    for b in input_reader.batches(record_paths(reader), K, 1, resized_shape=lambda h, w: model.resized_shape(h, w, rz)):
+    stream = record_batches(f.input_pipeline, record_paths(reader), K, 1, (), None, dev, reader,
+                            resized_shape=lambda h, w: model.resized_shape(h, w, rz))
+    for b in stream:
         if n_img >= limit:
             break
         pd = model.predict(model.preprocess(b["images"].to(dev)))
@@ -83,6 +88,8 @@ def main(argv=None):
         ev.add_single_detected_image_info(n_img, np.asarray(d["detection_boxes"][0][:n], np.float64) * scale,
                                           d["detection_scores"][0][:n], d["detection_classes"][0][:n])
         n_img += 1
+    if hasattr(stream, "close"):
+        stream.close()
     res = ev.evaluate()
     out = {"global_step": int(step), "num_images": n_img}
     for k, v in res.items():

@@ -232,10 +232,25 @@ def decode_example(serialized, num_classes):
     the `synthetic.make_batch` contract: image float32 [H,W,3] (0..255), groundtruth_boxes [G,4]
     normalised, groundtruth_classes one-hot [G,K] (labels are 1-based in the record), window boxes /
     classes, closeness, edge mask [2,h,w], plus difficult flags, filename and source id."""
+    out = decode_example_uint8(serialized, num_classes)
+    out["image"] = np.asarray(out["image"], np.float32)
+    return out
+
+
+def decode_example_uint8(serialized, num_classes, timings=None):
+    """decode_example with the image as decoded, uint8 [H,W,3] — the decoder both input paths share (the
+    asynchronous one, mtl_ssl_amd.input_pipeline, casts on the device). `timings`: an optional dict that receives
+    the seconds spent parsing the tf.Example ('parse') and decoding the image ('decode')."""
+    import time
     from PIL import Image
+    t0 = time.perf_counter()
     f = parse_example(serialized)
+    t1 = time.perf_counter()
     enc = f.get("image/encoded", [b""])[0]
-    img = np.asarray(Image.open(io.BytesIO(enc)).convert("RGB"), np.float32)
+    img = np.asarray(Image.open(io.BytesIO(enc)).convert("RGB"))
+    if timings is not None:
+        timings["parse"] = timings.get("parse", 0.0) + (t1 - t0)
+        timings["decode"] = timings.get("decode", 0.0) + (time.perf_counter() - t1)
 
     def boxes(prefix):
         cols = [np.asarray(f.get(prefix + k, np.zeros(0, np.float32)), np.float32) for k in ("ymin", "xmin", "ymax", "xmax")]
@@ -347,6 +362,13 @@ def collate(examples):
     if len(shapes) != 1:
         raise ValueError("images of one batch must share a shape, got %s" % sorted(shapes))
     out = {"images": torch.from_numpy(np.ascontiguousarray(np.stack([e["image"] for e in examples]), np.float32))}
+    out.update(collate_labels(examples))
+    return out
+
+
+def collate_labels(examples):
+    """Every field of a collated batch but `images` (label lists, evaluation flags, names), in collate's order."""
+    out = {}
     for k in ("groundtruth_boxes", "groundtruth_classes", "groundtruth_closeness", "window_boxes", "window_classes",
               "groundtruth_edgemask"):
         if all(k in e for e in examples):

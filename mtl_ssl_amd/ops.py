@@ -7,6 +7,7 @@ Names follow the reference operators they replace (see include/mtlssl_hip.h).
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from .lib import ConvDesc, lib, ptr
@@ -1158,6 +1159,37 @@ def resize_bilinear_fwd(x, OH, OW):
     y = torch.empty((N, OH, OW, C), dtype=f32, device=x.device)
     lib().resize_bilinear_fwd(ptr(_chk(x)), ptr(y), N, H, W, C, OH, OW, _stream())
     return y
+
+
+# mtlssl_image_desc of include/mtlssl_hip.h
+IMAGE_DESC = np.dtype({"names": ["offset", "H", "W", "flip", "sy", "sx", "pad"],
+                       "formats": ["<i8", "<i4", "<i4", "<i4", "<f4", "<f4", "<i4"],
+                       "offsets": [0, 8, 12, 16, 20, 24, 28], "itemsize": 32})
+
+
+def image_descs(shapes, flips, OH, OW):
+    """Descriptors of uint8 [H,W,3] images packed back to back -> (IMAGE_DESC array, total pixel bytes). The scales
+    are float32(H / OH), float32(W / OW): the rounding of preprocessor.resize_bilinear_legacy."""
+    d = np.zeros(len(shapes), IMAGE_DESC)
+    off = 0
+    for i, ((H, W), f) in enumerate(zip(shapes, flips)):
+        assert H >= 1 and W >= 1, (H, W)
+        d[i] = (off, H, W, int(bool(f)), np.float32(H / OH), np.float32(W / OW), 0)
+        off += int(H) * int(W) * 3
+    return d, off
+
+
+def prepare_images(pixels, desc, B, OH, OW, out=None):
+    """float32 [B,OH,OW,3] = resize_bilinear_legacy(flip(float32(image))) of B uint8 images (mtlssl_prepare_images).
+    pixels: device uint8 tensor of the packed images; desc: device uint8 tensor of B IMAGE_DESC entries (8-byte
+    aligned) whose offsets and sizes the caller made from image_descs, so every read stays inside `pixels`."""
+    assert pixels.is_cuda and pixels.dtype == torch.uint8 and desc.is_cuda and desc.dtype == torch.uint8
+    assert desc.numel() >= B * IMAGE_DESC.itemsize and desc.data_ptr() % 8 == 0
+    if out is None:
+        out = torch.empty((B, OH, OW, 3), dtype=f32, device=pixels.device)
+    assert tuple(out.shape) == (B, OH, OW, 3)
+    lib().prepare_images(ptr(pixels), ptr(desc), B, OH, OW, ptr(_chk(out)), _stream())
+    return out
 
 
 def resize_bilinear_bwd(dy, in_shape):

@@ -32,6 +32,9 @@ def _flags(argv):
     ap.add_argument("--logtostderr", action="store_true")
     ap.add_argument("--num_steps", type=int, default=None, help="overrides train_config.num_steps")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--input_pipeline", choices=("async", "host"), default="async",
+                    help="async: decode workers + on-device flip / resize (mtl_ssl_amd.input_pipeline); host: the serial "
+                         "generator input_reader.batches (the same batches, bit for bit)")
     return ap.parse_args(argv)
 
 
@@ -66,6 +69,27 @@ def record_paths(input_config):
     return paths
 
 
+def record_batches(kind, paths, num_classes, batch_size, augmentation_options, rng, device, input_config,
+                   prefetch=10, **kw):
+    """The batches of input_reader.batches with `images` on `device`: 'async' = mtl_ssl_amd.input_pipeline
+    (input_reader.proto num_readers decode workers, train.proto prefetch_queue_capacity batches ahead), 'host' = the
+    serial generator, images copied at hand-out."""
+    from . import input_pipeline, input_reader
+    if kind == "async":
+        local = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
+        workers = input_pipeline.default_num_workers(int(input_config.get("num_readers", 8) or 8), local)
+        return input_pipeline.InputPipeline(paths, num_classes, batch_size, augmentation_options, rng, device=device,
+                                            num_workers=workers, prefetch=max(1, prefetch), **kw)
+    if kind != "host":
+        raise ValueError("input pipeline %r: async or host" % kind)
+
+    def gen():
+        for b in input_reader.batches(paths, num_classes, batch_size, augmentation_options, rng, **kw):
+            b["images"] = b["images"].to(device, non_blocking=True)
+            yield b
+    return gen()
+
+
 def main(argv=None):
     f = _flags(sys.argv[1:] if argv is None else argv)
     if f.num_clones != 1 or f.worker_replicas != 1 or f.ps_tasks != 0:
@@ -77,7 +101,7 @@ def main(argv=None):
     import torch
     import torch.distributed as dist
     import __graft_entry__ as ge
-    from . import input_reader, model_builder, trainer
+    from . import model_builder, trainer
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if rank == 0:
@@ -98,26 +122,29 @@ def main(argv=None):
         B //= world
     probe = model_builder.build(model_config, True, dev, seed=f.seed)
     rz = model_config.faster_rcnn.image_resizer
-    stream = input_reader.batches(record_paths(input_config), K, B, train_config.data_augmentation_options,
-                                  np.random.RandomState(f.seed + rank), loop=True, rank=rank, world=world,
-                                  # protos/input_reader.proto: shuffle (default true) draws from a queue that holds
-                                  # at least min_after_dequeue (default 1000) serialized records
-                                  shuffle_buffer=int(input_config.get("min_after_dequeue", 1000) or 0)
-                                  if input_config.get("shuffle", True) else 0,
-                                  resized_shape=lambda h, w: probe.resized_shape(h, w, rz),
-                                  max_pending=64 if world == 1 else 256)
+    stream = record_batches(f.input_pipeline, record_paths(input_config), K, B, train_config.data_augmentation_options,
+                            np.random.RandomState(f.seed + rank), dev, input_config, loop=True, rank=rank, world=world,
+                            # protos/input_reader.proto: shuffle (default true) draws from a queue that holds
+                            # at least min_after_dequeue (default 1000) serialized records
+                            shuffle_buffer=int(input_config.get("min_after_dequeue", 1000) or 0)
+                            if input_config.get("shuffle", True) else 0,
+                            resized_shape=lambda h, w: probe.resized_shape(h, w, rz),
+                            max_pending=64 if world == 1 else 256,
+                            prefetch=int(train_config.prefetch_queue_capacity))
 
     def next_batch():
-        b = next(stream)
-        b["images"] = b["images"].to(dev, non_blocking=True)
-        return b
+        return next(stream)
     os.makedirs(f.train_dir, exist_ok=True)
     if rank == 0 and f.pipeline_config_path:          # train.py:235-247 keeps the configuration beside the checkpoints
         with open(os.path.join(f.train_dir, "pipeline.config"), "w") as out:
             out.write(open(f.pipeline_config_path).read())
-    trainer.train(next_batch, lambda: probe, train_config, master=f.master, task=rank, num_clones=1,
-                  worker_replicas=world, is_chief=rank == 0, train_dir=f.train_dir, model_config=model_config,
-                  num_steps=f.num_steps)
+    try:
+        trainer.train(next_batch, lambda: probe, train_config, master=f.master, task=rank, num_clones=1,
+                      worker_replicas=world, is_chief=rank == 0, train_dir=f.train_dir, model_config=model_config,
+                      num_steps=f.num_steps)
+    finally:
+        if hasattr(stream, "close"):
+            stream.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
