@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 9
+#define MTLSSL_ABI_VERSION 10
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -463,6 +463,20 @@ typedef struct {
 } mtlssl_image_desc;         /* 32 bytes */
 int mtlssl_prepare_images(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW, float* out,
                           mtlssl_stream_t stream);
+/* mtlssl_prepare_images with the photometric augmentations of core/preprocessor.py (normalize_image :120,
+ * subtract_channel_mean :1490, random_adjust_brightness / contrast / hue / saturation :459-540, random_distort_color
+ * :542, random_rgb_to_gray :430, random_pixel_value_scale :347, random_black_patches :1189) and random_horizontal_flip
+ * applied at the source resolution before the resize, in config order. `prog` (HOST memory) holds n_ops <= 128 op
+ * codes, the same for every image; `params` (device) holds B x P float32 parameters, P the sum of the ops' parameter
+ * counts (mtl_ssl_amd.preprocessor: OP_* codes, OP_PARAMS counts, plan() fills them, apply_program restates every op
+ * on the host). desc[n].flip mirrors the source before the program. Each contrast op adds two small launches that
+ * compute its per-channel means in float64 (row sums, then rows ascending) into `workspace`, which must hold
+ * mtlssl_prepare_images_aug_workspace(B, contrast ops, max_H) bytes, max_H >= every image's H. An empty program
+ * gives mtlssl_prepare_images's output. */
+int64_t mtlssl_prepare_images_aug_workspace(int B, int n_contrast, int max_H);
+int mtlssl_prepare_images_aug(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
+                              const int32_t* prog, int n_ops, const float* params, int P, int max_H, void* workspace,
+                              int64_t workspace_bytes, float* out, mtlssl_stream_t stream);
 
 /* ------------------------------------------------------------------ loss family
  * Fused loss + gradient. Every loss is a weighted sum of per-row terms; `row_loss_out[rows]`

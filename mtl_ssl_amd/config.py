@@ -60,9 +60,16 @@ FIELD_KIND = {
     "constant_learning_rate": "ConstantLearningRate",
     "exponential_decay_learning_rate": "ExponentialDecayLearningRate", "schedule": "LearningRateSchedule",
     "hard_example_miner": "HardExampleMiner",
+    # protos/preprocessor.proto: the PreprocessingStep options mtl_ssl_amd.preprocessor runs
+    "random_horizontal_flip": "RandomHorizontalFlip", "normalize_image": "NormalizeImage",
+    "subtract_channel_mean": "SubtractChannelMean", "random_adjust_brightness": "RandomAdjustBrightness",
+    "random_adjust_contrast": "RandomAdjustContrast", "random_adjust_saturation": "RandomAdjustSaturation",
+    "random_adjust_hue": "RandomAdjustHue", "random_distort_color": "RandomDistortColor",
+    "random_rgb_to_gray": "RandomRGBtoGray", "random_pixel_value_scale": "RandomPixelValueScale",
+    "random_black_patches": "RandomBlackPatches", "random_jitter_boxes": "RandomJitterBoxes",
 }
 REPEATED = {"scales", "aspect_ratios", "schedule", "data_augmentation_options", "input_path",
-            "freeze_variables", "eval_metric_index", "metrics_set"}
+            "freeze_variables", "eval_metric_index", "metrics_set", "means"}
 
 DEFAULTS = {
     "DetectionModel": {"init_file": "", "mtl": "@MTL"},
@@ -137,6 +144,19 @@ DEFAULTS = {
     "ManualStepLearningRate": {"initial_learning_rate": 0.002, "schedule": []},
     "LearningRateSchedule": {"learning_rate": 0.002},
     "ConstantLearningRate": {"learning_rate": 0.002},
+    # protos/preprocessor.proto (the options of mtl_ssl_amd.preprocessor; the reference's functions default alike)
+    "RandomHorizontalFlip": {},
+    "NormalizeImage": {"original_minval": 0.0, "original_maxval": 0.0, "target_minval": 0, "target_maxval": 1},
+    "SubtractChannelMean": {"means": []},
+    "RandomAdjustBrightness": {"max_delta": 0.2},
+    "RandomAdjustContrast": {"min_delta": 0.8, "max_delta": 1.25},
+    "RandomAdjustSaturation": {"min_delta": 0.8, "max_delta": 1.25},
+    "RandomAdjustHue": {"max_delta": 0.02},
+    "RandomDistortColor": {"color_ordering": 0},
+    "RandomRGBtoGray": {"probability": 0.1},
+    "RandomPixelValueScale": {"minval": 0.9, "maxval": 1.1},
+    "RandomBlackPatches": {"max_black_patches": 10, "probability": 0.5, "size_to_image_ratio": 0.1},
+    "RandomJitterBoxes": {"ratio": 0.05},
 }
 
 _TOKEN = re.compile(r'\s*(?:(#[^\n]*)|("(?:[^"\\]|\\.)*"|\'(?:[^\'\\]|\\.)*\')|([{}<>:\[\],])|([^\s{}<>:\[\],#"\']+))')

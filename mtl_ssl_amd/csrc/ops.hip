@@ -668,6 +668,243 @@ __global__ void k_prepare_images(const uint8_t* __restrict__ pixels, const mtlss
     o[c] = resize_blend((float)r0[x0 * 3 + c], (float)r0[x1 * 3 + c], (float)r1[x0 * 3 + c], (float)r1[x1 * 3 + c],
                         yl, xl);
 }
+// Photometric augmentation inside the preparation (core/preprocessor.py normalize_image, subtract_channel_mean,
+// random_adjust_{brightness,contrast,saturation,hue}, random_distort_color, random_rgb_to_gray,
+// random_pixel_value_scale, random_black_patches): a program of primitive ops, the same for every image, with B x P
+// float32 parameters, evaluated on each source tap before the legacy resize. The float32 sequence of every op is
+// restated on the host by mtl_ssl_amd.preprocessor.apply_program (op codes and parameter counts: OP_* / OP_PARAMS
+// there); this file is built with -ffp-contract=off, so the two agree to the bit.
+enum : int {
+  kAugFlip = 0, kAugNormalize, kAugSubMean, kAugAdd, kAugContrast, kAugSaturation, kAugHue, kAugClip, kAugGray,
+  kAugPixelScale, kAugPatch, kAugNumOps
+};
+constexpr int kAugMaxOps = 128;
+constexpr uint32_t kAugPixelScaleStream = 0x50584C53u;
+struct AugProgram {            // passed by value: the host validates it and plans the contrast pre-passes
+  int n;
+  int8_t code[kAugMaxOps];
+};
+__host__ __device__ __forceinline__ int aug_nparams(int code) {
+  return code == kAugNormalize || code == kAugSubMean || code == kAugPixelScale ? 3
+         : code == kAugClip                                                      ? 0
+         : code == kAugPatch                                                     ? 4
+                                                                                 : 1;
+}
+__device__ __forceinline__ uint32_t aug_mix32(uint32_t seed, uint32_t stream, uint32_t i) {   // glue.hip glue_mix32
+  uint32_t x = i + 0x9E3779B9u * seed + 0x85EBCA6Bu * stream;
+  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ float aug_clip01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+// TF 1.7 adjust_hue_op.cc: rgb_to_hv_range, the hue rotation with its `while` wraps, hv_range_to_rgb.
+__device__ __forceinline__ void aug_hue(float v[3], float delta) {
+  const float r = v[0], g = v[1], b = v[2];
+  float vmax, vmid, vmin;
+  int cat;
+  if (r < g) {
+    if (b < r)      { vmax = g; vmid = r; vmin = b; cat = 1; }
+    else if (b > g) { vmax = b; vmid = g; vmin = r; cat = 3; }
+    else            { vmax = g; vmid = b; vmin = r; cat = 2; }
+  } else {
+    if (b < g)      { vmax = r; vmid = g; vmin = b; cat = 0; }
+    else if (b > r) { vmax = b; vmid = r; vmin = g; cat = 4; }
+    else            { vmax = r; vmid = b; vmin = g; cat = 5; }
+  }
+  float h = 0.f;
+  if (vmax != vmin) {
+    const float ratio = (vmid - vmin) / (vmax - vmin);
+    h = (float)cat + ((cat & 1) == 0 ? ratio : 1.f - ratio);
+  }
+  h = h + delta * 6.f;
+  while (h < 0.f) h = h + 6.f;
+  while (h >= 6.f) h = h - 6.f;
+  const int c = (int)h;
+  float ratio = h - (float)c;
+  if (c & 1) ratio = 1.f - ratio;
+  vmid = vmin + ratio * (vmax - vmin);
+  switch (c) {
+    case 0: v[0] = vmax; v[1] = vmid; v[2] = vmin; break;
+    case 1: v[0] = vmid; v[1] = vmax; v[2] = vmin; break;
+    case 2: v[0] = vmin; v[1] = vmax; v[2] = vmid; break;
+    case 3: v[0] = vmin; v[1] = vmid; v[2] = vmax; break;
+    case 4: v[0] = vmid; v[1] = vmin; v[2] = vmax; break;
+    default: v[0] = vmax; v[1] = vmin; v[2] = vmid; break;
+  }
+}
+// TF 1.7 adjust_saturation_op.cc: rgb_to_hsv (its 2/6 and 4/6 are double constants), s = min(1, max(0, s * k)),
+// hsv_to_rgb with its `while` wraps.
+__device__ __forceinline__ void aug_saturation(float v[3], float k) {
+  const float r = v[0], g = v[1], b = v[2];
+  const float vv = fmaxf(r, fmaxf(g, b));
+  const float range = vv - fminf(r, fminf(g, b));
+  float s = vv > 0.f ? range / vv : 0.f;
+  const float norm = 1.f / (6.f * range);
+  float hh;
+  if (r == vv) hh = norm * (g - b);
+  else if (g == vv) hh = (float)((double)(norm * (b - r)) + 2.0 / 6.0);
+  else hh = (float)((double)(norm * (r - g)) + 4.0 / 6.0);
+  if (range <= 0.f) hh = 0.f;
+  if (hh < 0.f) hh = hh + 1.f;
+  s = fminf(1.f, fmaxf(0.f, s * k));
+  const float c = s * vv, m = vv - c, dh = hh * 6.f;
+  const int cat = (int)dh;
+  float f = dh;
+  while (f <= 0.f) f = f + 2.f;
+  while (f >= 2.f) f = f - 2.f;
+  const float x = c * (1.f - fabsf(f - 1.f));
+  float rr = 0.f, gg = 0.f, bb = 0.f;
+  switch (cat) {
+    case 0: rr = c; gg = x; break;
+    case 1: rr = x; gg = c; break;
+    case 2: gg = c; bb = x; break;
+    case 3: gg = x; bb = c; break;
+    case 4: rr = x; bb = c; break;
+    case 5: rr = c; bb = x; break;
+    default: break;
+  }
+  v[0] = rr + m; v[1] = gg + m; v[2] = bb + m;
+}
+// The 3 channels of pixel (y, x) of image n after the first `n_ops` ops, (y, x) in that stage's coordinates (flips
+// mirror the columns). prm: the image's P parameters; means: its contrast means, [contrast op][3].
+__device__ __forceinline__ void aug_pixel(const uint8_t* __restrict__ src, int H, int W, bool src_flip, int y, int x,
+                                          const AugProgram& pr, int n_ops, const float* __restrict__ prm,
+                                          const float* __restrict__ means, float v[3]) {
+  int k = 0, cx = x;
+  for (int i = 0; i < n_ops; ++i) {                      // the column at stage 0
+    const int code = pr.code[i];
+    if (code == kAugFlip && prm[k] != 0.f) cx = W - 1 - cx;
+    k += aug_nparams(code);
+  }
+  const int sx = src_flip ? W - 1 - cx : cx;
+  const uint8_t* s = src + ((int64_t)y * W + sx) * 3;
+  v[0] = (float)s[0]; v[1] = (float)s[1]; v[2] = (float)s[2];
+  k = 0;
+  int nc = 0;
+  for (int i = 0; i < n_ops; ++i) {
+    const int code = pr.code[i];
+    const float* p = prm + k;
+    k += aug_nparams(code);
+    switch (code) {
+      case kAugFlip:
+        if (p[0] != 0.f) cx = W - 1 - cx;
+        break;
+      case kAugNormalize:
+        for (int c = 0; c < 3; ++c) v[c] = (v[c] - p[0]) * p[1] + p[2];
+        break;
+      case kAugSubMean:
+        for (int c = 0; c < 3; ++c) v[c] = v[c] - p[c];
+        break;
+      case kAugAdd:
+        for (int c = 0; c < 3; ++c) v[c] = v[c] + p[0];
+        break;
+      case kAugContrast: {
+        const float* m = means + nc * 3;
+        ++nc;
+        for (int c = 0; c < 3; ++c) v[c] = (v[c] - m[c]) * p[0] + m[c];
+        break;
+      }
+      case kAugSaturation: aug_saturation(v, p[0]); break;
+      case kAugHue: aug_hue(v, p[0]); break;
+      case kAugClip:
+        for (int c = 0; c < 3; ++c) v[c] = aug_clip01(v[c]);
+        break;
+      case kAugGray:
+        if (p[0] != 0.f) {
+          const float gray = (v[0] * 0.2989f + v[1] * 0.5870f) + v[2] * 0.1140f;
+          v[0] = gray; v[1] = gray; v[2] = gray;
+        }
+        break;
+      case kAugPixelScale: {
+        const uint32_t seed = __float_as_uint(p[0]);
+        const uint32_t e = ((uint32_t)y * (uint32_t)W + (uint32_t)cx) * 3u;
+        for (int c = 0; c < 3; ++c) {
+          const float u = (float)(aug_mix32(seed, kAugPixelScaleStream, e + c) >> 8) * 0x1p-24f;
+          v[c] = v[c] * (p[1] + p[2] * u);
+        }
+        break;
+      }
+      case kAugPatch:
+        if (p[0] != 0.f) {
+          const int y0 = (int)p[1], x0 = (int)p[2], box = (int)p[3];
+          if (y >= y0 && y < y0 + box && cx >= x0 && cx < x0 + box)
+            for (int c = 0; c < 3; ++c) v[c] = v[c] * 0.f;
+        }
+        break;
+      default: break;
+    }
+  }
+}
+// Contrast pre-pass, one launch pair per contrast op of the program (op index `stage`): k_aug_rowsum sums each row
+// of the image after the ops before it in float64, x ascending (one thread per row); k_aug_mean adds the row sums
+// ascending and writes float32(sum / (H * W)) per channel — preprocessor.contrast_mean's order.
+__global__ void k_aug_rowsum(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
+                             AugProgram pr, int stage, const float* __restrict__ params, int P,
+                             const float* __restrict__ means, int n_contrast, int max_H, double* __restrict__ rows) {
+  const int n = blockIdx.y;
+  const int y = blockIdx.x * blockDim.x + threadIdx.x;
+  const mtlssl_image_desc d = desc[n];
+  if (y >= d.H || y >= max_H) return;
+  const uint8_t* src = pixels + d.offset;
+  const float* prm = params + (int64_t)n * P;
+  const float* mn = means + (int64_t)n * n_contrast * 3;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int x = 0; x < d.W; ++x) {
+    float v[3];
+    aug_pixel(src, d.H, d.W, d.flip != 0, y, x, pr, stage, prm, mn, v);
+    s0 += (double)v[0]; s1 += (double)v[1]; s2 += (double)v[2];
+  }
+  double* o = rows + ((int64_t)n * max_H + y) * 3;
+  o[0] = s0; o[1] = s1; o[2] = s2;
+}
+__global__ void k_aug_mean(const mtlssl_image_desc* __restrict__ desc, int slot, int n_contrast, int max_H,
+                           const double* __restrict__ rows, float* __restrict__ means) {
+  const int n = blockIdx.x, c = threadIdx.x;
+  if (c >= 3) return;
+  const mtlssl_image_desc d = desc[n];
+  float m = __builtin_nanf("");                          // an image taller than max_H: visibly wrong, never a stray read
+  if (d.H <= max_H) {
+    const double* r = rows + (int64_t)n * max_H * 3 + c;
+    double t = 0.0;
+    for (int y = 0; y < d.H; ++y) t += r[(int64_t)y * 3];
+    m = (float)(t / (double)((int64_t)d.H * d.W));
+  }
+  means[((int64_t)n * n_contrast + slot) * 3 + c] = m;
+}
+// k_prepare_images with the program applied to each of the four taps before the blend (and to the single tap of the
+// no-resize case). desc.flip mirrors the source before the program, as in k_prepare_images.
+__global__ void k_prepare_images_aug(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
+                                     int OH, int OW, AugProgram pr, const float* __restrict__ params, int P,
+                                     const float* __restrict__ means, int n_contrast, float* __restrict__ out) {
+  const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (p >= (int64_t)OH * OW) return;
+  const int n = blockIdx.y;
+  const mtlssl_image_desc d = desc[n];
+  const int H = d.H, W = d.W;
+  const bool fl = d.flip != 0;
+  const uint8_t* src = pixels + d.offset;
+  const float* prm = params + (int64_t)n * P;
+  const float* mn = means + (int64_t)n * n_contrast * 3;
+  const int oy = (int)(p / OW), ox = (int)(p % OW);
+  float* o = out + ((int64_t)n * OH * OW + p) * 3;
+  if (H == OH && W == OW) {
+    float v[3];
+    aug_pixel(src, H, W, fl, oy, ox, pr, pr.n, prm, mn, v);
+    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+    return;
+  }
+  int y0, y1, x0, x1;
+  float yl, xl;
+  resize_taps(oy, d.sy, H, y0, y1, yl);
+  resize_taps(ox, d.sx, W, x0, x1, xl);
+  y0 = min(y0, H - 1); x0 = min(x0, W - 1);
+  float tl[3], tr[3], bl[3], br[3];
+  aug_pixel(src, H, W, fl, y0, x0, pr, pr.n, prm, mn, tl);
+  aug_pixel(src, H, W, fl, y0, x1, pr, pr.n, prm, mn, tr);
+  aug_pixel(src, H, W, fl, y1, x0, pr, pr.n, prm, mn, bl);
+  aug_pixel(src, H, W, fl, y1, x1, pr, pr.n, prm, mn, br);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c] = resize_blend(tl[c], tr[c], bl[c], br[c], yl, xl);
+}
 // Gradient of the resize as a GATHER (one thread per input element sums, in a fixed order, the output pixels
 // whose two source rows / columns include it): no float atomics, run-to-run bit-identical. The candidate
 // output rows of input row iy are those with floor(oy * sy) in {iy - 1, iy}; each is re-checked with the
@@ -1329,6 +1566,49 @@ int mtlssl_prepare_images(const uint8_t* pixels, const mtlssl_image_desc* desc, 
   hipLaunchKernelGGL(k_prepare_images, dim3((unsigned)cdiv(pix, 256), (unsigned)B), dim3(256), 0, S(stream), pixels,
                      desc, OH, OW, out);
   return check_launch("prepare_images");
+}
+int64_t mtlssl_prepare_images_aug_workspace(int B, int n_contrast, int max_H) {
+  if (B <= 0 || n_contrast <= 0) return 0;
+  const int64_t means = ((int64_t)B * n_contrast * 3 * 4 + 255) / 256 * 256;
+  return means + (int64_t)B * max_H * 3 * 8;
+}
+int mtlssl_prepare_images_aug(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
+                              const int32_t* prog, int n_ops, const float* params, int P, int max_H, void* workspace,
+                              int64_t workspace_bytes, float* out, mtlssl_stream_t stream) {
+  MTLSSL_REQUIRE(B >= 0 && B <= 65535 && OH > 0 && OW > 0, "prepare_images_aug: bad geometry");
+  MTLSSL_REQUIRE(n_ops >= 0 && n_ops <= kAugMaxOps, "prepare_images_aug: %d ops, at most %d", n_ops, kAugMaxOps);
+  MTLSSL_REQUIRE(n_ops == 0 || prog, "prepare_images_aug: null program");
+  AugProgram pr;
+  pr.n = n_ops;
+  int need = 0, n_contrast = 0;
+  for (int i = 0; i < n_ops; ++i) {
+    MTLSSL_REQUIRE(prog[i] >= 0 && prog[i] < kAugNumOps, "prepare_images_aug: bad op code %d at op %d", prog[i], i);
+    pr.code[i] = (int8_t)prog[i];
+    need += aug_nparams(prog[i]);
+    n_contrast += prog[i] == kAugContrast;
+  }
+  MTLSSL_REQUIRE(P == need, "prepare_images_aug: the program takes %d parameters per image, P = %d", need, P);
+  MTLSSL_REQUIRE(P == 0 || B == 0 || params, "prepare_images_aug: null parameters");
+  const int64_t ws = mtlssl_prepare_images_aug_workspace(B, n_contrast, max_H);
+  MTLSSL_REQUIRE(n_contrast == 0 || (max_H >= 1 && workspace && workspace_bytes >= ws),
+                 "prepare_images_aug: %d contrast ops need max_H >= 1 and %lld workspace bytes, got max_H = %d and %lld",
+                 n_contrast, (long long)ws, max_H, (long long)workspace_bytes);
+  if (!B) return MTLSSL_OK;
+  float* means = static_cast<float*>(workspace);
+  double* rows = n_contrast ? reinterpret_cast<double*>(static_cast<char*>(workspace) + (ws - (int64_t)B * max_H * 24))
+                            : nullptr;
+  for (int i = 0, slot = 0; i < n_ops; ++i) {
+    if (pr.code[i] != kAugContrast) continue;
+    hipLaunchKernelGGL(k_aug_rowsum, dim3((unsigned)cdiv(max_H, 64), (unsigned)B), dim3(64), 0, S(stream), pixels,
+                       desc, pr, i, params, P, means, n_contrast, max_H, rows);
+    hipLaunchKernelGGL(k_aug_mean, dim3((unsigned)B), dim3(64), 0, S(stream), desc, slot, n_contrast, max_H, rows,
+                       means);
+    ++slot;
+  }
+  const int64_t pix = (int64_t)OH * OW;
+  hipLaunchKernelGGL(k_prepare_images_aug, dim3((unsigned)cdiv(pix, 256), (unsigned)B), dim3(256), 0, S(stream),
+                     pixels, desc, OH, OW, pr, params, P, means, n_contrast, out);
+  return check_launch("prepare_images_aug");
 }
 int mtlssl_resize_bilinear_bwd(const float* dy, float* dx, int N, int H, int W, int C, int OH,
                                int OW, mtlssl_stream_t stream) {

@@ -1,20 +1,24 @@
 """Asynchronous TFRecord input: the batches of `input_reader.batches`, decoded in worker processes a few batches
-ahead of the step, flipped and resized on the device.
+ahead of the step, augmented and resized on the device.
 
 The reference overlaps its input with the step through parallel readers and prefetch / batch queues
 (protos/input_reader.proto:39 `num_readers`, protos/train.proto:57-63 `prefetch_queue_capacity`). Here:
 
 * The consuming process replays the record stream of `input_reader.examples` exactly (rank sharding, the shuffle
-  buffer, one uniform draw per listed `random_horizontal_flip`, the same RandomState in the same order). Only the
-  framing of a TFRecord is read here; the draws do not depend on pixels.
+  buffer, the fixed number of uniform draws of every listed augmentation option (`preprocessor.Step.draws`), the
+  same RandomState in the same order). Only the framing of a TFRecord is read here; the draws do not depend on
+  pixels or boxes.
 * Worker processes (the `spawn` context: a process that has initialised HIP is never forked, and a worker never
-  imports torch) read the record, parse the tf.Example, decode the image to uint8 and flip the labels with the
-  consumer's draws (`preprocessor.preprocess`, replayed); they return the image and the flag the image flip uses.
+  imports torch) read the record, parse the tf.Example, decode the image to uint8, turn the consumer's draws into
+  the image's float32 op parameters (`preprocessor.plan`: flip flags, jitter, colour deltas, patch corners, seeds)
+  and apply the label side (flips, box jitter); they return the image and its parameters.
 * The consumer buckets the decoded examples by resized shape exactly like `batches` (same flushes, same remainder).
-* On a GPU, a batch is packed into a pinned staging slot (descriptors + uint8 pixels), copied in one H2D copy and
-  turned into the float32 [B,OH,OW,3] batch by `ops.prepare_images` on a stream of its own; the consumer's stream
-  waits on the batch's event at hand-out. Copies and kernels are launched from the consumer's thread, so no second
-  Python thread competes with the step's launch thread. On the CPU, the host preparer runs today's numpy path.
+* On a GPU, a batch is packed into a pinned staging slot (descriptors + op parameters + uint8 pixels), copied in one
+  H2D copy and turned into the float32 [B,OH,OW,3] batch on a stream of its own: `ops.prepare_images` when the
+  options are flips only, `ops.prepare_images_aug` (the op program before the resize) otherwise. The consumer's
+  stream waits on the batch's event at hand-out. Copies and kernels are launched from the consumer's thread, so no
+  second Python thread competes with the step's launch thread. On the CPU, the host preparer runs the numpy path
+  (`preprocessor.apply_program`, then `resize_bilinear_legacy`).
 """
 import collections
 import multiprocessing
@@ -29,17 +33,10 @@ import numpy as np
 from . import input_reader, preprocessor
 
 
-def flip_option_count(augmentation_options):
-    """How many random_horizontal_flip draws `preprocessor.preprocess` makes per example (a config may list the
-    option more than once); other options are refused, as preprocess refuses them."""
-    n = 0
-    for opt in augmentation_options:
-        for kind in (list(opt.keys()) if hasattr(opt, "keys") else [opt]):
-            if kind != "random_horizontal_flip":
-                raise ValueError("data augmentation %r is not supported (the reference's configs only "
-                                 "use random_horizontal_flip)" % kind)
-            n += 1
-    return n
+def option_draw_counts(augmentation_options):
+    """The uniform draws `preprocessor.preprocess` makes per example for each listed option, in config order
+    (refusing what preprocess refuses)."""
+    return [s.draws for s in preprocessor.parse_options(augmentation_options, warn=False)]
 
 
 def default_num_workers(num_readers=8, local_ranks=1):
@@ -71,32 +68,21 @@ def record_spans(path):
             pos += 16 + n
 
 
-class _Draws:
-    """Replays the consumer's uniform draws into preprocessor.preprocess inside a worker."""
-
-    def __init__(self, draws):
-        self.draws = list(draws)
-
-    def uniform(self):
-        return self.draws.pop(0)
-
-
-_NO_IMAGE = np.zeros((0, 0, 3), np.uint8)
-
-
-def decode_record(serialized, num_classes, augmentation_options, draws, timings=None):
-    """-> (example with a uint8 image and flipped labels, image flip flag). `draws`: the consumer's uniform draws of
-    this record, one per random_horizontal_flip. random_horizontal_flip flips only an image with boxes, and two flips
-    cancel on the image (the labels are flipped one after the other, like the host path: 1 - (1 - x) need not be x)."""
+def decode_record(serialized, num_classes, steps, draws, timings=None):
+    """-> (example with a uint8 image and augmented labels, float32 op parameters of the image). `steps`: the parsed
+    options (preprocessor.parse_options); `draws`: the consumer's uniform draws of this record (preprocessor.preprocess
+    takes the same ones up front). The labels are flipped / jittered one action after the other, like the host path
+    (1 - (1 - x) need not be x)."""
     ex = input_reader.decode_example_uint8(serialized, num_classes, timings)
     image = ex.pop("image")
-    ex = preprocessor.preprocess(dict(ex, image=_NO_IMAGE), augmentation_options, _Draws(draws))
-    flip = ex["groundtruth_boxes"].size > 0 and sum(float(u) > 0.5 for u in draws) % 2 == 1
+    params, actions = preprocessor.plan(steps, draws, image.shape[0], image.shape[1],
+                                        np.asarray(ex["groundtruth_boxes"]).reshape(-1, 4).shape[0])
+    ex = preprocessor.apply_labels(ex, actions)
     ex["image"] = image
-    return ex, bool(flip)
+    return ex, params
 
 
-def _worker_main(tasks, results, num_classes, augmentation_options):
+def _worker_main(tasks, results, num_classes, steps):
     files = {}
     while True:
         task = tasks.get()
@@ -112,10 +98,10 @@ def _worker_main(tasks, results, num_classes, augmentation_options):
             data = f.read(length)
             if len(data) != length:
                 raise IOError("truncated record")
-            ex, flip = decode_record(data, num_classes, augmentation_options, draws, timings)
-            results.put((seq, ex, flip, timings, None))
+            ex, params = decode_record(data, num_classes, steps, draws, timings)
+            results.put((seq, ex, params, timings, None))
         except Exception as e:
-            results.put((seq, None, False, timings, "record %d of %s: %s: %s\n%s" % (
+            results.put((seq, None, None, timings, "record %d of %s: %s: %s\n%s" % (
                 index, path, type(e).__name__, e, traceback.format_exc())))
 
 
@@ -124,14 +110,16 @@ class InputPipelineError(RuntimeError):
 
 
 class _HostPreparer:
-    """Today's host path on the decoded uint8 images: float32 cast, flip, resize_bilinear_legacy, collate."""
+    """The host path on the decoded uint8 images: float32 cast, the op program (flips, colour ops, patches),
+    resize_bilinear_legacy, collate."""
+
+    def __init__(self, codes):
+        self.codes = codes
 
     def prepare(self, items, OH, OW):
         exs = []
-        for ex, flip in items:
-            img = np.asarray(ex["image"], np.float32)
-            if flip:
-                img = img[:, ::-1].copy()
+        for ex, params in items:
+            img = preprocessor.apply_program(np.asarray(ex["image"], np.float32), self.codes, params)
             exs.append(dict(ex, image=preprocessor.resize_bilinear_legacy(img, OH, OW)))
         return input_reader.collate(exs)
 
@@ -140,13 +128,18 @@ class _HostPreparer:
 
 
 class _DevicePreparer:
-    """Pinned staging ring -> one H2D copy + one mtlssl_prepare_images launch per batch on a dedicated stream."""
+    """Pinned staging ring -> one H2D copy + one mtlssl_prepare_images launch per batch on a dedicated stream (a
+    program of flips only: the net flip goes into the descriptor), or mtlssl_prepare_images_aug with the batch's
+    [B, P] op parameters staged between the descriptors and the pixels."""
 
     _ALIGN = 256
 
-    def __init__(self, device, slots, profile=False):
+    def __init__(self, device, slots, codes, profile=False):
         import torch
         self.torch = torch
+        self.codes = list(codes)
+        self.P = preprocessor.num_params(self.codes)
+        self.flips_only = all(c == preprocessor.OP_FLIP for c in self.codes)
         self.device = device
         self.stream = torch.cuda.Stream(device)
         self.slots = [None] * slots          # pinned uint8 staging buffers
@@ -158,8 +151,14 @@ class _DevicePreparer:
     def prepare(self, items, OH, OW):
         torch = self.torch
         from . import ops
-        desc, nbytes = ops.image_descs([ex["image"].shape[:2] for ex, _ in items], [f for _, f in items], OH, OW)
-        head = -(-desc.nbytes // self._ALIGN) * self._ALIGN
+        if self.flips_only:      # the net mirror of the listed flips (the flip flag is each op's one parameter)
+            flips, P = [int(np.count_nonzero(p)) % 2 == 1 for _, p in items], 0
+        else:
+            flips, P = [False] * len(items), self.P
+        desc, nbytes = ops.image_descs([ex["image"].shape[:2] for ex, _ in items], flips, OH, OW)
+        align = lambda n: -(-n // self._ALIGN) * self._ALIGN
+        poff = align(desc.nbytes)
+        head = poff + align(len(items) * P * 4)
         total = head + nbytes
         s = self.k % len(self.slots)
         self.k += 1
@@ -170,6 +169,8 @@ class _DevicePreparer:
             buf = self.slots[s] = torch.empty(total + total // 4, dtype=torch.uint8, pin_memory=True)
         host = buf.numpy()
         host[:desc.nbytes] = desc.view(np.uint8)
+        if P:
+            host[poff:poff + len(items) * P * 4] = np.stack([p for _, p in items]).astype(np.float32).view(np.uint8).reshape(-1)
         off = head
         for ex, _ in items:
             a = np.ascontiguousarray(ex["image"], np.uint8).reshape(-1)
@@ -183,7 +184,11 @@ class _DevicePreparer:
             dev.copy_(buf[:total], non_blocking=True)
             if ev:
                 ev[1].record(self.stream)
-            out = ops.prepare_images(dev[head:], dev[:desc.nbytes], len(items), OH, OW)
+            if self.flips_only:
+                out = ops.prepare_images(dev[head:], dev[:desc.nbytes], len(items), OH, OW)
+            else:
+                out = ops.prepare_images_aug(dev[head:], dev[:desc.nbytes], len(items), OH, OW, self.codes,
+                                             dev[poff:head], P, max(ex["image"].shape[0] for ex, _ in items))
             done = torch.cuda.Event(enable_timing=self.profile)
             done.record(self.stream)
         self.events[s] = done
@@ -224,7 +229,9 @@ class InputPipeline:
         self.num_classes = int(num_classes)
         self.batch_size = int(batch_size)
         self.options = list(augmentation_options or ())
-        self.n_draws = flip_option_count(self.options)
+        self.steps = preprocessor.parse_options(self.options)
+        self.codes = preprocessor.program(self.steps)
+        self.n_draws = preprocessor.draw_count(self.steps)
         self.rng = rng if rng is not None else np.random.RandomState(0)
         self.loop, self.rank, self.world, self.shuffle_buffer = loop, rank, world, int(shuffle_buffer)
         self.resized_shape, self.max_pending, self.drop_remainder = resized_shape, int(max_pending), drop_remainder
@@ -243,13 +250,13 @@ class InputPipeline:
         self._closed = False
         import torch
         dev = torch.device(device)
-        self._preparer = _HostPreparer() if dev.type == "cpu" else _DevicePreparer(dev, self.prefetch + 1, profile)
+        self._preparer = (_HostPreparer(self.codes) if dev.type == "cpu"
+                          else _DevicePreparer(dev, self.prefetch + 1, self.codes, profile))
         ctx = multiprocessing.get_context("spawn")
         self._tasks, self._results = ctx.Queue(), ctx.Queue()
         try:
             for _ in range(self.num_workers):
-                p = ctx.Process(target=_worker_main, args=(self._tasks, self._results, self.num_classes,
-                                                           ["random_horizontal_flip"] * self.n_draws),
+                p = ctx.Process(target=_worker_main, args=(self._tasks, self._results, self.num_classes, self.steps),
                                 daemon=True)
                 p.start()
                 self._procs.append(p)
@@ -290,7 +297,7 @@ class InputPipeline:
                 yield buf.pop()
 
         for rec in shuffled():
-            # preprocessor.random_horizontal_flip: one rng.uniform() per listed option, boxes or not
+            # preprocessor.preprocess: a fixed number of rng.uniform() per listed option, whatever the pixels or boxes
             yield rec, [float(rng.uniform()) for _ in range(self.n_draws)]
 
     def _submit(self):
@@ -305,10 +312,10 @@ class InputPipeline:
             self._seq_next += 1
 
     # ---------------------------------------------------------------- bucketing of input_reader.batches
-    def _bucket(self, ex, flip):
+    def _bucket(self, ex, params):
         H, W = ex["image"].shape[:2]
         key = tuple(self.resized_shape(H, W)) if self.resized_shape is not None else (H, W)
-        self._buckets.setdefault(key, []).append((ex, flip))
+        self._buckets.setdefault(key, []).append((ex, params))
         self._pending += 1
         if len(self._buckets[key]) == self.batch_size:
             self._pending -= self.batch_size
@@ -322,9 +329,9 @@ class InputPipeline:
         """The next assembled batch: None at the end of the stream, or (block=False) when none is assembled yet."""
         while not self._ready:
             while self._seq_want in self._done:              # bucket what has arrived, in stream order
-                ex, flip = self._done.pop(self._seq_want)
+                ex, params = self._done.pop(self._seq_want)
                 self._seq_want += 1
-                self._bucket(ex, flip)
+                self._bucket(ex, params)
             if self._ready:
                 break
             self._submit()
@@ -335,7 +342,7 @@ class InputPipeline:
                 self._buckets, self._pending = {}, 0
                 break
             try:
-                seq, ex, flip, timings, err = self._results.get(timeout=0.5) if block else self._results.get_nowait()
+                seq, ex, params, timings, err = self._results.get(timeout=0.5) if block else self._results.get_nowait()
             except queue.Empty:
                 if not block:
                     return None
@@ -346,7 +353,7 @@ class InputPipeline:
             self.timings.update(timings)
             if err is not None:
                 raise InputPipelineError("decoding failed: " + err)
-            self._done[seq] = (ex, flip)
+            self._done[seq] = (ex, params)
         return self._ready.popleft() if self._ready else None
 
     def _stage(self, ready):

@@ -1192,6 +1192,28 @@ def prepare_images(pixels, desc, B, OH, OW, out=None):
     return out
 
 
+def prepare_images_aug(pixels, desc, B, OH, OW, prog, params, P, max_H, out=None):
+    """prepare_images with an augmentation program applied at the source resolution before the resize
+    (mtlssl_prepare_images_aug) = resize_bilinear_legacy(preprocessor.apply_program(image)) per image. prog: the op
+    codes of preprocessor.program (a host sequence, checked by the library); params: a device tensor holding the
+    B x P float32 parameters of preprocessor.plan, 4-byte aligned; max_H >= the H of every image (it sizes the
+    contrast-mean workspace)."""
+    assert pixels.is_cuda and pixels.dtype == torch.uint8 and desc.is_cuda and desc.dtype == torch.uint8
+    assert desc.numel() >= B * IMAGE_DESC.itemsize and desc.data_ptr() % 8 == 0
+    assert params.is_cuda and params.data_ptr() % 4 == 0
+    assert params.numel() * params.element_size() >= B * P * 4, "params hold fewer than B x P floats"
+    from .preprocessor import OP_CONTRAST
+    codes = np.ascontiguousarray(prog, np.int32).reshape(-1)
+    if out is None:
+        out = torch.empty((B, OH, OW, 3), dtype=f32, device=pixels.device)
+    assert tuple(out.shape) == (B, OH, OW, 3)
+    nbytes = int(lib().prepare_images_aug_workspace(B, int((codes == OP_CONTRAST).sum()), int(max_H)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pixels.device) if nbytes else None
+    lib().prepare_images_aug(ptr(pixels), ptr(desc), B, OH, OW, codes.ctypes.data, len(codes), ptr(params), P,
+                             int(max_H), ptr(ws), nbytes, ptr(_chk(out)), _stream())
+    return out
+
+
 def resize_bilinear_bwd(dy, in_shape):
     N, H, W, C = in_shape
     dx = torch.zeros(in_shape, dtype=f32, device=dy.device)

@@ -11,6 +11,10 @@ Reports, in one JSON document:
             (parse / decode in the workers, staging in the consumer, H2D copy / prepare kernel on the device);
   train     ms/step of the configuration fed from records by each feed, and on synthetic device batches of the same
             shape in the same process. The training records are all landscape (one resized shape, the synthetic one).
+With --augment, the feed and train sections also report the feeds with AUGMENT (normalize to [0, 1], flip,
+random_distort_color, random_pixel_value_scale, random_black_patches, normalize back) as host_augment /
+async_augment, beside the flip-only ones from the same run (the augmented host generator is timed on fewer
+batches, and in the feed section only).
 Not part of bench.py."""
 import argparse
 import io
@@ -100,12 +104,22 @@ def host_speed(recs, jpegs):
             "edgemask_parse_ms": parse_ms - parse_plain_ms}
 
 
-def feed_kwargs(model_config, K, B):
+FLIP_ONLY = "train_config { data_augmentation_options { random_horizontal_flip { } } }"
+AUGMENT = """train_config {
+  data_augmentation_options { normalize_image { original_minval: 0 original_maxval: 255 target_minval: 0 target_maxval: 1 } }
+  data_augmentation_options { random_horizontal_flip { } }
+  data_augmentation_options { random_distort_color { } }
+  data_augmentation_options { random_pixel_value_scale { } }
+  data_augmentation_options { random_black_patches { } }
+  data_augmentation_options { normalize_image { original_minval: 0 original_maxval: 1 target_minval: 0 target_maxval: 255 } }
+}"""
+
+
+def feed_kwargs(model_config, K, B, options=FLIP_ONLY):
     from mtl_ssl_amd.frcnn import FasterRCNNMetaArch as M
     rz = model_config.faster_rcnn.image_resizer
     from mtl_ssl_amd import config
-    opts = config.parse_pipeline_config("train_config { data_augmentation_options { random_horizontal_flip { } } }"
-                                        ).train_config.data_augmentation_options
+    opts = config.parse_pipeline_config(options).train_config.data_augmentation_options
     return dict(num_classes=K, batch_size=B, augmentation_options=opts, loop=True, shuffle_buffer=16,
                 resized_shape=lambda h, w: M.resized_shape(h, w, rz))
 
@@ -121,15 +135,16 @@ def make_feed(kind, path, dev, kw, seed, workers=None, profile=False):
     return input_pipeline.InputPipeline([path], K, B, opts, rng, device=dev, num_workers=workers, profile=profile, **k)
 
 
-def feed_only(path, dev, kw, batches, workers):
+def feed_only(path, dev, feeds, batches, workers):
+    """feeds: {name: (host | async, feed kwargs, batches to time or None for `batches`)}."""
     import torch
     out = {}
-    for kind in ("host", "async"):
+    for name, (kind, kw, nb) in feeds.items():
         feed = make_feed(kind, path, dev, kw, 1, workers, profile=True)
         next(feed)                                 # worker start-up / first decode outside the timed region
         torch.cuda.synchronize()
         n, t = 0, time.perf_counter()
-        for _ in range(batches):
+        for _ in range(nb or batches):
             n += next(feed)["images"].shape[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t
@@ -146,15 +161,15 @@ def feed_only(path, dev, kw, batches, workers):
                        prepare_kernel_us_per_batch=1e6 * p / max(1, len(feed._preparer.timed)),
                        prepare_kernel_out_gb_per_s=12 * pix / max(p, 1e-9) / 1e9)
             feed.close()
-        out[kind] = row
+        out[name] = row
     return out
 
 
-def train_rates(cfg_path, path, dev, kw, steps, warmup, workers, HW):
+def train_rates(cfg_path, path, dev, feeds, steps, warmup, workers, HW):
     import torch
     from mtl_ssl_amd import config, model_builder, synthetic, trainer
     cfg = config.parse_pipeline_config(open(cfg_path).read())
-    B, K = kw["batch_size"], kw["num_classes"]
+    B, K = feeds["async"][1]["batch_size"], feeds["async"][1]["num_classes"]
     model = model_builder.build(cfg.model, True, dev, seed=0)
     tr = trainer.Trainer(model, cfg.train_config, 1)
     out = {}
@@ -173,14 +188,16 @@ def train_rates(cfg_path, path, dev, kw, steps, warmup, workers, HW):
             for i in range(4)]
     it = iter(range(10 ** 9))
     out["synthetic_ms_per_step"] = timed(lambda: dict(ring[next(it) % 4]))
-    for kind in ("host", "async"):
+    for name, (kind, kw, _) in feeds.items():
         feed = make_feed(kind, path, dev, kw, 2, workers)
-        out[kind + "_ms_per_step"] = timed(lambda: next(feed))
+        out[name + "_ms_per_step"] = timed(lambda: next(feed))
         if hasattr(feed, "close"):
             feed.close()
     out["synthetic_ms_per_step_again"] = timed(lambda: dict(ring[next(it) % 4]))
     out["async_over_synthetic"] = out["async_ms_per_step"] / min(out["synthetic_ms_per_step"],
                                                                out["synthetic_ms_per_step_again"])
+    if "async_augment" in feeds:
+        out["async_augment_over_async"] = out["async_augment_ms_per_step"] / out["async_ms_per_step"]
     return out
 
 
@@ -197,6 +214,7 @@ def main(argv=None):
     ap.add_argument("--skip", choices=("none", "feed", "train"), default="none")
     ap.add_argument("--workdir", default="/tmp/input_feed_rate")
     ap.add_argument("--out", default="")
+    ap.add_argument("--augment", action="store_true", help="also time the feeds with the AUGMENT options")
     a = ap.parse_args(argv)
     import torch
     import __graft_entry__ as ge
@@ -207,21 +225,26 @@ def main(argv=None):
     K = int(cfg.model.faster_rcnn.num_classes)
     dev = torch.device("cuda", 0)
     kw = feed_kwargs(cfg.model, K, a.batch)
+    feeds = {"host": ("host", kw, None), "async": ("async", kw, None)}
+    if a.augment:
+        akw = feed_kwargs(cfg.model, K, a.batch, AUGMENT)
+        feeds.update(host_augment=("host", akw, max(1, a.feed_batches // 6)), async_augment=("async", akw, None))
     mixed = os.path.join(a.workdir, "mixed.record")
     recs, jpegs = write_records(mixed, a.records, SHAPES[a.kind], K, 0)
-    res = {"config": os.path.relpath(a.config, ROOT), "kind": a.kind, "shapes_hw": SHAPES[a.kind],
+    res = {"config": os.path.relpath(a.config, ROOT), "kind": a.kind, "shapes_hw": SHAPES[a.kind], "augment": a.augment,
            "records": a.records, "per_gpu_batch": a.batch,
            "default_workers": input_pipeline.default_num_workers(8, 1), "host": host_speed(recs, jpegs)}
     print(json.dumps(res["host"]), flush=True)
     if a.skip != "feed":
-        res["feed"] = feed_only(mixed, dev, kw, a.feed_batches, a.workers)
+        res["feed"] = feed_only(mixed, dev, feeds, a.feed_batches, a.workers)
         print(json.dumps(res["feed"]), flush=True)
     if a.skip != "train":
         land = os.path.join(a.workdir, "landscape.record")
         write_records(land, a.records, SHAPES[a.kind][:1], K, 1)
         from mtl_ssl_amd.frcnn import FasterRCNNMetaArch as M
         HW = M.resized_shape(*SHAPES[a.kind][0], cfg.model.faster_rcnn.image_resizer)
-        res["train"] = dict(train_rates(a.config, land, dev, kw, a.steps, a.warmup, a.workers, HW), image_hw=HW,
+        train_feeds = {k: v for k, v in feeds.items() if k != "host_augment"}      # its feed rate says enough
+        res["train"] = dict(train_rates(a.config, land, dev, train_feeds, a.steps, a.warmup, a.workers, HW), image_hw=HW,
                             steps=a.steps, warmup=a.warmup)
         print(json.dumps(res["train"]), flush=True)
     if a.out:
