@@ -21,6 +21,12 @@ SCOPES = dict(first_stage_fe="FirstStageFeatureExtractor", second_stage_fe="Seco
               refine="MTLClassRefiner")
 
 
+EMA_SUFFIX = "/ExponentialMovingAverage"
+# evaluator.py:330-333 restores every variable from its moving average; a state without any is an error, not a fallback
+NO_MOVING_AVERAGES = ("eval_config.use_moving_averages is set but %s holds no ExponentialMovingAverage values "
+                      "(train with optimizer.use_moving_average: true)")
+
+
 def _names(ps):
     return [s.name for s in ps.specs]
 
@@ -181,3 +187,27 @@ def load_moving_averages(path, ps):
             ps.value(s.name).copy_(torch.as_tensor(ck[key]).to(ps.device))
             n += 1
     return n
+
+
+def inference_values(specs, path, use_moving_averages=False):
+    """{variable name: float32 array} for every VarSpec of an inference model, read from a state file of this build
+    or a TensorFlow V1 / V2 checkpoint (open_checkpoint). Unlike load(), nothing is skipped: a variable the source
+    lacks, or holds at another shape, raises KeyError / ValueError naming it. With `use_moving_averages` each variable
+    takes its `<name>/ExponentialMovingAverage` shadow where the source has one (exporter.py:361-364,
+    variables_to_restore); a source without any shadow raises NO_MOVING_AVERAGES. Returns (values, shadows used)."""
+    ck = open_checkpoint(path)
+    missing = [s.name for s in specs if s.name not in ck]
+    if missing:
+        raise KeyError("%s lacks %d variable(s) of the inference model, first %r" % (path, len(missing), missing[0]))
+    values, n_ema = {}, 0
+    for s in specs:
+        key = s.name
+        if use_moving_averages and s.name + EMA_SUFFIX in ck:
+            key, n_ema = s.name + EMA_SUFFIX, n_ema + 1
+        if _ckpt_shape(ck, key) != s.shape:
+            raise ValueError("%s: %s has shape %s, the inference model's %s is %s"
+                             % (path, key, _ckpt_shape(ck, key), s.name, s.shape))
+        values[s.name] = np.ascontiguousarray(ck[key], np.float32)
+    if use_moving_averages and n_ema == 0:
+        raise ValueError(NO_MOVING_AVERAGES % path)
+    return values, n_ema

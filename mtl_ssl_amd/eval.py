@@ -55,8 +55,7 @@ def main(argv=None):
         # `<name>/ExponentialMovingAverage` shadow when the training run kept one
         n_ema = checkpoint.load_moving_averages(state, model.ps)
         if n_ema == 0:
-            raise ValueError("eval_config.use_moving_averages is set but %s holds no ExponentialMovingAverage values "
-                             "(train with optimizer.use_moving_average: true)" % state)
+            raise ValueError(checkpoint.NO_MOVING_AVERAGES % state)
     model.prepare()
     coco = "coco" in str(ec.get("metrics_set", "pascal_voc_metrics"))
     limit = int(ec.get("num_examples", 5000))

@@ -62,11 +62,8 @@ FASTER_RCNN_FEATURE_EXTRACTOR_CLASS_MAP = {
 }
 
 
-def build(model_config, is_training, device="cuda", seed=0, values=None):
-    """Builds a DetectionModel from a `model { ... }` config message (Msg).
-
-    Raises ValueError on an unknown meta architecture / feature extractor, like the reference
-    (model_builder.py:88-95,176-180)."""
+def _construct(model_config, is_training, seed):
+    """The model and its ParamStore with every variable registered, nothing allocated (host only)."""
     which = model_config.which_oneof(["faster_rcnn", "ssd"])
     if which == "ssd":
         raise ValueError("ssd meta-architecture is out of scope of this build (SURVEY.md §2.1 #5)")
@@ -82,7 +79,21 @@ def build(model_config, is_training, device="cuda", seed=0, values=None):
     bp = fr.second_stage_box_predictor
     # builders/model_builder.py:352-380: rfcn_box_predictor selects the R-FCN meta-architecture
     arch = rfcn.RFCNMetaArch if bp.has("rfcn_box_predictor") else frcnn.FasterRCNNMetaArch
-    model = arch(ps, is_training, fr, model_config.mtl, fe, seed=seed)
+    return arch(ps, is_training, fr, model_config.mtl, fe, seed=seed), ps
+
+
+def variable_specs(model_config, is_training=False):
+    """The VarSpecs (reference names, shapes) of the model `build` would make, in registration order, without a
+    device: the constructors only register variables; buffers are allocated by ParamStore.finalize."""
+    return list(_construct(model_config, is_training, 0)[1].specs)
+
+
+def build(model_config, is_training, device="cuda", seed=0, values=None):
+    """Builds a DetectionModel from a `model { ... }` config message (Msg).
+
+    Raises ValueError on an unknown meta architecture / feature extractor, like the reference
+    (model_builder.py:88-95,176-180)."""
+    model, ps = _construct(model_config, is_training, seed)
     ps.finalize(device, seed=seed, values=values)
     model.prepare()
     return model
