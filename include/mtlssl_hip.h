@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 10
+#define MTLSSL_ABI_VERSION 11
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -358,6 +358,33 @@ int64_t mtlssl_nms_workspace_bytes(int n);
 int mtlssl_nms(const float* boxes, const float* scores, int n, float iou_thresh, int max_out,
                int32_t* selected_out, int32_t* num_out, void* workspace,
                mtlssl_stream_t stream);
+
+/* Evaluation (mtl_ssl_amd/eval.py), no training counterpart.
+ * Per-class re-suppression of postprocessed detections inside the evaluator: eval_config.nms_type / nms_threshold /
+ * soft_nms_sigma (utils/per_image_evaluation.py:35-68, 258; utils/object_detection_evaluation.py:45-59, 294-357) with
+ * the semantics of utils/np_box_list_ops.py: nms_type 1 = non_max_suppression (:185-258), 2 / 3 =
+ * soft_non_max_suppression linear / Gaussian (:259-366), score filter > -10, iou_threshold == 1.0 = sort and cap only.
+ * One workgroup per segment: segment s is rows [segment_offsets[s], segment_offsets[s+1]) of boxes [N,4] (fp32, times
+ * scale_y / scale_x in double like the host evaluator) and scores [N] (fp32); segment_offsets int32[num_segments+1]
+ * in device memory; max_segment = the largest segment length (host int), at most MTLSSL_EVAL_NMS_MAX_SEGMENT (the
+ * segment is held in LDS). IoU, weights and the Gaussian exp (csrc/portable_math.h) are evaluated in double;
+ * every rescale rounds once to fp32. Outputs per segment, in its own rows: index_out = segment-local input indices in
+ * output order, scores_out = their (rescored) scores, count_out[s] = how many; rows past the count hold -1 / 0.
+ * Thresholds and scales are doubles (the evaluator's numpy arithmetic). */
+#define MTLSSL_EVAL_NMS_MAX_SEGMENT 1024
+#define MTLSSL_EVAL_NMS_STANDARD 1
+#define MTLSSL_EVAL_NMS_SOFT_LINEAR 2
+#define MTLSSL_EVAL_NMS_SOFT_GAUSSIAN 3
+int mtlssl_eval_nms(const float* boxes, const float* scores, const int32_t* segment_offsets, int num_segments,
+                    int max_segment, int nms_type, double iou_threshold, double sigma, double scale_y, double scale_x,
+                    int max_output, int32_t* index_out, float* scores_out, int32_t* count_out,
+                    mtlssl_stream_t stream);
+/* The edge-mask metric's per-pixel work for one image (utils/mtl_util.py:91-101): logits [Hf,Wf,2] resized to
+ * [h,w] as skimage.transform.resize(x, (h, w, 2)) does at order 1 in scikit-image 0.13 / 0.14 (pixel (r, c) samples
+ * ((r+0.5)*Hf/h - 0.5, (c+0.5)*Wf/w - 0.5), bilinear, outside the map reads 0, no anti-aliasing), each channel rounded
+ * to fp32, label = ch0 < ch1; count_out (one int32, device) = pixels whose label equals gt_mask [h,w]. */
+int mtlssl_edgemask_agreement(const float* logits, int Hf, int Wf, const float* gt_mask, int h, int w,
+                              int32_t* count_out, mtlssl_stream_t stream);
 
 /* TargetAssigner.assign with IouSimilarity + ArgMaxMatcher
  * (core/target_assigner.py:99-213, matchers/argmax_matcher.py:102-189,

@@ -23,6 +23,7 @@ SOURCES = {
     "conv.hip": [],
     "glue.hip": ["-ffp-contract=off"],
     "depthwise.hip": [], "pool_concat.hip": [], "winograd.hip": [],
+    "eval_metrics.hip": ["-ffp-contract=off"],   # evaluator NMS / edge-mask metric: numpy's double arithmetic
     "comm.hip": [],                     # RCCL wrappers (host code only; RCCL itself is bound with dlopen)
 }
 

@@ -1,13 +1,18 @@
 """Evaluation launcher with the flags of object_detection/eval.py:66-82: restores the newest state of
 --checkpoint_dir into an inference replica, runs predict -> (refine) -> postprocess over eval_input_reader's records
 (evaluator.py:102-230: one image per step, at its own resized shape) and reports the metrics of
-eval_config.metrics_set (PASCAL VOC mAP@0.5 by default, COCO mAP with 'coco_metrics').
+eval_config.metrics_set (PASCAL VOC mAP at eval_config.iou_threshold by default, COCO mAP with 'coco_metrics').
+With mtl.window / closeness / edgemask the model also gets the record's groundtruth windows and the JSON carries
+mtl/window_map, mtl/closeness_diff and mtl/edgemask_ap (mtl_metrics.py); eval_config.nms_type / nms_threshold /
+soft_nms_sigma re-suppress each class's detections on the device before the evaluator sees them
+(utils/per_image_evaluation.py:35-68, 258).
 
     python -m mtl_ssl_amd.eval --checkpoint_dir=/runs/a --eval_dir=/runs/a/eval --pipeline_config_path=..."""
 import argparse
 import json
 import os
 import sys
+import warnings
 
 import numpy as np
 
@@ -22,6 +27,50 @@ def _plain(v):
     if isinstance(v, dict):
         return {k: _plain(x) for k, x in v.items()}
     return v
+
+
+def eval_nms_options(ec):
+    """(nms_type, nms_threshold, soft_nms_sigma, iou_threshold) of eval_config, as the float32 values the proto holds.
+    An unknown nms_type is a ValueError (eval_util.get_string_list_for_nms)."""
+    from .ops import EVAL_NMS_TYPES
+    nms_type = str(ec.get("nms_type", "standard"))
+    if nms_type not in EVAL_NMS_TYPES:
+        raise ValueError("eval_config.nms_type %r: Cannot identify NMS type (standard, soft-linear or soft-gaussian)"
+                         % nms_type)
+    f32 = lambda v: float(np.float32(v))
+    return (nms_type, f32(ec.get("nms_threshold", 1.0)), f32(ec.get("soft_nms_sigma", 0.5)),
+            f32(ec.get("iou_threshold", 0.5)))
+
+
+def suppress_per_class(boxes, scores, classes, scale, num_classes, nms_type, nms_threshold, sigma, max_per_class,
+                       device):
+    """The evaluator's per-class NMS of one image (per_image_evaluation.py:233-258, CocoEvaluation :330-357) on the
+    device: boxes [n,4] fp32 normalised, scores [n] fp32, classes [n] 0-based; scale multiplies the boxes in double
+    (what the evaluator is handed). Invalid boxes are dropped first (_remove_invalid_boxes). -> (boxes [m,4] float64
+    scaled, scores [m] fp32, classes [m]) grouped by class."""
+    import torch
+    from . import ops
+    sc = np.broadcast_to(np.asarray(scale, np.float64), (4,))
+    bd = np.asarray(boxes, np.float64) * sc
+    valid = (bd[:, 0] < bd[:, 2]) & (bd[:, 1] < bd[:, 3])
+    classes = np.asarray(classes).astype(np.int64)
+    rows = [np.flatnonzero(valid & (classes == c)) for c in range(num_classes)]
+    lengths = [len(r) for r in rows]
+    order = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    if not len(order):
+        return np.zeros((0, 4)), np.zeros(0, np.float32), np.zeros(0, np.int64)
+    b = torch.from_numpy(np.ascontiguousarray(boxes[order], np.float32)).to(device)
+    s = torch.from_numpy(np.ascontiguousarray(scores[order], np.float32)).to(device)
+    idx, out_s, cnt = ops.eval_nms(b, s, lengths, nms_type, nms_threshold, sigma, max_per_class,
+                                   scale=(float(sc[0]), float(sc[1])))
+    idx, out_s, cnt = idx.cpu().numpy(), out_s.cpu().numpy(), cnt.cpu().numpy()
+    keep, kept_scores, off = [], [], 0
+    for L, k in zip(lengths, cnt):
+        keep.append(order[off + idx[off:off + k]])
+        kept_scores.append(out_s[off:off + k])
+        off += L
+    keep = np.concatenate(keep)
+    return bd[keep], np.concatenate(kept_scores), classes[keep]
 
 
 def main(argv=None):
@@ -39,7 +88,7 @@ def main(argv=None):
     import torch
     import __graft_entry__ as ge
     ge.build()
-    from . import checkpoint, config, evaluation, model_builder
+    from . import checkpoint, config, evaluation, model_builder, mtl_metrics, ops
     from .train import record_batches, record_paths
     cfg = config.parse_pipeline_config(open(f.pipeline_config_path).read())
     ec = cfg.get("eval_config", config.Msg("EvalConfig"))
@@ -60,20 +109,66 @@ def main(argv=None):
     coco = "coco" in str(ec.get("metrics_set", "pascal_voc_metrics"))
     limit = int(ec.get("num_examples", 5000))
     rz = cfg.model.faster_rcnn.image_resizer
-    ev = evaluation.CocoDetectionEvaluator(K) if coco else evaluation.PascalDetectionEvaluator(K, 0.5)
+    nms_type, nms_thr, sigma, iou_thr = eval_nms_options(ec)
+    # evaluator.py:318-322: iou_threshold is PASCAL's matching threshold; COCO keeps its .50:.05:.95
+    ev = evaluation.CocoDetectionEvaluator(K) if coco else evaluation.PascalDetectionEvaluator(K, iou_thr)
+    # object_detection_evaluation.py:45-59 / :294-305: per-class caps of the evaluator's NMS
+    eval_nms = None if (nms_type == "standard" and nms_thr == 1.0) else (256 if coco else 10000)
+    mtl = cfg.model.get("mtl")
+    use = {k: mtl is not None and bool(mtl.get(k, False)) for k in ("window", "closeness", "edgemask", "refine")}
+    mm = mtl_metrics.MtlMetrics()
+    missing = {}
+    em_counts = []
+    closeness_error = None
     n_img = 0
     stream = record_batches(f.input_pipeline, record_paths(reader), K, 1, (), None, dev, reader,
                             resized_shape=lambda h, w: model.resized_shape(h, w, rz))
     for b in stream:
         if n_img >= limit:
             break
+        # evaluator.py:123-148: predict -> predict_with_window (the record's groundtruth windows) -> predict_edgemask
+        # -> refine -> postprocess; the auxiliary outputs are copied on the device at once (later passes reuse buffers)
         pd = model.predict(model.preprocess(b["images"].to(dev)))
-        if cfg.model.get("mtl") is not None and cfg.model.mtl.get("refine", False):
+        win = clo = em = None
+        if use["window"]:
+            if b.get("window_boxes") is None:
+                missing["mtl/window_map"] = "window boxes / labels (image/window/...)"
+            elif len(b["window_boxes"][0]):
+                wb = torch.from_numpy(np.ascontiguousarray(b["window_boxes"][0], np.float32)).to(dev).view(1, -1, 4)
+                win = model.predict_with_window(pd, wb)["window_class_predictions"].clone()
+            else:
+                mm.add_window(np.zeros((0, K + 1), np.float32), np.zeros((0, K + 1), np.float32))
+        if use["closeness"] and closeness_error is None:
+            if b.get("groundtruth_closeness") is None:
+                missing["mtl/closeness_diff"] = "groundtruth closeness (image/object/closeness/text)"
+            else:
+                clo = pd["closeness_predictions"].clone()
+        if use["edgemask"]:
+            model.predict_edgemask(pd)
+            if b.get("groundtruth_edgemask") is None:
+                missing["mtl/edgemask_ap"] = "groundtruth edge mask (image/edgemask/masks)"
+            else:
+                gt_em = b["groundtruth_edgemask"][0]
+                gt0 = torch.from_numpy(np.ascontiguousarray(gt_em[0], np.float32)).to(dev)
+                em = ops.edgemask_agreement(pd["edgemask_predictions"][0].contiguous(), gt0)
+                em_counts.append((em, gt_em.shape[1], gt_em.shape[2]))
+        if use["refine"]:
             pd = model.predict_with_mtl_results(pd)
         d = {k: v.cpu().numpy() for k, v in model.postprocess(pd).items()}
         model.check_device_flags()             # e.g. the refiner's window de-duplication ran out of slots (NaN boxes)
         n = int(d["num_detections"][0])
         H, W = b["images"].shape[1:3]
+        if win is not None:
+            mm.add_window(win.cpu().numpy(), b["window_classes"][0])
+        if clo is not None and closeness_error is None:
+            # the reference's absolute fp32 boxes (box_list_ops.scale / to_absolute_coordinates), all padded slots
+            hw = np.asarray([H, W, H, W], np.float32)
+            try:
+                mm.add_closeness(clo.cpu().numpy(), b["groundtruth_closeness"][0],
+                                 np.asarray(b["groundtruth_boxes"][0], np.float32).reshape(-1, 4) * hw,
+                                 np.asarray(d["detection_boxes"][0], np.float32) * hw)
+            except ValueError as e:        # the reference stops with an IndexError; the other metrics stay valid
+                closeness_error = str(e)
         # evaluator.py:137-150 hands the COCO evaluator absolute boxes, the PASCAL one either (IoU is scale-free)
         scale = np.asarray([H, W, H, W], np.float64) if coco else 1.0
         gt_boxes = np.asarray(b["groundtruth_boxes"][0], np.float64).reshape(-1, 4) * scale
@@ -84,16 +179,33 @@ def main(argv=None):
             diff = b.get("groundtruth_difficult")
             ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls,
                                                   is_difficult=None if diff is None else np.asarray(diff[0], bool))
-        ev.add_single_detected_image_info(n_img, np.asarray(d["detection_boxes"][0][:n], np.float64) * scale,
-                                          d["detection_scores"][0][:n], d["detection_classes"][0][:n])
+        if eval_nms is None:
+            ev.add_single_detected_image_info(n_img, np.asarray(d["detection_boxes"][0][:n], np.float64) * scale,
+                                              d["detection_scores"][0][:n], d["detection_classes"][0][:n])
+        else:
+            ev.add_single_detected_image_info(n_img, *suppress_per_class(
+                d["detection_boxes"][0][:n], d["detection_scores"][0][:n], d["detection_classes"][0][:n], scale, K,
+                nms_type, nms_thr, sigma, eval_nms, dev))
         n_img += 1
     if hasattr(stream, "close"):
         stream.close()
+    if em_counts:
+        counts = torch.cat([c for c, _, _ in em_counts]).cpu().numpy()
+        for c, (_, h, w) in zip(counts, em_counts):
+            mm.add_edgemask(int(c), h, w)
     res = ev.evaluate()
     out = {"global_step": int(step), "num_images": n_img}
     for k, v in res.items():
         if k not in ("precisions", "recalls"):           # the per-class curves stay in the evaluator
             out[k] = _plain(v)
+    mres = mm.evaluate()
+    if closeness_error is not None:
+        mres.pop("mtl/closeness_diff", None)
+        warnings.warn("mtl/closeness_diff left out: " + closeness_error)
+    for key, field in sorted(missing.items()):
+        if key not in mres:
+            warnings.warn("%s left out: no evaluated record carries the %s it needs" % (key, field))
+    out.update(mres)
     print(json.dumps(out))
     if f.eval_dir:
         os.makedirs(f.eval_dir, exist_ok=True)

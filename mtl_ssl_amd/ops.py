@@ -992,6 +992,43 @@ def batch_multiclass_nms(boxes, scores, score_thresh, iou_thresh, max_per_class,
     return ob, os_, oc, on
 
 
+# eval_config.nms_type -> mtlssl_eval_nms (eval_util.get_string_list_for_nms: anything else is a ValueError)
+EVAL_NMS_TYPES = {"standard": 1, "soft-linear": 2, "soft-gaussian": 3}
+EVAL_NMS_MAX_SEGMENT = 1024          # MTLSSL_EVAL_NMS_MAX_SEGMENT: one segment lives in the workgroup's LDS
+
+
+def eval_nms(boxes, scores, segment_lengths, nms_type, iou_threshold, sigma, max_output, scale=(1.0, 1.0)):
+    """The evaluator's per-class NMS (np_box_list_ops.non_max_suppression / soft_non_max_suppression) over
+    consecutive segments of boxes [N,4] / scores [N] (fp32, device); segment_lengths: host ints summing to N.
+    scale = (y, x) multiplies the boxes in double first. -> (index [N] int32, scores [N] fp32, count [S] int32) on the
+    device: segment s's first count[s] rows of its own range hold its kept segment-local indices and scores."""
+    if nms_type not in EVAL_NMS_TYPES:
+        raise ValueError("Cannot identify NMS type: %r (standard, soft-linear or soft-gaussian)" % (nms_type,))
+    lengths = np.asarray(segment_lengths, np.int64).reshape(-1)
+    n, S = int(lengths.sum()), len(lengths)
+    dev = boxes.device
+    assert boxes.shape == (n, 4) and scores.shape == (n,), (boxes.shape, scores.shape, n)
+    offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)).to(dev)
+    idx = torch.empty((max(n, 1),), dtype=i32, device=dev)
+    sco = torch.empty((max(n, 1),), dtype=f32, device=dev)
+    cnt = torch.empty((max(S, 1),), dtype=i32, device=dev)
+    lib().eval_nms(ptr(_chk(boxes)), ptr(_chk(scores)), ptr(offsets), S, int(lengths.max()) if S else 0,
+                   EVAL_NMS_TYPES[nms_type], float(iou_threshold), float(sigma), float(scale[0]), float(scale[1]),
+                   int(max_output), ptr(idx), ptr(sco), ptr(cnt), _stream())
+    return idx[:n], sco[:n], cnt[:S]
+
+
+def edgemask_agreement(logits, gt_mask):
+    """utils/mtl_util.py:91-101 per image: logits [Hf,Wf,2] and the groundtruth edge mask's channel 0 [h,w] (fp32,
+    device) -> int32 [1] on the device, the pixels whose resized label (ch0 < ch1) equals the mask."""
+    Hf, Wf, two = logits.shape
+    h, w = gt_mask.shape
+    assert two == 2, logits.shape
+    out = torch.empty((1,), dtype=i32, device=logits.device)
+    lib().edgemask_agreement(ptr(_chk(logits)), Hf, Wf, ptr(_chk(gt_mask)), h, w, ptr(out), _stream())
+    return out
+
+
 def hard_example_mining(loc_rl, cls_rl, boxes, num_proposals, d_box, d_cls, num_hard_examples, iou_threshold, loss_type):
     """core/losses.py:418-631 on the second stage (see mtlssl_hard_mining_*): loc_rl / cls_rl [B,n2] per-proposal
     losses, boxes [B,n2,4] the proposal boxes. Zeroes the gradient rows of proposals that were not mined (in place)
