@@ -520,7 +520,9 @@ class Oracle:
                                    mtl.get("refine_dropout_rate", 1.0), 0, seed, step, True)   # :835-839
             refined = self.fc(hidden, "MTLClassRefiner/fc%d" % (nh + 1))
             if mtl["refine_residue"]:
-                refined = refined + cls
+                # faster_rcnn_meta_arch.py:767-769, 842-843: the residual is the class logits, tf.stop_gradient'ed
+                # when mtl.stop_gradient_for_prediction_org is set
+                refined = refined + (cls.detach() if mtl.get("stop_gradient_for_prediction_org") else cls)
             losses.update(L.loss_refined_classifier(refined, num, dt, mtl["refined_classification_loss_weight"]))
         total = sum(losses.values())
         total.backward()

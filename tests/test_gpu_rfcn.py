@@ -299,3 +299,53 @@ def test_rfcn_shared_classifier_feature_maps_matches_oracle(stop):
                             {k: v for k, v in grads.items() if k in rgrads and np.any(rgrads[k])}, rgrads, got, ref)
     tr.apply_gradients()
     assert np.isfinite(model.ps.weights.sum().item())
+
+
+def test_rfcn_stop_gradient_for_prediction_org_matches_oracle():
+    """mtl.stop_gradient_for_prediction_org (faster_rcnn_meta_arch.py:767-769, 842-843) under RFCNMetaArch: the refiner's
+    residual adds the class logits without their gradient. Checked against the oracle with the switch on, and against
+    the product with it off so that ignoring the switch cannot pass."""
+    import bench
+    from mtl_ssl_amd import config, model_builder, synthetic, trainer
+    from oracle.model import Oracle
+    from tests import parity_report
+    text = open(os.path.join(ROOT, "configs", "smoke_rfcn_resnet50_mtl.config")).read()
+    assert "refine_residue: true" in text
+    on = text.replace("refine_residue: true", "refine_residue: true  stop_gradient_for_prediction_org: true")
+    batch = synthetic.make_batch(2, 160, 224, 5, seed=11, device="cuda", max_gt=4, num_windows=6)
+    hb = dict(batch)
+    hb["images"] = batch["images"].cpu().numpy()
+    grads = {}
+    for switch, txt in (("on", on), ("off", text)):
+        cfg = config.parse_pipeline_config(txt)
+        assert bool(cfg.model.mtl.stop_gradient_for_prediction_org) == (switch == "on")
+        model = model_builder.build(cfg.model, True, "cuda", seed=3)
+        tr = trainer.Trainer(model, cfg.train_config, 1)
+        values = model.ps.state_dict()
+        losses = tr.forward_backward(batch)
+        torch.cuda.synchronize()
+        grads[switch] = model.ps.grads_dict()
+        if switch == "off":
+            break
+        got = {k: float(v.item()) for k, v in losses.items()}
+        hp = bench.hyper_params_for_oracle(cfg)
+        hp["mtl"]["stop_gradient_for_prediction_org"] = True
+        ref, rgrads, _ = parity_report.oracle_on_device_rpn(Oracle, hp, values, hb, model.seed, 0, tr._pd)
+        assert set(got) == set(ref)
+        for k in ref:
+            assert abs(got[k] - ref[k]) <= 1e-3 * max(abs(ref[k]), 1e-3), (k, got[k], ref[k])
+        l2 = []
+        for n, gv in grads["on"].items():
+            r = rgrads.get(n)
+            if r is None or not np.any(r):
+                assert not np.any(gv), n
+                continue
+            e = float(np.linalg.norm((gv - r).ravel()) / max(np.linalg.norm(r.ravel()), 1e-12))
+            assert e < 5e-3, (n, e)
+            l2.append(e)
+        assert len(l2) > 50 and np.median(l2) < 1e-3
+    names = [n for n in grads["on"] if n.startswith("SecondStageBoxPredictor/class_predictions/")]
+    assert names
+    for n in names:
+        a, b = grads["on"][n].ravel(), grads["off"][n].ravel()
+        assert np.linalg.norm(a - b) > 0.1 * np.linalg.norm(b), (n, np.linalg.norm(a - b) / np.linalg.norm(b))

@@ -8,6 +8,7 @@
     (stop_gradient_for_aux_tasks on and off)
   * first_stage_only (RPN + edge-mask head only)                faster_rcnn_meta_arch.py:603, 1029-1039, 1549-1567
   * hard_example_miner on the second stage                      core/losses.py:418-631, faster_rcnn_meta_arch.py:1758-1762
+  * mtl.stop_gradient_for_prediction_org                        faster_rcnn_meta_arch.py:767-769, 842-843
 Dropout draws are the samplers' counter hash in both implementations (mtlssl_dropout / oracle.assign.dropout_mask)."""
 
 import numpy as np
@@ -23,7 +24,7 @@ model {
     refined_classification_loss_weight: 1.0  window_class_loss_weight: 1.0
     closeness_loss_weight: 0.3  edgemask_loss_weight: 1.0
     refine_residue: true  refine_num_fc_layers: %(refine_layers)d  refine_dropout_rate: %(refine_keep)s
-    stop_gradient_for_aux_tasks: %(stop)s  shared_feature: '%(shared)s'
+    stop_gradient_for_aux_tasks: %(stop)s  shared_feature: '%(shared)s'  %(mtl_extra)s
     refiner_fc_hyperparams { op: FC regularizer { l2_regularizer { weight: 0.0 } }
       initializer { truncated_normal_initializer { stddev: 0.05 } } }
     window_box_predictor { mask_rcnn_box_predictor { spatial_average: %(win_avg)s
@@ -61,7 +62,8 @@ train_config { batch_size: 2
 """
 
 BASE = dict(refine="true", window="true", closeness="true", refine_layers=0, refine_keep="1.0", stop="true",
-            shared="proposal_feature_maps", win_avg="true", first_only="false", main_extra="", miner="", fe_extra="")
+            shared="proposal_feature_maps", win_avg="true", first_only="false", main_extra="", miner="", fe_extra="",
+            mtl_extra="")
 CASES = {
     "refiner_fc_stack_with_dropout": dict(refine_layers=2, refine_keep="0.7"),
     "predictor_extra_layers_with_dropout": dict(
@@ -79,6 +81,9 @@ CASES = {
     # slim/nets/resnet_utils.py:203-237): gamma / beta of EVERY BatchNorm train — also those of the frozen root conv
     # and of frozen block1 — on the moving statistics
     "resnet_batch_norm_trainable": dict(fe_extra="batch_norm_trainable: true"),
+    # the refiner's residual adds the class logits without their gradient: the refined loss no longer reaches the
+    # second-stage class predictor
+    "stop_gradient_for_prediction_org": dict(mtl_extra="stop_gradient_for_prediction_org: true"),
     "hard_example_miner_cls_all_survivors": dict(
         refine="false", miner="hard_example_miner { num_hard_examples: 0 iou_threshold: 0.3 loss_type: CLASSIFICATION }"),
 }
@@ -138,7 +143,9 @@ def test_switch_matches_the_oracle(case):
     forced = None if case == "first_stage_only" else dict(
         rpn_box_encodings=pd["rpn_box_encodings"].cpu().numpy(),
         rpn_objectness=pd["rpn_objectness_predictions_with_background"].cpu().numpy())
-    ref, rgrads, aux = Oracle(bench.hyper_params_for_oracle(cfg), values).step(hb, seed=model.seed, step=0, forced=forced)
+    hp = bench.hyper_params_for_oracle(cfg)
+    hp["mtl"]["stop_gradient_for_prediction_org"] = bool(cfg.model.mtl.stop_gradient_for_prediction_org)
+    ref, rgrads, aux = Oracle(hp, values).step(hb, seed=model.seed, step=0, forced=forced)
     np.testing.assert_array_equal(pd["_rpn_targets"]["match"].cpu().numpy(), aux["rpn_match"])
     np.testing.assert_array_equal(pd["_rpn_targets"]["sampled"].cpu().numpy(), aux["rpn_sampled"])
     if case != "first_stage_only":
@@ -186,6 +193,10 @@ def test_switch_matches_the_oracle(case):
         ref2, _, _ = parity_report.oracle_on_device_rpn(Oracle, bench.hyper_params_for_oracle(cfg), values2, hb, model.seed, 1, tr._pd)
         for k in ref2:
             assert abs(got2[k] - ref2[k]) <= 1e-3 * max(abs(ref2[k]), 1e-3), (k, got2[k], ref2[k])
+    if case == "stop_gradient_for_prediction_org":
+        off = CONFIG % dict(BASE, **CASES[case])
+        _assert_switch_moves_class_predictor(off.replace("stop_gradient_for_prediction_org: true", ""), batch, grads,
+                                             "SecondStageBoxPredictor/ClassPredictor/")
     parity_report.gradients("switch %s (ResNet-50 160x224)" % case, {k: v for k, v in grads.items() if k in rgrads and np.any(rgrads[k])},
                             rgrads, got, ref)
     # and one optimizer step runs (every variable of the configuration has a slot in the fused update)
@@ -193,6 +204,24 @@ def test_switch_matches_the_oracle(case):
     tr.step(batch)
     torch.cuda.synchronize()
     assert all(np.isfinite(float(v.item())) for v in losses.values())
+
+
+def _assert_switch_moves_class_predictor(config_off, batch, grads_on, prefix):
+    """The same step with stop_gradient_for_prediction_org off: the class predictor's gradients must differ from those
+    with it on by far more than the 5e-3 parity bound above, or a product that ignored the switch would pass."""
+    from mtl_ssl_amd import config, model_builder, trainer
+    cfg = config.parse_pipeline_config(config_off)
+    assert not cfg.model.mtl.stop_gradient_for_prediction_org
+    model = model_builder.build(cfg.model, True, "cuda", seed=3)
+    tr = trainer.Trainer(model, cfg.train_config, 1)
+    tr.forward_backward(batch)
+    torch.cuda.synchronize()
+    grads_off = model.ps.grads_dict()
+    names = [n for n in grads_on if n.startswith(prefix)]
+    assert len(names) == 2, names
+    for n in names:
+        a, b = grads_on[n].ravel(), grads_off[n].ravel()
+        assert np.linalg.norm(a - b) > 0.1 * np.linalg.norm(b), (n, np.linalg.norm(a - b) / np.linalg.norm(b))
 
 
 def test_dropout_kernel_matches_the_oracle_mask():
