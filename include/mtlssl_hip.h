@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 11
+#define MTLSSL_ABI_VERSION 12
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -385,6 +385,45 @@ int mtlssl_eval_nms(const float* boxes, const float* scores, const int32_t* segm
  * to fp32, label = ch0 < ch1; count_out (one int32, device) = pixels whose label equals gt_mask [h,w]. */
 int mtlssl_edgemask_agreement(const float* logits, int Hf, int Wf, const float* gt_mask, int h, int w,
                               int32_t* count_out, mtlssl_stream_t stream);
+
+/* Auxiliary-task labels from the groundtruth alone (Trainer(aux_labels="generate")): what the reference computes once,
+ * offline, when it writes a record (create_records/create_pascal_tf_record.py:120-421), made per step on the device
+ * from the padded tensors the model holds after provide_groundtruth: boxes_norm [B,max_gt,4] (normalised), classes_bg
+ * [B,max_gt,K+1] (one-hot, column 0 = background and zero), num int32[B] (rows >= num[b] are never read). height /
+ * width: the size in pixels of the (resized) image the boxes are relative to; absolute box = (double)normalised * size.
+ * All arithmetic in double, each output rounded once to fp32, every reduction in a fixed order (no atomics): the same
+ * bits run to run. Host definitions: mtl_ssl_amd/labels.py draw_windows / window_labels_exact /
+ * closeness_labels_exact / edgemask_exact. The label kernels keep an image's boxes in LDS: max_gt is at most
+ * MTLSSL_AUX_MAX_GT, beyond it they return MTLSSL_EINVAL. */
+#define MTLSSL_AUX_MAX_GT 256
+#define MTLSSL_AUX_WINDOW_ATTEMPTS 100
+/* create_multi_object, random_multi_object branch (create_pascal_tf_record.py:225-261), with Python's sequential
+ * random.random() replaced by the counter hash: uniform j of window slot w, attempt a of image b is
+ * (mix32(seed', 0x57494E44, (w * 100 + a) * 4 + j) >> 8) * 2^-24, seed' = mix32(mix32(seed, 0x57494E44, step),
+ * 0x57494E44, image0 + b). A window that has no intersection of positive area with any box is redrawn, at most
+ * MTLSSL_AUX_WINDOW_ATTEMPTS times per slot (the last draw is kept); an image without boxes repeats its first window.
+ * window_boxes [B,num_windows,4] normalised; bit-exact against labels.draw_windows. */
+int mtlssl_aux_draw_windows(const float* boxes_norm, const int32_t* num, int batch, int max_gt, int num_windows,
+                            double height, double width, double min_obj_size, uint32_t seed, uint32_t step,
+                            uint32_t image0, float* window_boxes, mtlssl_stream_t stream);
+/* get_multi_label with label_option 1 / normalize_option 1 (create_pascal_tf_record.py:199-226) over
+ * get_rect_area_total (:140-162): per (image, window) the exact area of the union of each present class's boxes
+ * clipped to the window (slab sweep over the sorted x edges, intervals merged in y), of all boxes for the background
+ * slot, then sqrt and division by the sum. window_boxes [B,num_windows,4] normalised (an input, so that recorded
+ * windows can be labelled too); labels_out [B,num_windows,K+1]. One workgroup per (image, window). */
+int mtlssl_aux_window_labels(const float* boxes_norm, const float* classes_bg, const int32_t* num,
+                             const float* window_boxes, int batch, int max_gt, int num_classes, int num_windows,
+                             double height, double width, float* labels_out, mtlssl_stream_t stream);
+/* get_closeness (create_pascal_tf_record.py:325-358): per object and OTHER class 1 - centre distance / image diagonal
+ * of the nearest instance, background slot 1 when nothing of another class is around (a single object included),
+ * normalised to sum 1. closeness_out [B,max_gt,K+1], rows >= num[b] zero. */
+int mtlssl_aux_closeness(const float* boxes_norm, const float* classes_bg, const int32_t* num, int batch, int max_gt,
+                         int num_classes, double height, double width, float* closeness_out, mtlssl_stream_t stream);
+/* create_edgemask (create_pascal_tf_record.py:375-421): cell ranges with its int() truncations, the +0.99 and the
+ * zero-width fix-ups; plane 0 = covered by a box, plane 1 = max(1/mask^2, max over covering boxes of 1/bw/bh) divided
+ * by its mean (accumulated in double). edgemask_out [B,2,mask_size,mask_size]; the reference's mask_size is 64. */
+int mtlssl_aux_edgemask(const float* boxes_norm, const int32_t* num, int batch, int max_gt, double height, double width,
+                        int mask_size, float* edgemask_out, mtlssl_stream_t stream);
 
 /* TargetAssigner.assign with IouSimilarity + ArgMaxMatcher
  * (core/target_assigner.py:99-213, matchers/argmax_matcher.py:102-189,

@@ -24,6 +24,7 @@ SOURCES = {
     "glue.hip": ["-ffp-contract=off"],
     "depthwise.hip": [], "pool_concat.hip": [], "winograd.hip": [],
     "eval_metrics.hip": ["-ffp-contract=off"],   # evaluator NMS / edge-mask metric: numpy's double arithmetic
+    "aux_labels.hip": ["-ffp-contract=off"],     # labels from boxes: the host definitions' double arithmetic
     "comm.hip": [],                     # RCCL wrappers (host code only; RCCL itself is bound with dlopen)
 }
 

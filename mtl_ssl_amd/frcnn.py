@@ -415,6 +415,23 @@ class FasterRCNNMetaArch:
         self._edgemask = torch.stack([torch.as_tensor(e, dtype=f32) for e in groundtruth_edgemask_list]) \
             .to(dev).contiguous()
 
+    def provide_generated_labels(self, seed, step, image_hw, image0=0, num_windows=64, min_obj_size=32.0,
+                                 mask_size=64):
+        """The auxiliary labels of the heads that `mtl` switches on, made on the device from the boxes and classes
+        provide_groundtruth installed (csrc/aux_labels.hip; definitions: labels.draw_windows / *_exact), in the
+        layouts provide_window / provide_edgemask / provide_groundtruth(..., closeness) leave behind. Windows are
+        drawn afresh for (seed, step, image0 + b); image_hw = the resized batch's (height, width) in pixels. Enqueued
+        on the current stream, nothing returns to the host."""
+        gt, mtl = self._gt, self._mtl
+        boxes, cls_bg, num = gt["boxes_norm"].contiguous(), gt["classes_bg"], gt["num"]
+        if mtl.window:
+            wb = ops.aux_draw_windows(boxes, num, num_windows, image_hw, seed, step, image0, min_obj_size)
+            self._window = dict(boxes=wb, classes=ops.aux_window_labels(boxes, cls_bg, num, wb, image_hw))
+        if mtl.closeness:
+            gt["closeness"] = ops.aux_closeness(boxes, cls_bg, num, image_hw)
+        if mtl.edgemask:
+            self._edgemask = ops.aux_edgemask(boxes, num, image_hw, mask_size)
+
     def _anchors_for(self, Hf, Wf, H, W, device):
         key = (Hf, Wf, H, W)
         if key not in self._anchors:

@@ -178,3 +178,166 @@ def edgemask(boxes, width, height, mask_size=64):
         box_weight[y0:y1 + 1, x0:x1 + 1] = np.maximum(w, box_weight[y0:y1 + 1, x0:x1 + 1])
     box_weight /= np.mean(box_weight)
     return np.array([box_mask, box_weight])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Run-time definitions: what the device generates per step (csrc/aux_labels.hip) when the trainer runs with
+# aux_labels="generate". Same arithmetic as window_label / closeness_labels / edgemask above, in float64, WITHOUT the
+# three-decimal rounding: _round3 restates the record's text encoding, and a label that never passes through text has
+# no reason to be quantised. Inputs are what the trainer holds: boxes normalised [ymin, xmin, ymax, xmax] float32,
+# classes as provide_groundtruth receives them (one-hot [G,K], column k = class id k + 1; a 1-D array of 1-based ids
+# is accepted too), and the image size in pixels. The size meant everywhere below is the RESIZED batch's (OH, OW),
+# the frame the step trains in: min_obj_size = 32 px and the closeness diagonal are measured in it. Absolute box =
+# float64(normalised) * size, in that order, so the host and the device start from the same doubles.
+
+WINDOW_STREAM = 0x57494E44                         # mix32 stream of draw_windows ("WIND")
+WINDOW_ATTEMPTS = 100                              # redraws per window slot before the last draw is kept
+
+
+def _class_ids(classes):
+    c = np.asarray(classes)
+    if c.ndim == 2:
+        return (np.argmax(c, 1) + 1).astype(np.int64) if c.shape[0] else np.zeros((0,), np.int64)
+    return c.astype(np.int64).reshape(-1)
+
+
+def _absolute(boxes, height, width):
+    b = np.asarray(boxes, np.float32).reshape(-1, 4).astype(np.float64)
+    return b * np.array([height, width, height, width], np.float64)
+
+
+def window_labels_exact(boxes, classes, windows, num_classes, height, width):
+    """get_multi_label :199-226 (label_option=1, normalize_option=1) for every window, unrounded: [W,K+1] float64.
+    boxes [G,4] / windows [W,4] normalised float32; height, width: the resized image's size in pixels."""
+    b = _absolute(boxes, height, width)
+    ids = _class_ids(classes)
+    wins = _absolute(windows, height, width)
+    out = np.zeros((len(wins), num_classes + 1), np.float64)
+    for n, win in enumerate(wins):
+        lab = out[n]
+        lab[0] = math.sqrt(max(0.0, 1.0 - _window_area_fraction(b, win)))
+        for c in np.unique(ids):
+            lab[c] = math.sqrt(_window_area_fraction(b[ids == c], win))
+        lab /= lab.sum()
+    return out
+
+
+def closeness_labels_exact(boxes, classes, num_classes, height, width):
+    """get_closeness :325-358, unrounded: [G,K+1] float64 (a single object: [1, 0, ...])."""
+    b = _absolute(boxes, height, width)
+    ids = _class_ids(classes)
+    G = len(b)
+    out = np.zeros((G, num_classes + 1), np.float64)
+    if G == 1:
+        out[0, 0] = 1
+        return out
+    diag = math.sqrt(float(width) * float(width) + float(height) * float(height))
+    cy, cx = (b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2
+    for i in range(G):
+        for j in range(G):
+            if i == j or ids[i] == ids[j]:
+                continue
+            dx, dy = cx[i] - cx[j], cy[i] - cy[j]
+            out[i, ids[j]] = max(out[i, ids[j]], 1.0 - math.sqrt(dx * dx + dy * dy) / diag)
+        if out[i, 1:].sum() == 0:
+            out[i, 0] = 1
+        out[i] /= out[i].sum()
+    return out
+
+
+def edgemask_exact(boxes, height, width, mask_size=64):
+    """create_edgemask :375-421 from normalised float32 boxes -> [2, mask, mask] float32. Identical to `edgemask` on
+    the same absolute doubles except for the final division: the mean of the weight plane is accumulated in float64
+    (then rounded to float32), where numpy's float32 pairwise mean carries ~log2(mask^2) * 2^-24 of relative error."""
+    em = edgemask_unnormalised(_absolute(boxes, height, width), width, height, mask_size)
+    mean = np.float32(em[1].astype(np.float64).sum() / float(mask_size * mask_size))
+    em[1] /= mean
+    return em
+
+
+def edgemask_unnormalised(abs_boxes, width, height, mask_size=64):
+    """The loop of `edgemask` (cell ranges with their int() truncations, +0.99 and zero-width fix-ups; max of the
+    per-box weights) before the division by the mean."""
+    box_mask = np.zeros([mask_size, mask_size], np.float32)
+    box_weight = np.ones([mask_size, mask_size], np.float32) / mask_size / mask_size
+    for ymin, xmin, ymax, xmax in np.asarray(abs_boxes, np.float64).reshape(-1, 4):
+        y0 = int(ymin / height * mask_size)
+        x0 = int(xmin / width * mask_size)
+        y1 = min(mask_size - 1, int(ymax / height * mask_size + 0.99))
+        x1 = min(mask_size - 1, int(xmax / width * mask_size + 0.99))
+        bw, bh = x1 - x0 + 1, y1 - y0 + 1
+        if bw == 0:
+            if x0 + x1 > mask_size:
+                x0 -= 1
+            else:
+                x1 += 1
+            bw = 1
+        if bh == 0:
+            if y0 + y1 > mask_size:
+                y0 -= 1
+            else:
+                y1 += 1
+            bh = 1
+        box_mask[y0:y1 + 1, x0:x1 + 1] = 1.0
+        w = np.ones([bh, bw], np.float32) / bw / bh
+        box_weight[y0:y1 + 1, x0:x1 + 1] = np.maximum(w, box_weight[y0:y1 + 1, x0:x1 + 1])
+    return np.array([box_mask, box_weight])
+
+
+def _mix32(seed, stream, i):
+    """preprocessor.mix32 (csrc/glue.hip glue_mix32) on Python ints."""
+    m = 0xFFFFFFFF
+    x = (int(i) + 0x9E3779B9 * int(seed) + 0x85EBCA6B * int(stream)) & m
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & m
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & m
+    x ^= x >> 16
+    return x
+
+
+def window_seed(seed, step, image):
+    """seed' of draw_windows: the run's seed mixed with the step and the (global) image index."""
+    return _mix32(_mix32(seed, WINDOW_STREAM, int(step) & 0xFFFFFFFF), WINDOW_STREAM, int(image) & 0xFFFFFFFF)
+
+
+def draw_windows(boxes, height, width, num_windows, seed, step, image, min_obj_size=32.0, return_attempts=False):
+    """The window distribution of `random_windows` (create_multi_object's random branch :225-261: size uniform in
+    [min_obj_size, side], centre uniform in the image, clipped, the two min_obj_size fix-ups, a window that meets no
+    object redrawn while the image has objects), driven by the counter hash instead of Python's sequential
+    random.random(): uniform j (0 height, 1 width, 2 centre y, 3 centre x) of window slot w, attempt a is
+    (mix32(seed', WINDOW_STREAM, (w * WINDOW_ATTEMPTS + a) * 4 + j) >> 8) * 2^-24 with seed' = window_seed(seed,
+    step, image). Slots are independent; a slot keeps its last draw after WINDOW_ATTEMPTS attempts. "Meets no object"
+    is "no box has an intersection of positive area with the window" (= the reference's bg == 1.0). An image without
+    boxes gets its first window repeated. boxes normalised float32 [G,4]; height, width: the resized image's size in
+    pixels, both at least min_obj_size (the fix-ups push a window out of a smaller image, as the reference's do). All arithmetic in float64, the result rounded once to float32: mtlssl_aux_draw_windows gives the same bits.
+    -> [num_windows,4] float32 normalised (and the attempts each slot used, if asked)."""
+    b = _absolute(boxes, height, width)
+    H, W, m = float(height), float(width), float(min_obj_size)
+    s = window_seed(seed, step, image)
+    out = np.zeros((num_windows, 4), np.float32)
+    attempts = np.zeros((num_windows,), np.int64)
+    for w in range(num_windows):
+        slot = w if len(b) else 0
+        for a in range(WINDOW_ATTEMPTS):
+            u = [float(_mix32(s, WINDOW_STREAM, (slot * WINDOW_ATTEMPTS + a) * 4 + j) >> 8) * 2.0 ** -24 for j in range(4)]
+            bh = u[0] * (H - m) + m
+            bw = u[1] * (W - m) + m
+            cy, cx = u[2] * H, u[3] * W
+            ymin, xmin = max(0.0, cy - bh / 2), max(0.0, cx - bw / 2)
+            ymax, xmax = min(H, cy + bh / 2), min(W, cx + bw / 2)
+            if xmax - xmin < m:
+                if xmin == 0.0:
+                    xmax = m
+                elif xmax == W:
+                    xmin = W - m
+            if ymax - ymin < m:
+                if ymin == 0.0:
+                    ymax = m
+                elif ymax == H:
+                    ymin = H - m
+            attempts[w] = a + 1
+            if not len(b) or any(min(ymax, y1) > max(ymin, y0) and min(xmax, x1) > max(xmin, x0) for y0, x0, y1, x1 in b):
+                break
+        out[w] = [ymin / H, xmin / W, ymax / H, xmax / W]
+    return (out, attempts) if return_attempts else out

@@ -1029,6 +1029,61 @@ def edgemask_agreement(logits, gt_mask):
     return out
 
 
+AUX_MAX_GT = 256                     # MTLSSL_AUX_MAX_GT: the label kernels hold one image's boxes in LDS
+AUX_WINDOW_ATTEMPTS = 100            # MTLSSL_AUX_WINDOW_ATTEMPTS (labels.WINDOW_ATTEMPTS)
+
+
+def _aux_gt(boxes_norm, num, classes_bg=None):
+    B, G, four = boxes_norm.shape
+    assert four == 4 and num.shape == (B,), (boxes_norm.shape, num.shape)
+    if classes_bg is not None:
+        assert classes_bg.dim() == 3 and classes_bg.shape[:2] == (B, G), (classes_bg.shape, boxes_norm.shape)
+    return B, G
+
+
+def aux_draw_windows(boxes_norm, num, num_windows, image_hw, seed, step, image0=0, min_obj_size=32.0):
+    """labels.draw_windows for a batch on the device: boxes_norm [B,G,4], num int32 [B], image_hw = (height, width) of
+    the resized image in pixels; image b draws with image index image0 + b. -> window boxes [B,num_windows,4]."""
+    B, G = _aux_gt(boxes_norm, num)
+    out = torch.empty((B, int(num_windows), 4), dtype=f32, device=boxes_norm.device)
+    lib().aux_draw_windows(ptr(_chk(boxes_norm)), ptr(_chk(num, i32)), B, G, int(num_windows), float(image_hw[0]),
+                           float(image_hw[1]), float(min_obj_size), int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF,
+                           int(image0) & 0xFFFFFFFF, ptr(out), _stream())
+    return out
+
+
+def aux_window_labels(boxes_norm, classes_bg, num, window_boxes, image_hw):
+    """labels.window_labels_exact on the device: classes_bg [B,G,K+1] one-hot, window_boxes [B,Wn,4] normalised
+    -> soft labels [B,Wn,K+1]. G is at most AUX_MAX_GT."""
+    B, G = _aux_gt(boxes_norm, num, classes_bg)
+    Wn = int(window_boxes.shape[1])
+    assert window_boxes.shape == (B, Wn, 4), window_boxes.shape
+    K1 = int(classes_bg.shape[2])
+    out = torch.empty((B, Wn, K1), dtype=f32, device=boxes_norm.device)
+    lib().aux_window_labels(ptr(_chk(boxes_norm)), ptr(_chk(classes_bg)), ptr(_chk(num, i32)), ptr(_chk(window_boxes)),
+                            B, G, K1 - 1, Wn, float(image_hw[0]), float(image_hw[1]), ptr(out), _stream())
+    return out
+
+
+def aux_closeness(boxes_norm, classes_bg, num, image_hw):
+    """labels.closeness_labels_exact on the device -> [B,G,K+1], rows past num[b] zero."""
+    B, G = _aux_gt(boxes_norm, num, classes_bg)
+    K1 = int(classes_bg.shape[2])
+    out = torch.empty((B, G, K1), dtype=f32, device=boxes_norm.device)
+    lib().aux_closeness(ptr(_chk(boxes_norm)), ptr(_chk(classes_bg)), ptr(_chk(num, i32)), B, G, K1 - 1,
+                        float(image_hw[0]), float(image_hw[1]), ptr(out), _stream())
+    return out
+
+
+def aux_edgemask(boxes_norm, num, image_hw, mask_size=64):
+    """labels.edgemask_exact on the device -> [B,2,mask_size,mask_size] (foreground mask, per-pixel weight)."""
+    B, G = _aux_gt(boxes_norm, num)
+    out = torch.empty((B, 2, int(mask_size), int(mask_size)), dtype=f32, device=boxes_norm.device)
+    lib().aux_edgemask(ptr(_chk(boxes_norm)), ptr(_chk(num, i32)), B, G, float(image_hw[0]), float(image_hw[1]),
+                       int(mask_size), ptr(out), _stream())
+    return out
+
+
 def hard_example_mining(loc_rl, cls_rl, boxes, num_proposals, d_box, d_cls, num_hard_examples, iou_threshold, loss_type):
     """core/losses.py:418-631 on the second stage (see mtlssl_hard_mining_*): loc_rl / cls_rl [B,n2] per-proposal
     losses, boxes [B,n2,4] the proposal boxes. Zeroes the gradient rows of proposals that were not mined (in place)

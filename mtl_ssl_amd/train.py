@@ -35,6 +35,10 @@ def _flags(argv):
     ap.add_argument("--input_pipeline", choices=("async", "host"), default="async",
                     help="async: decode workers + on-device flip / resize (mtl_ssl_amd.input_pipeline); host: the serial "
                          "generator input_reader.batches (the same batches, bit for bit)")
+    ap.add_argument("--aux_labels", choices=("record", "generate"), default="record",
+                    help="record: window / closeness / edge-mask labels are read from the records (frozen when they were "
+                         "written); generate: they are made on the device at every step from the boxes and classes "
+                         "alone, with fresh windows per step, so plain detection records train the auxiliary heads")
     return ap.parse_args(argv)
 
 
@@ -141,7 +145,7 @@ def main(argv=None):
     try:
         trainer.train(next_batch, lambda: probe, train_config, master=f.master, task=rank, num_clones=1,
                       worker_replicas=world, is_chief=rank == 0, train_dir=f.train_dir, model_config=model_config,
-                      num_steps=f.num_steps)
+                      num_steps=f.num_steps, aux_labels=f.aux_labels)
     finally:
         if hasattr(stream, "close"):
             stream.close()

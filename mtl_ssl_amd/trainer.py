@@ -277,10 +277,27 @@ def gradient_multipliers(ps, train_config):
     return torch.tensor(mult, dtype=torch.float32, device=ps.device)
 
 
+def _missing(v):
+    """A label field the batch does not carry: absent, an empty list, or a list of None."""
+    return v is None or (isinstance(v, (list, tuple)) and (len(v) == 0 or v[0] is None))
+
+
 class Trainer:
     """One training replica. step(batch) = forward + loss + backward + all-reduce + update."""
 
-    def __init__(self, model, train_config, world_size=1, comm=None, reduce_always=False):
+    AUX_LABEL_MODES = ("record", "generate")
+
+    def __init__(self, model, train_config, world_size=1, comm=None, reduce_always=False, aux_labels="record",
+                 aux_seed=None, aux_num_windows=64):
+        """aux_labels: "record" = the window / closeness / edge-mask labels come with the batch (frozen when the record
+        was written); "generate" = they are made on the device at every step from the batch's boxes and classes, with
+        fresh windows drawn for (aux_seed or the model's seed, global step, rank * B + b); such fields of the batch are
+        ignored."""
+        if aux_labels not in self.AUX_LABEL_MODES:
+            raise ValueError("aux_labels %r: one of %s" % (aux_labels, ", ".join(self.AUX_LABEL_MODES)))
+        self.aux_labels = aux_labels
+        self.aux_seed = int(getattr(model, "seed", 0) if aux_seed is None else aux_seed)
+        self.aux_num_windows = int(aux_num_windows)
         self.model, self.ps, self.cfg = model, model.ps, train_config
         self.opt = optimizer_from_config(train_config.optimizer)
         self.lr_fn, self.momentum = self.opt["lr_fn"], self.opt.get("momentum", 0.0)
@@ -365,6 +382,20 @@ class Trainer:
             gt, m._window, m._edgemask = batch["_staged"]
             m._gt = dict(gt)
             return
+        if self.aux_labels == "generate":
+            m.provide_groundtruth(batch["groundtruth_boxes"], batch["groundtruth_classes"], None)
+            B, H, W = (int(v) for v in batch["images"].shape[:3])
+            rank = int(getattr(self.comm, "rank", 0)) if self.comm is not None else 0
+            m.provide_generated_labels(self.aux_seed, self.global_step, m.resized_shape(H, W, m.cfg.image_resizer),
+                                       image0=rank * B, num_windows=self.aux_num_windows)
+            return
+        mtl = m._mtl
+        for on, field in ((mtl.window, "window_boxes"), (mtl.window, "window_classes"),
+                          (mtl.edgemask, "groundtruth_edgemask"), (mtl.closeness, "groundtruth_closeness")):
+            if on and _missing(batch.get(field)):
+                raise ValueError("the batch has no %r, which the switched-on auxiliary head needs: the records were "
+                                 "written without the frozen labels. Train with aux_labels=\"generate\" "
+                                 "(--aux_labels=generate) to make them on the device from the boxes." % field)
         m.provide_groundtruth(batch["groundtruth_boxes"], batch["groundtruth_classes"],
                               batch.get("groundtruth_closeness"))
         if m._mtl.window:
@@ -523,7 +554,7 @@ def collective_verdict(comm, code, device):
 def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=0, num_clones=1,
           worker_replicas=1, clone_on_cpu=False, ps_tasks=0, worker_job_name="lonely_worker",
           is_chief=True, train_dir=None, num_examples=0, total_configs=None, model_config=None,
-          is_first_training=True, num_steps=None, log_every=10, save_interval_secs=600):
+          is_first_training=True, num_steps=None, log_every=10, save_interval_secs=600, aux_labels="record"):
     """object_detection/trainer.py:217-219 signature. `create_tensor_dict_fn()` yields one batch
     dict per call (see mtl_ssl_amd.synthetic.make_batch for the field contract);
     `create_model_fn()` returns a built FasterRCNNMetaArch. Parameter-server arguments
@@ -534,7 +565,10 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
     from . import checkpoint
     world = dist.get_world_size() if dist.is_initialized() else 1
     model = create_model_fn()
-    trainer = Trainer(model, train_config, world)
+    trainer = Trainer(model, train_config, world, aux_labels=aux_labels)
+    if is_chief:
+        print("auxiliary labels: %s" % ("generated on the device from the boxes at every step (fresh windows per step)"
+                                        if aux_labels == "generate" else "read from the records"))
     # Resume from train_dir if a state file is there (slim.learning.train restores the latest checkpoint of
     # logdir), else initialise from fine_tune_checkpoint (trainer.py:309-356: a Saver over restore_map() that
     # FAILS when the checkpoint cannot be read). Containers: this build's .npz keyed by the reference's variable
