@@ -14,10 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests.f64_check import EPS, TINY, bits, dev, host, within
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EPS = float(np.finfo(np.float32).eps)
-TINY = float(np.finfo(np.float32).tiny)
 f32 = np.float32
 
 
@@ -28,31 +28,6 @@ def ops():
     from mtl_ssl_amd import ops
     assert torch.cuda.is_available()
     return ops
-
-
-def dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).cuda()
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def within(got, ref, tol, what):
-    got = np.asarray(got, np.float64)
-    err = np.abs(got - ref)
-    bad = ~(err <= tol)
-    if bad.any():
-        i = np.unravel_index(int(np.argmax(np.where(bad, err - tol, -np.inf))), err.shape) if err.ndim else ()
-        raise AssertionError("%s: %d elements out of bound; worst at %s: got %r, float64 %r, bound %r"
-                             % (what, int(bad.sum()), i, got[i], ref[i], np.broadcast_to(tol, err.shape)[i]))
-
-
-def bits(a, b, what):
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    diff = a.view(np.int32) != b.view(np.int32)
-    assert not diff.any(), "%s: %d elements differ, first at %s: %r vs %r" % (
-        what, int(diff.sum()), np.argwhere(diff)[0], a[tuple(np.argwhere(diff)[0])], b[tuple(np.argwhere(diff)[0])])
 
 
 def _configs1():
