@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 12
+#define MTLSSL_ABI_VERSION 13
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -541,6 +541,22 @@ int mtlssl_prepare_images(const uint8_t* pixels, const mtlssl_image_desc* desc, 
  * gives mtlssl_prepare_images's output. */
 int64_t mtlssl_prepare_images_aug_workspace(int B, int n_contrast, int max_H);
 int mtlssl_prepare_images_aug(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
+                              const int32_t* prog, int n_ops, const float* params, int P, int max_H, void* workspace,
+                              int64_t workspace_bytes, float* out, mtlssl_stream_t stream);
+/* mtlssl_prepare_images_aug generalised to programs that move the frame (ABI 13): two more op codes, OP_CROP (y0, x0,
+ * h, w: integers held exactly in float32; the identity crop is 0, 0, H, W) and OP_PAD (offset y, offset x, target h,
+ * target w, colour mode, r, g, b; mode 0: the given colour, otherwise the mean of the frame the pad receives), for
+ * random_crop_image :757, random_pad_image :856, random_crop_pad_image :959 and ssd_random_crop :1548. desc[n].H / W
+ * stay the SOURCE size; desc[n].sy / sx are float32(final H / OH), float32(final W / OW) of the frame after the whole
+ * program. Each output tap is walked back through the program to a source pixel or a pad colour and takes the ops of
+ * the stages it passes, each with the coordinate and frame width of its own stage, so the result equals
+ * resize_bilinear_legacy(apply_program(image)) to the bit and no read leaves the H x W source. Every contrast op and
+ * every pad op is a mean slot with the two pre-pass launches of mtlssl_prepare_images_aug over the frame of its stage
+ * (a pad with a given colour returns at once); `workspace` holds mtlssl_prepare_images_geo_workspace(B, contrast ops +
+ * pad ops, max_H) bytes, max_H >= the tallest frame of any stage of any image. A program without crop / pad ops gives
+ * mtlssl_prepare_images_aug's output. */
+int64_t mtlssl_prepare_images_geo_workspace(int B, int n_slots, int max_H);
+int mtlssl_prepare_images_geo(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
                               const int32_t* prog, int n_ops, const float* params, int P, int max_H, void* workspace,
                               int64_t workspace_bytes, float* out, mtlssl_stream_t stream);
 

@@ -67,9 +67,13 @@ FIELD_KIND = {
     "random_adjust_hue": "RandomAdjustHue", "random_distort_color": "RandomDistortColor",
     "random_rgb_to_gray": "RandomRGBtoGray", "random_pixel_value_scale": "RandomPixelValueScale",
     "random_black_patches": "RandomBlackPatches", "random_jitter_boxes": "RandomJitterBoxes",
+    "random_crop_image": "RandomCropImage", "random_pad_image": "RandomPadImage",
+    "random_crop_pad_image": "RandomCropPadImage", "ssd_random_crop": "SSDRandomCrop",
+    "operations": "SSDRandomCropOperation",
 }
 REPEATED = {"scales", "aspect_ratios", "schedule", "data_augmentation_options", "input_path",
-            "freeze_variables", "eval_metric_index", "metrics_set", "means"}
+            "freeze_variables", "eval_metric_index", "metrics_set", "means", "pad_color", "min_padded_size_ratio",
+            "max_padded_size_ratio", "operations"}
 
 DEFAULTS = {
     "DetectionModel": {"init_file": "", "mtl": "@MTL"},
@@ -157,6 +161,18 @@ DEFAULTS = {
     "RandomPixelValueScale": {"minval": 0.9, "maxval": 1.1},
     "RandomBlackPatches": {"max_black_patches": 10, "probability": 0.5, "size_to_image_ratio": 0.1},
     "RandomJitterBoxes": {"ratio": 0.05},
+    # the options that move the frame (preprocessor.parse_options(geometric=True)); an unset min/max_image_* or an
+    # empty list means "not given" to builders/preprocessor_builder.py:138-192
+    "RandomCropImage": {"min_object_covered": 1.0, "min_aspect_ratio": 0.75, "max_aspect_ratio": 1.33, "min_area": 0.1,
+                        "max_area": 1.0, "overlap_thresh": 0.3, "random_coef": 0.0},
+    "RandomPadImage": {"min_image_height": 0, "min_image_width": 0, "max_image_height": 0, "max_image_width": 0,
+                       "pad_color": []},
+    "RandomCropPadImage": {"min_object_covered": 1.0, "min_aspect_ratio": 0.75, "max_aspect_ratio": 1.33,
+                           "min_area": 0.1, "max_area": 1.0, "overlap_thresh": 0.3, "random_coef": 0.0,
+                           "min_padded_size_ratio": [], "max_padded_size_ratio": [], "pad_color": []},
+    "SSDRandomCrop": {"operations": []},
+    "SSDRandomCropOperation": {"min_object_covered": 0.0, "min_aspect_ratio": 0.0, "max_aspect_ratio": 0.0,
+                               "min_area": 0.0, "max_area": 0.0, "overlap_thresh": 0.0, "random_coef": 0.0},
 }
 
 _TOKEN = re.compile(r'\s*(?:(#[^\n]*)|("(?:[^"\\]|\\.)*"|\'(?:[^\'\\]|\\.)*\')|([{}<>:\[\],])|([^\s{}<>:\[\],#"\']+))')

@@ -676,7 +676,8 @@ __global__ void k_prepare_images(const uint8_t* __restrict__ pixels, const mtlss
 // there); this file is built with -ffp-contract=off, so the two agree to the bit.
 enum : int {
   kAugFlip = 0, kAugNormalize, kAugSubMean, kAugAdd, kAugContrast, kAugSaturation, kAugHue, kAugClip, kAugGray,
-  kAugPixelScale, kAugPatch, kAugNumOps
+  kAugPixelScale, kAugPatch, kAugNumOps,               // what mtlssl_prepare_images_aug takes
+  kAugCrop = kAugNumOps, kAugPad, kAugNumGeoOps         // + the ops that move the frame (mtlssl_prepare_images_geo)
 };
 constexpr int kAugMaxOps = 128;
 constexpr uint32_t kAugPixelScaleStream = 0x50584C53u;
@@ -687,7 +688,8 @@ struct AugProgram {            // passed by value: the host validates it and pla
 __host__ __device__ __forceinline__ int aug_nparams(int code) {
   return code == kAugNormalize || code == kAugSubMean || code == kAugPixelScale ? 3
          : code == kAugClip                                                      ? 0
-         : code == kAugPatch                                                     ? 4
+         : code == kAugPatch || code == kAugCrop                                 ? 4
+         : code == kAugPad                                                       ? 8
                                                                                  : 1;
 }
 __device__ __forceinline__ uint32_t aug_mix32(uint32_t seed, uint32_t stream, uint32_t i) {   // glue.hip glue_mix32
@@ -764,6 +766,53 @@ __device__ __forceinline__ void aug_saturation(float v[3], float k) {
   }
   v[0] = rr + m; v[1] = gg + m; v[2] = bb + m;
 }
+// One colour op on the 3 channels of a pixel at row y, column cx of a frame W wide (the frame of the op's own stage);
+// m: the op's mean (contrast only). Flips, crops and pads move coordinates and are the caller's.
+__device__ __forceinline__ void aug_apply(int code, const float* __restrict__ p, const float* __restrict__ m, int y,
+                                          int cx, int W, float v[3]) {
+  switch (code) {
+    case kAugNormalize:
+      for (int c = 0; c < 3; ++c) v[c] = (v[c] - p[0]) * p[1] + p[2];
+      break;
+    case kAugSubMean:
+      for (int c = 0; c < 3; ++c) v[c] = v[c] - p[c];
+      break;
+    case kAugAdd:
+      for (int c = 0; c < 3; ++c) v[c] = v[c] + p[0];
+      break;
+    case kAugContrast:
+      for (int c = 0; c < 3; ++c) v[c] = (v[c] - m[c]) * p[0] + m[c];
+      break;
+    case kAugSaturation: aug_saturation(v, p[0]); break;
+    case kAugHue: aug_hue(v, p[0]); break;
+    case kAugClip:
+      for (int c = 0; c < 3; ++c) v[c] = aug_clip01(v[c]);
+      break;
+    case kAugGray:
+      if (p[0] != 0.f) {
+        const float gray = (v[0] * 0.2989f + v[1] * 0.5870f) + v[2] * 0.1140f;
+        v[0] = gray; v[1] = gray; v[2] = gray;
+      }
+      break;
+    case kAugPixelScale: {
+      const uint32_t seed = __float_as_uint(p[0]);
+      const uint32_t e = ((uint32_t)y * (uint32_t)W + (uint32_t)cx) * 3u;
+      for (int c = 0; c < 3; ++c) {
+        const float u = (float)(aug_mix32(seed, kAugPixelScaleStream, e + c) >> 8) * 0x1p-24f;
+        v[c] = v[c] * (p[1] + p[2] * u);
+      }
+      break;
+    }
+    case kAugPatch:
+      if (p[0] != 0.f) {
+        const int y0 = (int)p[1], x0 = (int)p[2], box = (int)p[3];
+        if (y >= y0 && y < y0 + box && cx >= x0 && cx < x0 + box)
+          for (int c = 0; c < 3; ++c) v[c] = v[c] * 0.f;
+      }
+      break;
+    default: break;
+  }
+}
 // The 3 channels of pixel (y, x) of image n after the first `n_ops` ops, (y, x) in that stage's coordinates (flips
 // mirror the columns). prm: the image's P parameters; means: its contrast means, [contrast op][3].
 __device__ __forceinline__ void aug_pixel(const uint8_t* __restrict__ src, int H, int W, bool src_flip, int y, int x,
@@ -784,54 +833,13 @@ __device__ __forceinline__ void aug_pixel(const uint8_t* __restrict__ src, int H
     const int code = pr.code[i];
     const float* p = prm + k;
     k += aug_nparams(code);
-    switch (code) {
-      case kAugFlip:
-        if (p[0] != 0.f) cx = W - 1 - cx;
-        break;
-      case kAugNormalize:
-        for (int c = 0; c < 3; ++c) v[c] = (v[c] - p[0]) * p[1] + p[2];
-        break;
-      case kAugSubMean:
-        for (int c = 0; c < 3; ++c) v[c] = v[c] - p[c];
-        break;
-      case kAugAdd:
-        for (int c = 0; c < 3; ++c) v[c] = v[c] + p[0];
-        break;
-      case kAugContrast: {
-        const float* m = means + nc * 3;
-        ++nc;
-        for (int c = 0; c < 3; ++c) v[c] = (v[c] - m[c]) * p[0] + m[c];
-        break;
-      }
-      case kAugSaturation: aug_saturation(v, p[0]); break;
-      case kAugHue: aug_hue(v, p[0]); break;
-      case kAugClip:
-        for (int c = 0; c < 3; ++c) v[c] = aug_clip01(v[c]);
-        break;
-      case kAugGray:
-        if (p[0] != 0.f) {
-          const float gray = (v[0] * 0.2989f + v[1] * 0.5870f) + v[2] * 0.1140f;
-          v[0] = gray; v[1] = gray; v[2] = gray;
-        }
-        break;
-      case kAugPixelScale: {
-        const uint32_t seed = __float_as_uint(p[0]);
-        const uint32_t e = ((uint32_t)y * (uint32_t)W + (uint32_t)cx) * 3u;
-        for (int c = 0; c < 3; ++c) {
-          const float u = (float)(aug_mix32(seed, kAugPixelScaleStream, e + c) >> 8) * 0x1p-24f;
-          v[c] = v[c] * (p[1] + p[2] * u);
-        }
-        break;
-      }
-      case kAugPatch:
-        if (p[0] != 0.f) {
-          const int y0 = (int)p[1], x0 = (int)p[2], box = (int)p[3];
-          if (y >= y0 && y < y0 + box && cx >= x0 && cx < x0 + box)
-            for (int c = 0; c < 3; ++c) v[c] = v[c] * 0.f;
-        }
-        break;
-      default: break;
+    if (code == kAugFlip) {
+      if (p[0] != 0.f) cx = W - 1 - cx;
+      continue;
     }
+    const float* m = means + nc * 3;
+    nc += code == kAugContrast;
+    aug_apply(code, p, m, y, cx, W, v);
   }
 }
 // Contrast pre-pass, one launch pair per contrast op of the program (op index `stage`): k_aug_rowsum sums each row
@@ -902,6 +910,171 @@ __global__ void k_prepare_images_aug(const uint8_t* __restrict__ pixels, const m
   aug_pixel(src, H, W, fl, y0, x1, pr, pr.n, prm, mn, tr);
   aug_pixel(src, H, W, fl, y1, x0, pr, pr.n, prm, mn, bl);
   aug_pixel(src, H, W, fl, y1, x1, pr, pr.n, prm, mn, br);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c] = resize_blend(tl[c], tr[c], bl[c], br[c], yl, xl);
+}
+// Geometric augmentation (core/preprocessor.py random_crop_image :757, random_pad_image :856, random_crop_pad_image
+// :959, ssd_random_crop :1548) inside the preparation: kAugCrop (y0, x0, h, w) and kAugPad (offset y, offset x,
+// target h, target w, colour mode, r, g, b) change the frame between ops, so every op has the frame of its own stage.
+// An output tap is walked BACKWARDS from the final frame to the source (a flip mirrors within its stage's width, a crop
+// adds its offset, a pad subtracts its offset); a tap that lands in the padding of op s starts there with the pad
+// colour and takes only the ops after s, any other tap reads the uint8 source and takes them all. No intermediate
+// image exists. Host restatement: preprocessor.apply_program.
+struct GeoProgram {            // passed by value; built and validated by the host entry point
+  int n;
+  int n_slots;                       // mean slots: one per contrast op and per pad op, in program order
+  int8_t code[kAugMaxOps];
+  uint8_t slot[kAugMaxOps];          // mean slot of op i (contrast and pad ops)
+  uint16_t koff[kAugMaxOps + 1];     // offset of op i's parameters in an image's P
+};
+// The frame before each of the first `upto` ops (fh[i] x fw[i], i <= upto; fh[upto] x fw[upto] is the frame after them).
+__device__ __forceinline__ void geo_frames(const GeoProgram& pr, const float* __restrict__ prm, int H, int W, int upto,
+                                           int* fh, int* fw) {
+  int h = H, w = W;
+  for (int i = 0; i < upto; ++i) {
+    fh[i] = h; fw[i] = w;
+    const int code = pr.code[i];
+    if (code == kAugCrop || code == kAugPad) {
+      h = (int)prm[pr.koff[i] + 2];
+      w = (int)prm[pr.koff[i] + 3];
+    }
+  }
+  fh[upto] = h; fw[upto] = w;
+}
+// The 3 channels of pixel (y, x) of the frame after the first `n_ops` ops. fh / fw: geo_frames of this image; means:
+// the image's mean slots [slot][3], filled for every slot before op n_ops.
+__device__ __forceinline__ void geo_pixel(const uint8_t* __restrict__ src, int H, int W, bool src_flip, int y, int x,
+                                          const GeoProgram& pr, int n_ops, const float* __restrict__ prm,
+                                          const float* __restrict__ means, const int* fh, const int* fw, float v[3]) {
+  int start = 0;
+  bool padding = false;
+  for (int i = n_ops - 1; i >= 0; --i) {
+    const int code = pr.code[i];
+    const float* p = prm + pr.koff[i];
+    if (code == kAugFlip) {
+      if (p[0] != 0.f) x = fw[i] - 1 - x;
+    } else if (code == kAugCrop) {
+      y += (int)p[0]; x += (int)p[1];
+    } else if (code == kAugPad) {
+      const int yy = y - (int)p[0], xx = x - (int)p[1];
+      if (yy < 0 || yy >= fh[i] || xx < 0 || xx >= fw[i]) {          // in the padding of op i: (y, x) stays in ITS frame
+        const float* c = p[4] != 0.f ? means + pr.slot[i] * 3 : p + 5;
+        v[0] = c[0]; v[1] = c[1]; v[2] = c[2];
+        start = i + 1;
+        padding = true;
+        break;
+      }
+      y = yy; x = xx;
+    }
+  }
+  if (!padding) {
+    // inside H x W by construction (every crop lies in its frame); the clamp only guards the read against bad parameters
+    const int sy = min(max(y, 0), H - 1), cx = min(max(x, 0), W - 1);
+    const uint8_t* s = src + ((int64_t)sy * W + (src_flip ? W - 1 - cx : cx)) * 3;
+    v[0] = (float)s[0]; v[1] = (float)s[1]; v[2] = (float)s[2];
+  }
+  for (int i = start; i < n_ops; ++i) {
+    const int code = pr.code[i];
+    const float* p = prm + pr.koff[i];
+    if (code == kAugFlip) {
+      if (p[0] != 0.f) x = fw[i] - 1 - x;
+    } else if (code == kAugCrop) {
+      y -= (int)p[0]; x -= (int)p[1];
+    } else if (code == kAugPad) {
+      y += (int)p[0]; x += (int)p[1];
+    } else {
+      aug_apply(code, p, means + pr.slot[i] * 3, y, x, fw[i], v);
+    }
+  }
+}
+// Pre-pass of one mean slot (op `stage`: a contrast op, or a pad whose colour is the mean of its input frame), as
+// k_aug_rowsum / k_aug_mean but over the frame of that stage, which may hold padding of an earlier slot. A pad with a
+// given colour skips the work.
+__device__ __forceinline__ bool geo_slot_unused(const GeoProgram& pr, int stage, const float* __restrict__ prm) {
+  return pr.code[stage] == kAugPad && prm[pr.koff[stage] + 4] == 0.f;
+}
+__global__ void k_geo_rowsum(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
+                             GeoProgram pr, int stage, const float* __restrict__ params, int P,
+                             const float* __restrict__ means, int max_H, double* __restrict__ rows) {
+  __shared__ int fh[kAugMaxOps + 1], fw[kAugMaxOps + 1];
+  const int n = blockIdx.y;
+  const int y = blockIdx.x * blockDim.x + threadIdx.x;
+  const mtlssl_image_desc d = desc[n];
+  const float* prm = params + (int64_t)n * P;
+  if (threadIdx.x == 0) geo_frames(pr, prm, d.H, d.W, stage, fh, fw);
+  __syncthreads();
+  if (geo_slot_unused(pr, stage, prm)) return;
+  const int FH = fh[stage], FW = fw[stage];
+  if (y >= FH || y >= max_H) return;
+  const uint8_t* src = pixels + d.offset;
+  const float* mn = means + (int64_t)n * pr.n_slots * 3;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int x = 0; x < FW; ++x) {
+    float v[3];
+    geo_pixel(src, d.H, d.W, d.flip != 0, y, x, pr, stage, prm, mn, fh, fw, v);
+    s0 += (double)v[0]; s1 += (double)v[1]; s2 += (double)v[2];
+  }
+  double* o = rows + ((int64_t)n * max_H + y) * 3;
+  o[0] = s0; o[1] = s1; o[2] = s2;
+}
+__global__ void k_geo_mean(const mtlssl_image_desc* __restrict__ desc, GeoProgram pr, int stage,
+                           const float* __restrict__ params, int P, int max_H, const double* __restrict__ rows,
+                           float* __restrict__ means) {
+  const int n = blockIdx.x, c = threadIdx.x;
+  if (c >= 3) return;
+  const mtlssl_image_desc d = desc[n];
+  const float* prm = params + (int64_t)n * P;
+  if (geo_slot_unused(pr, stage, prm)) return;
+  int FH = d.H, FW = d.W;
+  for (int i = 0; i < stage; ++i)
+    if (pr.code[i] == kAugCrop || pr.code[i] == kAugPad) {
+      FH = (int)prm[pr.koff[i] + 2];
+      FW = (int)prm[pr.koff[i] + 3];
+    }
+  float m = __builtin_nanf("");                          // a frame taller than max_H: visibly wrong, never a stray read
+  if (FH <= max_H) {
+    const double* r = rows + (int64_t)n * max_H * 3 + c;
+    double t = 0.0;
+    for (int y = 0; y < FH; ++y) t += r[(int64_t)y * 3];
+    m = (float)(t / (double)((int64_t)FH * FW));
+  }
+  means[((int64_t)n * pr.n_slots + pr.slot[stage]) * 3 + c] = m;
+}
+// k_prepare_images_aug over the final frame of the program: desc.sy / sx are float32(final H / OH), float32(final W /
+// OW), and the no-resize branch is taken when the FINAL frame equals OH x OW.
+__global__ void k_prepare_images_geo(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
+                                     int OH, int OW, GeoProgram pr, const float* __restrict__ params, int P,
+                                     const float* __restrict__ means, float* __restrict__ out) {
+  __shared__ int fh[kAugMaxOps + 1], fw[kAugMaxOps + 1];
+  const int n = blockIdx.y;
+  const mtlssl_image_desc d = desc[n];
+  const float* prm = params + (int64_t)n * P;
+  if (threadIdx.x == 0) geo_frames(pr, prm, d.H, d.W, pr.n, fh, fw);
+  __syncthreads();
+  const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (p >= (int64_t)OH * OW) return;
+  const int H = d.H, W = d.W, FH = fh[pr.n], FW = fw[pr.n];
+  const bool fl = d.flip != 0;
+  const uint8_t* src = pixels + d.offset;
+  const float* mn = means + (int64_t)n * pr.n_slots * 3;
+  const int oy = (int)(p / OW), ox = (int)(p % OW);
+  float* o = out + ((int64_t)n * OH * OW + p) * 3;
+  if (FH == OH && FW == OW) {
+    float v[3];
+    geo_pixel(src, H, W, fl, oy, ox, pr, pr.n, prm, mn, fh, fw, v);
+    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+    return;
+  }
+  int y0, y1, x0, x1;
+  float yl, xl;
+  resize_taps(oy, d.sy, FH, y0, y1, yl);
+  resize_taps(ox, d.sx, FW, x0, x1, xl);
+  y0 = min(y0, FH - 1); x0 = min(x0, FW - 1);
+  float tl[3], tr[3], bl[3], br[3];
+  geo_pixel(src, H, W, fl, y0, x0, pr, pr.n, prm, mn, fh, fw, tl);
+  geo_pixel(src, H, W, fl, y0, x1, pr, pr.n, prm, mn, fh, fw, tr);
+  geo_pixel(src, H, W, fl, y1, x0, pr, pr.n, prm, mn, fh, fw, bl);
+  geo_pixel(src, H, W, fl, y1, x1, pr, pr.n, prm, mn, fh, fw, br);
 #pragma unroll
   for (int c = 0; c < 3; ++c) o[c] = resize_blend(tl[c], tr[c], bl[c], br[c], yl, xl);
 }
@@ -1609,6 +1782,50 @@ int mtlssl_prepare_images_aug(const uint8_t* pixels, const mtlssl_image_desc* de
   hipLaunchKernelGGL(k_prepare_images_aug, dim3((unsigned)cdiv(pix, 256), (unsigned)B), dim3(256), 0, S(stream),
                      pixels, desc, OH, OW, pr, params, P, means, n_contrast, out);
   return check_launch("prepare_images_aug");
+}
+int64_t mtlssl_prepare_images_geo_workspace(int B, int n_slots, int max_H) {
+  return mtlssl_prepare_images_aug_workspace(B, n_slots, max_H);
+}
+int mtlssl_prepare_images_geo(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
+                              const int32_t* prog, int n_ops, const float* params, int P, int max_H, void* workspace,
+                              int64_t workspace_bytes, float* out, mtlssl_stream_t stream) {
+  MTLSSL_REQUIRE(B >= 0 && B <= 65535 && OH > 0 && OW > 0, "prepare_images_geo: bad geometry");
+  MTLSSL_REQUIRE(n_ops >= 0 && n_ops <= kAugMaxOps, "prepare_images_geo: %d ops, at most %d", n_ops, kAugMaxOps);
+  MTLSSL_REQUIRE(n_ops == 0 || prog, "prepare_images_geo: null program");
+  GeoProgram pr;
+  memset(&pr, 0, sizeof(pr));
+  pr.n = n_ops;
+  int need = 0, n_slots = 0;
+  for (int i = 0; i < n_ops; ++i) {
+    MTLSSL_REQUIRE(prog[i] >= 0 && prog[i] < kAugNumGeoOps, "prepare_images_geo: bad op code %d at op %d", prog[i], i);
+    pr.code[i] = (int8_t)prog[i];
+    pr.koff[i] = (uint16_t)need;
+    need += aug_nparams(prog[i]);
+    if (prog[i] == kAugContrast || prog[i] == kAugPad) pr.slot[i] = (uint8_t)n_slots++;
+  }
+  pr.koff[n_ops] = (uint16_t)need;
+  pr.n_slots = n_slots;
+  MTLSSL_REQUIRE(P == need, "prepare_images_geo: the program takes %d parameters per image, P = %d", need, P);
+  MTLSSL_REQUIRE(P == 0 || B == 0 || params, "prepare_images_geo: null parameters");
+  const int64_t ws = mtlssl_prepare_images_geo_workspace(B, n_slots, max_H);
+  MTLSSL_REQUIRE(n_slots == 0 || (max_H >= 1 && workspace && workspace_bytes >= ws),
+                 "prepare_images_geo: %d mean slots need max_H >= 1 and %lld workspace bytes, got max_H = %d and %lld",
+                 n_slots, (long long)ws, max_H, (long long)workspace_bytes);
+  if (!B) return MTLSSL_OK;
+  float* means = static_cast<float*>(workspace);
+  double* rows = n_slots ? reinterpret_cast<double*>(static_cast<char*>(workspace) + (ws - (int64_t)B * max_H * 24))
+                         : nullptr;
+  for (int i = 0; i < n_ops; ++i) {                      // slots in program order: a later one may read an earlier one
+    if (pr.code[i] != kAugContrast && pr.code[i] != kAugPad) continue;
+    hipLaunchKernelGGL(k_geo_rowsum, dim3((unsigned)cdiv(max_H, 64), (unsigned)B), dim3(64), 0, S(stream), pixels,
+                       desc, pr, i, params, P, means, max_H, rows);
+    hipLaunchKernelGGL(k_geo_mean, dim3((unsigned)B), dim3(64), 0, S(stream), desc, pr, i, params, P, max_H, rows,
+                       means);
+  }
+  const int64_t pix = (int64_t)OH * OW;
+  hipLaunchKernelGGL(k_prepare_images_geo, dim3((unsigned)cdiv(pix, 256), (unsigned)B), dim3(256), 0, S(stream),
+                     pixels, desc, OH, OW, pr, params, P, means, out);
+  return check_launch("prepare_images_geo");
 }
 int mtlssl_resize_bilinear_bwd(const float* dy, float* dx, int N, int H, int W, int C, int OH,
                                int OW, mtlssl_stream_t stream) {

@@ -11,11 +11,14 @@ The reference overlaps its input with the step through parallel readers and pref
 * Worker processes (the `spawn` context: a process that has initialised HIP is never forked, and a worker never
   imports torch) read the record, parse the tf.Example, decode the image to uint8, turn the consumer's draws into
   the image's float32 op parameters (`preprocessor.plan`: flip flags, jitter, colour deltas, patch corners, seeds)
-  and apply the label side (flips, box jitter); they return the image and its parameters.
-* The consumer buckets the decoded examples by resized shape exactly like `batches` (same flushes, same remainder).
+  and apply the label side (flips, box jitter, crops and pads); they return the image, its parameters and the size
+  of the frame the program ends in.
+* The consumer buckets the decoded examples by the resized shape of that final frame exactly like `batches` (same
+  flushes, same remainder).
 * On a GPU, a batch is packed into a pinned staging slot (descriptors + op parameters + uint8 pixels), copied in one
   H2D copy and turned into the float32 [B,OH,OW,3] batch on a stream of its own: `ops.prepare_images` when the
-  options are flips only, `ops.prepare_images_aug` (the op program before the resize) otherwise. The consumer's
+  options are flips only, `ops.prepare_images_aug` (the op program before the resize) otherwise, or
+  `ops.prepare_images_geo` when the program crops or pads. The consumer's
   stream waits on the batch's event at hand-out. Copies and kernels are launched from the consumer's thread, so no
   second Python thread competes with the step's launch thread. On the CPU, the host preparer runs the numpy path
   (`preprocessor.apply_program`, then `resize_bilinear_legacy`).
@@ -33,10 +36,10 @@ import numpy as np
 from . import input_reader, preprocessor
 
 
-def option_draw_counts(augmentation_options):
+def option_draw_counts(augmentation_options, geometric=False):
     """The uniform draws `preprocessor.preprocess` makes per example for each listed option, in config order
     (refusing what preprocess refuses)."""
-    return [s.draws for s in preprocessor.parse_options(augmentation_options, warn=False)]
+    return [s.draws for s in preprocessor.parse_options(augmentation_options, warn=False, geometric=geometric)]
 
 
 def default_num_workers(num_readers=8, local_ranks=1):
@@ -68,21 +71,23 @@ def record_spans(path):
             pos += 16 + n
 
 
-def decode_record(serialized, num_classes, steps, draws, timings=None):
-    """-> (example with a uint8 image and augmented labels, float32 op parameters of the image). `steps`: the parsed
-    options (preprocessor.parse_options); `draws`: the consumer's uniform draws of this record (preprocessor.preprocess
-    takes the same ones up front). The labels are flipped / jittered one action after the other, like the host path
-    (1 - (1 - x) need not be x)."""
+def decode_record(serialized, num_classes, steps, draws, timings=None, geometric=False):
+    """-> (example with the uint8 image as decoded and augmented labels, float32 op parameters of the image, the
+    (height, width) of the frame after the program). `steps`: the parsed options (preprocessor.parse_options); `draws`:
+    the consumer's uniform draws of this record (preprocessor.preprocess takes the same ones up front). The labels are
+    flipped / jittered / cropped / padded one action after the other, like the host path (1 - (1 - x) need not be x).
+    geometric=True drops the record's frozen auxiliary labels, like preprocess."""
     ex = input_reader.decode_example_uint8(serialized, num_classes, timings)
     image = ex.pop("image")
-    params, actions = preprocessor.plan(steps, draws, image.shape[0], image.shape[1],
-                                        np.asarray(ex["groundtruth_boxes"]).reshape(-1, 4).shape[0])
-    ex = preprocessor.apply_labels(ex, actions)
+    params, actions, frame = preprocessor.plan(steps, draws, image.shape[0], image.shape[1],
+                                               np.asarray(ex["groundtruth_boxes"], np.float32).reshape(-1, 4),
+                                               frame=True)
+    ex = preprocessor.apply_labels(preprocessor.drop_aux_fields(ex) if geometric else ex, actions)
     ex["image"] = image
-    return ex, params
+    return ex, params, frame
 
 
-def _worker_main(tasks, results, num_classes, steps):
+def _worker_main(tasks, results, num_classes, steps, geometric=False):
     files = {}
     while True:
         task = tasks.get()
@@ -98,8 +103,8 @@ def _worker_main(tasks, results, num_classes, steps):
             data = f.read(length)
             if len(data) != length:
                 raise IOError("truncated record")
-            ex, params = decode_record(data, num_classes, steps, draws, timings)
-            results.put((seq, ex, params, timings, None))
+            ex, params, frame = decode_record(data, num_classes, steps, draws, timings, geometric)
+            results.put((seq, ex, (params, frame), timings, None))
         except Exception as e:
             results.put((seq, None, None, timings, "record %d of %s: %s: %s\n%s" % (
                 index, path, type(e).__name__, e, traceback.format_exc())))
@@ -118,7 +123,7 @@ class _HostPreparer:
 
     def prepare(self, items, OH, OW):
         exs = []
-        for ex, params in items:
+        for ex, (params, _) in items:
             img = preprocessor.apply_program(np.asarray(ex["image"], np.float32), self.codes, params)
             exs.append(dict(ex, image=preprocessor.resize_bilinear_legacy(img, OH, OW)))
         return input_reader.collate(exs)
@@ -130,7 +135,9 @@ class _HostPreparer:
 class _DevicePreparer:
     """Pinned staging ring -> one H2D copy + one mtlssl_prepare_images launch per batch on a dedicated stream (a
     program of flips only: the net flip goes into the descriptor), or mtlssl_prepare_images_aug with the batch's
-    [B, P] op parameters staged between the descriptors and the pixels."""
+    [B, P] op parameters staged between the descriptors and the pixels; a program with a crop or a pad goes to
+    mtlssl_prepare_images_geo, with the scales of each image's final frame in its descriptor. The whole decoded image
+    is copied even when a crop keeps a part of it."""
 
     _ALIGN = 256
 
@@ -140,6 +147,7 @@ class _DevicePreparer:
         self.codes = list(codes)
         self.P = preprocessor.num_params(self.codes)
         self.flips_only = all(c == preprocessor.OP_FLIP for c in self.codes)
+        self.geo = preprocessor.has_geometric(self.codes)
         self.device = device
         self.stream = torch.cuda.Stream(device)
         self.slots = [None] * slots          # pinned uint8 staging buffers
@@ -152,10 +160,11 @@ class _DevicePreparer:
         torch = self.torch
         from . import ops
         if self.flips_only:      # the net mirror of the listed flips (the flip flag is each op's one parameter)
-            flips, P = [int(np.count_nonzero(p)) % 2 == 1 for _, p in items], 0
+            flips, P = [int(np.count_nonzero(p)) % 2 == 1 for _, (p, _) in items], 0
         else:
             flips, P = [False] * len(items), self.P
-        desc, nbytes = ops.image_descs([ex["image"].shape[:2] for ex, _ in items], flips, OH, OW)
+        desc, nbytes = ops.image_descs([ex["image"].shape[:2] for ex, _ in items], flips, OH, OW,
+                                       [frame for _, (_, frame) in items] if self.geo else None)
         align = lambda n: -(-n // self._ALIGN) * self._ALIGN
         poff = align(desc.nbytes)
         head = poff + align(len(items) * P * 4)
@@ -170,7 +179,7 @@ class _DevicePreparer:
         host = buf.numpy()
         host[:desc.nbytes] = desc.view(np.uint8)
         if P:
-            host[poff:poff + len(items) * P * 4] = np.stack([p for _, p in items]).astype(np.float32).view(np.uint8).reshape(-1)
+            host[poff:poff + len(items) * P * 4] = np.stack([p for _, (p, _) in items]).astype(np.float32).view(np.uint8).reshape(-1)
         off = head
         for ex, _ in items:
             a = np.ascontiguousarray(ex["image"], np.uint8).reshape(-1)
@@ -186,6 +195,11 @@ class _DevicePreparer:
                 ev[1].record(self.stream)
             if self.flips_only:
                 out = ops.prepare_images(dev[head:], dev[:desc.nbytes], len(items), OH, OW)
+            elif self.geo:
+                max_H = max(h for ex, (p, _) in items
+                            for h, _ in preprocessor.stage_frames(self.codes, p, *ex["image"].shape[:2]))
+                out = ops.prepare_images_geo(dev[head:], dev[:desc.nbytes], len(items), OH, OW, self.codes,
+                                             dev[poff:head], P, max_H)
             else:
                 out = ops.prepare_images_aug(dev[head:], dev[:desc.nbytes], len(items), OH, OW, self.codes,
                                              dev[poff:head], P, max(ex["image"].shape[0] for ex, _ in items))
@@ -219,17 +233,19 @@ class InputPipeline:
     preparer yields exactly batches()'s dicts.
 
     num_workers: decode processes (default: `default_num_workers()` of 8 readers); local_ranks: ranks on this node
-    sharing its CPUs; prefetch: batches decoded / staged ahead of the consumer (train.proto prefetch_queue_capacity).
+    sharing its CPUs; prefetch: batches decoded / staged ahead of the consumer (train.proto prefetch_queue_capacity);
+    geometric: as in input_reader.batches (random crop / pad options run, no frozen auxiliary labels).
     """
 
     def __init__(self, paths, num_classes, batch_size, augmentation_options=(), rng=None, loop=False, rank=0,
                  world=1, shuffle_buffer=0, resized_shape=None, max_pending=64, drop_remainder=False, device="cpu",
-                 num_workers=None, prefetch=10, local_ranks=1, profile=False):
+                 num_workers=None, prefetch=10, local_ranks=1, profile=False, geometric=False):
         self.paths = list(paths)
         self.num_classes = int(num_classes)
         self.batch_size = int(batch_size)
         self.options = list(augmentation_options or ())
-        self.steps = preprocessor.parse_options(self.options)
+        self.geometric = bool(geometric)
+        self.steps = preprocessor.parse_options(self.options, geometric=self.geometric)
         self.codes = preprocessor.program(self.steps)
         self.n_draws = preprocessor.draw_count(self.steps)
         self.rng = rng if rng is not None else np.random.RandomState(0)
@@ -256,7 +272,7 @@ class InputPipeline:
         self._tasks, self._results = ctx.Queue(), ctx.Queue()
         try:
             for _ in range(self.num_workers):
-                p = ctx.Process(target=_worker_main, args=(self._tasks, self._results, self.num_classes, self.steps),
+                p = ctx.Process(target=_worker_main, args=(self._tasks, self._results, self.num_classes, self.steps, self.geometric),
                                 daemon=True)
                 p.start()
                 self._procs.append(p)
@@ -313,7 +329,8 @@ class InputPipeline:
 
     # ---------------------------------------------------------------- bucketing of input_reader.batches
     def _bucket(self, ex, params):
-        H, W = ex["image"].shape[:2]
+        """`params`: the worker's (op parameters, final frame); the frame is the source size unless a crop / pad moved it."""
+        H, W = params[1]
         key = tuple(self.resized_shape(H, W)) if self.resized_shape is not None else (H, W)
         self._buckets.setdefault(key, []).append((ex, params))
         self._pending += 1

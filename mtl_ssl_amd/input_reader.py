@@ -278,7 +278,7 @@ def decode_example_uint8(serialized, num_classes, timings=None):
 
 
 def examples(paths, num_classes, augmentation_options=(), rng=None, loop=False, rank=0, world=1,
-             shuffle_buffer=0):
+             shuffle_buffer=0, geometric=False):
     """Decoded + augmented examples of a list of TFRecord files (builders/input_reader_builder.py:34-65:
     parallel_reader with a shuffling RandomShuffleQueue, then core/preprocessor.preprocess). Data-parallel
     ranks read disjoint records (record i of the stream goes to rank i % world — the reference's clones each
@@ -287,7 +287,8 @@ def examples(paths, num_classes, augmentation_options=(), rng=None, loop=False, 
     `min_after_dequeue` elements (protos/input_reader.proto: queue_capacity 2000, min_after_dequeue 1000): a record
     is a few hundred KB of JPEG, a decoded and augmented example ~5 MB of float32 — decoding happens after the
     draw, one example at a time, so the buffer costs megabytes and the first step does not wait for a thousand
-    JPEG decodes."""
+    JPEG decodes. geometric=True: preprocessor.preprocess also runs the random crop / pad options and the examples
+    carry no frozen auxiliary labels."""
     from . import preprocessor
     rng = rng if rng is not None else np.random.RandomState(0)
 
@@ -320,11 +321,11 @@ def examples(paths, num_classes, augmentation_options=(), rng=None, loop=False, 
             yield buf.pop()
 
     for rec in shuffled():
-        yield preprocessor.preprocess(decode_example(rec, num_classes), augmentation_options, rng)
+        yield preprocessor.preprocess(decode_example(rec, num_classes), augmentation_options, rng, geometric=geometric)
 
 
 def batches(paths, num_classes, batch_size, augmentation_options=(), rng=None, loop=False, rank=0, world=1,
-            shuffle_buffer=0, resized_shape=None, max_pending=64, drop_remainder=False):
+            shuffle_buffer=0, resized_shape=None, max_pending=64, drop_remainder=False, geometric=False):
     """core/batcher.py for a per-GPU batch > 1. The reference gives every clone ONE image at its own shape
     (batch_size // num_clones, trainer.py:270) and never stacks images; a GPU here takes `batch_size` images
     per step as one NHWC tensor, so images are grouped by shape: with `resized_shape(h, w) -> (nh, nw)` (the
@@ -334,10 +335,12 @@ def batches(paths, num_classes, batch_size, augmentation_options=(), rng=None, l
     reference computes it. More than `max_pending` waiting images flush the fullest bucket as a smaller
     batch; what is left at the end of a non-looping stream is emitted too unless `drop_remainder`. Under data
     parallelism such a short batch weighs its images 1/len instead of 1/batch_size on that rank for that step (every
-    loss is a batch mean) — a slightly re-weighted but valid step; raise `max_pending` to make it rarer."""
+    loss is a batch mean) — a slightly re-weighted but valid step; raise `max_pending` to make it rarer. With
+    geometric=True the image an example arrives with is the final frame of its crop / pad options, so that frame is
+    what gets resized and bucketed."""
     from . import preprocessor
     buckets, pending = {}, 0
-    for ex in examples(paths, num_classes, augmentation_options, rng, loop, rank, world, shuffle_buffer):
+    for ex in examples(paths, num_classes, augmentation_options, rng, loop, rank, world, shuffle_buffer, geometric):
         if resized_shape is not None:
             nh, nw = resized_shape(ex["image"].shape[0], ex["image"].shape[1])
             ex = dict(ex, image=preprocessor.resize_bilinear_legacy(ex["image"], nh, nw))

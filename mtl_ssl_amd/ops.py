@@ -1259,14 +1259,18 @@ IMAGE_DESC = np.dtype({"names": ["offset", "H", "W", "flip", "sy", "sx", "pad"],
                        "offsets": [0, 8, 12, 16, 20, 24, 28], "itemsize": 32})
 
 
-def image_descs(shapes, flips, OH, OW):
+def image_descs(shapes, flips, OH, OW, frames=None):
     """Descriptors of uint8 [H,W,3] images packed back to back -> (IMAGE_DESC array, total pixel bytes). The scales
-    are float32(H / OH), float32(W / OW): the rounding of preprocessor.resize_bilinear_legacy."""
+    are float32(H / OH), float32(W / OW): the rounding of preprocessor.resize_bilinear_legacy. `frames`: the final
+    (height, width) of each image's augmentation program when it moves the frame (prepare_images_geo); the scales are
+    then those of the final frame, H and W stay the source size."""
     d = np.zeros(len(shapes), IMAGE_DESC)
     off = 0
     for i, ((H, W), f) in enumerate(zip(shapes, flips)):
         assert H >= 1 and W >= 1, (H, W)
-        d[i] = (off, H, W, int(bool(f)), np.float32(H / OH), np.float32(W / OW), 0)
+        FH, FW = (H, W) if frames is None else frames[i]
+        assert FH >= 1 and FW >= 1, (FH, FW)
+        d[i] = (off, H, W, int(bool(f)), np.float32(FH / OH), np.float32(FW / OW), 0)
         off += int(H) * int(W) * 3
     return d, off
 
@@ -1302,6 +1306,28 @@ def prepare_images_aug(pixels, desc, B, OH, OW, prog, params, P, max_H, out=None
     nbytes = int(lib().prepare_images_aug_workspace(B, int((codes == OP_CONTRAST).sum()), int(max_H)))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pixels.device) if nbytes else None
     lib().prepare_images_aug(ptr(pixels), ptr(desc), B, OH, OW, codes.ctypes.data, len(codes), ptr(params), P,
+                             int(max_H), ptr(ws), nbytes, ptr(_chk(out)), _stream())
+    return out
+
+
+def prepare_images_geo(pixels, desc, B, OH, OW, prog, params, P, max_H, out=None):
+    """prepare_images_aug for programs with OP_CROP / OP_PAD (mtlssl_prepare_images_geo) =
+    resize_bilinear_legacy(preprocessor.apply_program(image)) per image. desc: image_descs(..., frames=the final
+    frames); max_H >= the height of every stage's frame of every image (max over preprocessor.stage_frames): it sizes
+    the workspace of the mean slots (contrast ops and pads)."""
+    assert pixels.is_cuda and pixels.dtype == torch.uint8 and desc.is_cuda and desc.dtype == torch.uint8
+    assert desc.numel() >= B * IMAGE_DESC.itemsize and desc.data_ptr() % 8 == 0
+    assert params.is_cuda and params.data_ptr() % 4 == 0
+    assert params.numel() * params.element_size() >= B * P * 4, "params hold fewer than B x P floats"
+    from .preprocessor import OP_CONTRAST, OP_PAD
+    codes = np.ascontiguousarray(prog, np.int32).reshape(-1)
+    if out is None:
+        out = torch.empty((B, OH, OW, 3), dtype=f32, device=pixels.device)
+    assert tuple(out.shape) == (B, OH, OW, 3)
+    slots = int(((codes == OP_CONTRAST) | (codes == OP_PAD)).sum())
+    nbytes = int(lib().prepare_images_geo_workspace(B, slots, int(max_H)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pixels.device) if nbytes else None
+    lib().prepare_images_geo(ptr(pixels), ptr(desc), B, OH, OW, codes.ctypes.data, len(codes), ptr(params), P,
                              int(max_H), ptr(ws), nbytes, ptr(_chk(out)), _stream())
     return out
 

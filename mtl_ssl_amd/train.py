@@ -73,22 +73,41 @@ def record_paths(input_config):
     return paths
 
 
+def geometric_augmentation(augmentation_options, model_config, aux_labels):
+    """Whether the input path may run the options that move the frame (random_crop_image, random_pad_image,
+    random_crop_pad_image, ssd_random_crop): they deliver the image and the boxes in the new frame, so the window,
+    closeness and edge-mask labels must be made from those boxes (aux_labels="generate") or not be needed at all.
+    A config that lists such an option while a head reads its labels from the records is refused here."""
+    from . import preprocessor
+    mtl = model_config.mtl
+    heads = [h for h in ("window", "closeness", "edgemask") if getattr(mtl, h)]
+    ok = aux_labels == "generate" or not heads
+    listed = [k for k, _ in preprocessor._entries(augmentation_options or ()) if k in preprocessor.GEOMETRIC_KIND]
+    if listed and not ok:
+        raise ValueError("data augmentation %s moves the image and the boxes, but mtl.%s read%s the labels frozen into the "
+                         "records, which would stay in the old frame: train with --aux_labels=generate "
+                         "(aux_labels=\"generate\") to make them from the boxes at every step"
+                         % (", ".join(repr(k) for k in listed), " / mtl.".join(heads), "s" if len(heads) == 1 else ""))
+    return ok
+
+
 def record_batches(kind, paths, num_classes, batch_size, augmentation_options, rng, device, input_config,
-                   prefetch=10, **kw):
+                   prefetch=10, geometric=False, **kw):
     """The batches of input_reader.batches with `images` on `device`: 'async' = mtl_ssl_amd.input_pipeline
     (input_reader.proto num_readers decode workers, train.proto prefetch_queue_capacity batches ahead), 'host' = the
-    serial generator, images copied at hand-out."""
+    serial generator, images copied at hand-out. geometric: see geometric_augmentation."""
     from . import input_pipeline, input_reader
     if kind == "async":
         local = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
         workers = input_pipeline.default_num_workers(int(input_config.get("num_readers", 8) or 8), local)
         return input_pipeline.InputPipeline(paths, num_classes, batch_size, augmentation_options, rng, device=device,
-                                            num_workers=workers, prefetch=max(1, prefetch), **kw)
+                                            num_workers=workers, prefetch=max(1, prefetch), geometric=geometric, **kw)
     if kind != "host":
         raise ValueError("input pipeline %r: async or host" % kind)
 
     def gen():
-        for b in input_reader.batches(paths, num_classes, batch_size, augmentation_options, rng, **kw):
+        for b in input_reader.batches(paths, num_classes, batch_size, augmentation_options, rng, geometric=geometric,
+                                      **kw):
             b["images"] = b["images"].to(device, non_blocking=True)
             yield b
     return gen()
@@ -124,6 +143,10 @@ def main(argv=None):
         if B % world:                                # reference takes batch_size // num_clones images (trainer.py:270)
             raise SystemExit("train_config.batch_size %d does not divide over %d ranks" % (B, world))
         B //= world
+    try:
+        geometric = geometric_augmentation(train_config.data_augmentation_options, model_config, f.aux_labels)
+    except ValueError as e:
+        raise SystemExit(str(e))
     probe = model_builder.build(model_config, True, dev, seed=f.seed)
     rz = model_config.faster_rcnn.image_resizer
     stream = record_batches(f.input_pipeline, record_paths(input_config), K, B, train_config.data_augmentation_options,
@@ -134,7 +157,7 @@ def main(argv=None):
                             if input_config.get("shuffle", True) else 0,
                             resized_shape=lambda h, w: probe.resized_shape(h, w, rz),
                             max_pending=64 if world == 1 else 256,
-                            prefetch=int(train_config.prefetch_queue_capacity))
+                            prefetch=int(train_config.prefetch_queue_capacity), geometric=geometric)
 
     def next_batch():
         return next(stream)
