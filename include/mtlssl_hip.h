@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 13
+#define MTLSSL_ABI_VERSION 14
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -772,6 +772,19 @@ int mtlssl_comm_destroy(mtlssl_comm_t comm);
  * clones' gradients summed on the CPU; here RCCL's kernels share the GPU with the step). tools/cu_thief_probe.py. */
 int mtlssl_debug_cu_thief(int workgroups, int threads, int lds_bytes, int64_t microseconds, float* sink,
                           mtlssl_stream_t stream);
+
+/* ------------------------------------------------------------------ evaluation-time visualisation
+ * Replaces the rectangle part of utils/visualization_utils.py draw_bounding_box_on_image (PIL ImageDraw.line around
+ * the box) as eval_util.py:553-672 visualize_detection_results calls it for the first eval_config.num_visualizations
+ * images (evaluator.py:289-310): groundtruth boxes underneath, then the detections. Label text stays on the host.
+ *   image [height, width, 3] uint8 on the device, rows row_stride BYTES apart (>= 3 * width), painted in place;
+ *   boxes [n,4] int32 absolute pixels (ymin, xmin, ymax, xmax), half open: box i covers rows [ymin, ymax) and columns
+ *   [xmin, xmax); colors [n,3] uint8 RGB. The outline of box i = its pixels that are NOT inside
+ *   [ymin+thickness, ymax-thickness) x [xmin+thickness, xmax-thickness). Boxes are painted in input order (where
+ *   outlines overlap the LAST box wins), clipped to the image; a box with ymax <= ymin or xmax <= xmin paints nothing;
+ *   pixels that no outline covers are not written. thickness >= 1. */
+int mtlssl_draw_boxes(uint8_t* image, int height, int width, int64_t row_stride, const int32_t* boxes,
+                      const uint8_t* colors, int n, int thickness, mtlssl_stream_t stream);
 
 /* CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start): the checksum of the reference's
  * data containers — TFRecord framing (tensorflow/core/lib/io/record_writer.cc; the create_records scripts write them,

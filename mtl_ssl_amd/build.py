@@ -25,6 +25,7 @@ SOURCES = {
     "depthwise.hip": [], "pool_concat.hip": [], "winograd.hip": [],
     "eval_metrics.hip": ["-ffp-contract=off"],   # evaluator NMS / edge-mask metric: numpy's double arithmetic
     "aux_labels.hip": ["-ffp-contract=off"],     # labels from boxes: the host definitions' double arithmetic
+    "visualize.hip": [],                # box overlay of the evaluator's visualisations (integer work only)
     "comm.hip": [],                     # RCCL wrappers (host code only; RCCL itself is bound with dlopen)
 }
 
@@ -41,16 +42,23 @@ def _digest(path, flags):
 
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
-    jobs = []
+    jobs, digests = [], []
     for src, extra in SOURCES.items():
         path = os.path.join(CSRC, src)
         obj = os.path.join(OBJ, src + ".o")
         stamp = obj + ".sha"
         dig = _digest(path, COMMON + extra)
+        digests.append(dig)
         if (not force and os.path.exists(obj) and os.path.exists(stamp)
                 and open(stamp).read() == dig):
             continue
         jobs.append((path, obj, stamp, dig, extra))
+    # the library records the digests it was linked from: a tree that carries the library without its object files
+    # (a copy of a built tree) is up to date when they still match, and is not compiled again
+    link_stamp = os.path.join(OBJ, "link.sha")
+    link_dig = hashlib.sha256("\n".join(digests).encode()).hexdigest()
+    if not force and os.path.exists(OUT) and os.path.exists(link_stamp) and open(link_stamp).read() == link_dig:
+        return OUT
 
     def run(job):
         path, obj, stamp, dig, extra = job
@@ -69,6 +77,8 @@ def build(force=False, verbose=True):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
+    with open(link_stamp, "w") as f:
+        f.write(link_dig)
     return OUT
 
 

@@ -6,6 +6,11 @@ With mtl.window / closeness / edgemask the model also gets the record's groundtr
 mtl/window_map, mtl/closeness_diff and mtl/edgemask_ap (mtl_metrics.py); eval_config.nms_type / nms_threshold /
 soft_nms_sigma re-suppress each class's detections on the device before the evaluator sees them
 (utils/per_image_evaluation.py:35-68, 258).
+eval_config.calc_loss adds the model's losses (Loss/<name>, FasterRCNNMetaArch.eval_loss on the device);
+submission_format_output writes the test servers' files instead of metrics; a metrics run with --eval_dir keeps the
+best state under <eval_dir>/best/ (main_subset); --run_once=false evaluates every new state of --checkpoint_dir
+(eval_interval_secs, max_evals) with the model built once; num_visualizations / visualization_export_dir export
+annotated images (mtl_ssl_amd/eval_workflow.py).
 
     python -m mtl_ssl_amd.eval --checkpoint_dir=/runs/a --eval_dir=/runs/a/eval --pipeline_config_path=..."""
 import argparse
@@ -73,13 +78,51 @@ def suppress_per_class(boxes, scores, classes, scale, num_classes, nms_type, nms
     return bd[keep], np.concatenate(kept_scores), classes[keep]
 
 
+def _raw_records(paths):
+    """(source id or file name, encoded image bytes) of every record, in the order the input pipeline delivers them
+    (shuffle off, one image per batch): the decoded image and its size, which the resized batch no longer has — the
+    submission files and the visualisations are in the frame of the original image (evaluator.py:143, 156-159)."""
+    from . import input_reader
+    for p in paths:
+        for rec in input_reader.read_tfrecord(p):
+            f = input_reader.parse_example(rec)
+            sid = (f.get("image/source_id") or [b""])[0].decode("utf-8")
+            name = (f.get("image/filename") or [b""])[0].decode("utf-8")
+            yield sid, name, f.get("image/encoded", [b""])[0]
+
+
+def _download(post, losses):
+    """Host copies of one image's postprocess outputs and loss scalars. With losses everything travels in ONE device
+    buffer and one copy (float32: the class ids and the count are small integers, exact in it); without, the outputs
+    are copied one by one as before."""
+    import torch
+    if not losses:
+        return {k: v.cpu().numpy() for k, v in post.items()}, {}
+    keys, names = list(post), list(losses)
+    flat = torch.cat([post[k].reshape(-1).to(torch.float32) for k in keys]
+                     + [losses[n].reshape(-1) for n in names]).cpu().numpy()
+    d, off = {}, 0
+    for k in keys:
+        n = post[k].numel()
+        dtype = torch.empty(0, dtype=post[k].dtype).numpy().dtype
+        d[k] = flat[off:off + n].astype(dtype).reshape(tuple(post[k].shape))
+        off += n
+    vals = {n: float(flat[off + i]) for i, n in enumerate(names)}
+    for n, v in vals.items():
+        if not np.isfinite(v):                  # evaluator.py:214-216 tf.check_numerics on every term
+            raise FloatingPointError("%s is inf or nan." % n)
+    return d, vals
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint_dir", required=True)
     ap.add_argument("--eval_dir", default="")
     ap.add_argument("--pipeline_config_path", required=True)
     ap.add_argument("--eval_training_data", default="false")
-    ap.add_argument("--run_once", default="true")
+    ap.add_argument("--run_once", default="true",
+                    help="false: keep evaluating every new state of --checkpoint_dir (eval_config.eval_interval_secs, "
+                         "max_evals)")
     ap.add_argument("--logtostderr", action="store_true")
     ap.add_argument("--input_pipeline", choices=("async", "host"), default="async",
                     help="async: decode workers + on-device resize (mtl_ssl_amd.input_pipeline); host: the serial "
@@ -88,7 +131,7 @@ def main(argv=None):
     import torch
     import __graft_entry__ as ge
     ge.build()
-    from . import checkpoint, config, evaluation, model_builder, mtl_metrics, ops
+    from . import checkpoint, config, eval_workflow, evaluation, model_builder, mtl_metrics, ops
     from .train import record_batches, record_paths
     cfg = config.parse_pipeline_config(open(f.pipeline_config_path).read())
     ec = cfg.get("eval_config", config.Msg("EvalConfig"))
@@ -96,122 +139,208 @@ def main(argv=None):
     reader = cfg.get("train_input_reader" if use_train else "eval_input_reader", config.Msg())
     K = int(cfg.model.faster_rcnn.num_classes)
     dev = torch.device("cuda", 0)
-    model = model_builder.build(cfg.model, False, dev, seed=0)
-    state = os.path.join(f.checkpoint_dir, "model.ckpt.npz")
-    step = checkpoint.load(state, model.ps)
-    if bool(ec.get("use_moving_averages", False)):
-        # evaluator.py:330-333: restore variable_averages.variables_to_restore(), i.e. every variable from its
-        # `<name>/ExponentialMovingAverage` shadow when the training run kept one
-        n_ema = checkpoint.load_moving_averages(state, model.ps)
-        if n_ema == 0:
-            raise ValueError(checkpoint.NO_MOVING_AVERAGES % state)
-    model.prepare()
-    coco = "coco" in str(ec.get("metrics_set", "pascal_voc_metrics"))
+    model = model_builder.build(cfg.model, False, dev, seed=0)       # built once; every evaluation restores values
+    metrics_set = ec.get("metrics_set", "pascal_voc_metrics")
+    if isinstance(metrics_set, (list, tuple)):          # the config parser hands a field that may repeat over as a list
+        if len(metrics_set) != 1:
+            raise ValueError("eval_config.metrics_set: one metric set expected, got %r" % (list(metrics_set),))
+        metrics_set = metrics_set[0]
+    metrics_set = str(metrics_set)
+    coco = "coco" in metrics_set
     limit = int(ec.get("num_examples", 5000))
     rz = cfg.model.faster_rcnn.image_resizer
     nms_type, nms_thr, sigma, iou_thr = eval_nms_options(ec)
-    # evaluator.py:318-322: iou_threshold is PASCAL's matching threshold; COCO keeps its .50:.05:.95
-    ev = evaluation.CocoDetectionEvaluator(K) if coco else evaluation.PascalDetectionEvaluator(K, iou_thr)
     # object_detection_evaluation.py:45-59 / :294-305: per-class caps of the evaluator's NMS
     eval_nms = None if (nms_type == "standard" and nms_thr == 1.0) else (256 if coco else 10000)
     mtl = cfg.model.get("mtl")
     use = {k: mtl is not None and bool(mtl.get(k, False)) for k in ("window", "closeness", "edgemask", "refine")}
-    mm = mtl_metrics.MtlMetrics()
-    missing = {}
-    em_counts = []
-    closeness_error = None
-    n_img = 0
-    stream = record_batches(f.input_pipeline, record_paths(reader), K, 1, (), None, dev, reader,
-                            resized_shape=lambda h, w: model.resized_shape(h, w, rz))
-    for b in stream:
-        if n_img >= limit:
-            break
-        # evaluator.py:123-148: predict -> predict_with_window (the record's groundtruth windows) -> predict_edgemask
-        # -> refine -> postprocess; the auxiliary outputs are copied on the device at once (later passes reuse buffers)
-        pd = model.predict(model.preprocess(b["images"].to(dev)))
-        win = clo = em = None
-        if use["window"]:
-            if b.get("window_boxes") is None:
-                missing["mtl/window_map"] = "window boxes / labels (image/window/...)"
-            elif len(b["window_boxes"][0]):
-                wb = torch.from_numpy(np.ascontiguousarray(b["window_boxes"][0], np.float32)).to(dev).view(1, -1, 4)
-                win = model.predict_with_window(pd, wb)["window_class_predictions"].clone()
+    calc_loss = bool(ec.get("calc_loss", False))
+    submission = bool(ec.get("submission_format_output", False))
+    vis_dir = str(ec.get("visualization_export_dir", "") or "")
+    n_vis = int(ec.get("num_visualizations", 10)) if vis_dir else 0
+    cats = eval_workflow.categories(K, str(reader.get("label_map_path", "") or "")) if (submission or n_vis) else None
+    if submission and not f.eval_dir:
+        raise ValueError("eval_config.submission_format_output writes <eval_dir>/detection_results/: give --eval_dir")
+
+    def evaluate_state(fh):
+        """One evaluation of the state in the open file fh (eval_util.run_checkpoint_once)."""
+        step = checkpoint.load(fh, model.ps)
+        if bool(ec.get("use_moving_averages", False)):
+            # evaluator.py:330-333: restore variable_averages.variables_to_restore(), i.e. every variable from its
+            # `<name>/ExponentialMovingAverage` shadow when the training run kept one
+            fh.seek(0)
+            n_ema = checkpoint.load_moving_averages(fh, model.ps)
+            if n_ema == 0:
+                raise ValueError(checkpoint.NO_MOVING_AVERAGES % fh.name)
+        model.prepare()
+        # evaluator.py:318-322: iou_threshold is PASCAL's matching threshold; COCO keeps its .50:.05:.95
+        ev = evaluation.CocoDetectionEvaluator(K) if coco else evaluation.PascalDetectionEvaluator(K, iou_thr)
+        mm = mtl_metrics.MtlMetrics()
+        missing = {}
+        em_counts = []
+        closeness_error = None
+        loss_sums = {}
+        results = []
+        n_img = 0
+        raw = _raw_records(record_paths(reader)) if (submission or n_vis) else None
+        stream = record_batches(f.input_pipeline, record_paths(reader), K, 1, (), None, dev, reader,
+                                resized_shape=lambda h, w: model.resized_shape(h, w, rz))
+        for b in stream:
+            if n_img >= limit:
+                break
+            metrics = not submission
+            if calc_loss and metrics:
+                # evaluator.py:123-141: calc_loss hands the groundtruth to the is_training=False model
+                for key, field, on in (("groundtruth_closeness", "image/object/closeness/text", use["closeness"]),
+                                       ("window_boxes", "image/window/...", use["window"]),
+                                       ("groundtruth_edgemask", "image/edgemask/masks", use["edgemask"])):
+                    if on and b.get(key) is None:
+                        raise ValueError("eval_config.calc_loss: the records lack %s, which the loss of this model "
+                                         "reads" % field)
+                model.provide_groundtruth(b["groundtruth_boxes"], b["groundtruth_classes"],
+                                          b["groundtruth_closeness"] if use["closeness"] else None)
+                if use["window"]:
+                    model.provide_window(b["window_boxes"], b["window_classes"])
+                if use["edgemask"]:
+                    model.provide_edgemask(b["groundtruth_edgemask"])
+            # evaluator.py:123-148: predict -> predict_with_window (the record's groundtruth windows) ->
+            # predict_edgemask -> refine -> postprocess; the auxiliary outputs are copied on the device at once (later
+            # passes reuse buffers)
+            pd = model.predict(model.preprocess(b["images"].to(dev)))
+            win = clo = em = None
+            if use["window"] and metrics:
+                if b.get("window_boxes") is None:
+                    missing["mtl/window_map"] = "window boxes / labels (image/window/...)"
+                elif len(b["window_boxes"][0]):
+                    wb = torch.from_numpy(np.ascontiguousarray(b["window_boxes"][0], np.float32)).to(dev).view(1, -1, 4)
+                    win = model.predict_with_window(pd, wb)["window_class_predictions"].clone()
+                else:
+                    mm.add_window(np.zeros((0, K + 1), np.float32), np.zeros((0, K + 1), np.float32))
+            if use["closeness"] and closeness_error is None and metrics:
+                if b.get("groundtruth_closeness") is None:
+                    missing["mtl/closeness_diff"] = "groundtruth closeness (image/object/closeness/text)"
+                else:
+                    clo = pd["closeness_predictions"].clone()
+            if use["edgemask"] and metrics:
+                model.predict_edgemask(pd)
+                if b.get("groundtruth_edgemask") is None:
+                    missing["mtl/edgemask_ap"] = "groundtruth edge mask (image/edgemask/masks)"
+                else:
+                    gt_em = b["groundtruth_edgemask"][0]
+                    gt0 = torch.from_numpy(np.ascontiguousarray(gt_em[0], np.float32)).to(dev)
+                    em = ops.edgemask_agreement(pd["edgemask_predictions"][0].contiguous(), gt0)
+                    em_counts.append((em, gt_em.shape[1], gt_em.shape[2]))
+            if use["refine"]:
+                pd = model.predict_with_mtl_results(pd)
+            post = model.postprocess(pd)
+            # evaluator.py:211-216: model.loss(prediction_dict) of this image, seeded by its index; the scalars come
+            # back with the detections
+            losses = model.eval_loss(pd, image_index=n_img) if (calc_loss and metrics) else None
+            d, loss_vals = _download(post, losses)
+            model.check_device_flags()             # e.g. the refiner's window de-duplication ran out of slots (NaN boxes)
+            for k, v in loss_vals.items():
+                loss_sums.setdefault(k, []).append(v)
+            n = int(d["num_detections"][0])
+            H, W = b["images"].shape[1:3]
+            if raw is not None:
+                sid, name, encoded = next(raw)
+                if b.get("source_id") is not None and b["source_id"][0] != sid:
+                    raise RuntimeError("record %d: the input pipeline delivered %r, the record file holds %r"
+                                       % (n_img, b["source_id"][0], sid))
+                image_id = sid or name
+                if submission or n_img < n_vis:
+                    from .inference import decode_image
+                    original = decode_image(encoded)
+                    # box_list_ops.to_absolute_coordinates in the original image's frame (evaluator.py:156-159), float32
+                    ohw = np.asarray(original.shape[:2] * 2, np.float32)
+                    abs_boxes = np.asarray(d["detection_boxes"][0][:n], np.float32) * ohw
+                    classes1 = np.asarray(d["detection_classes"][0][:n]).astype(np.int64) + 1    # label_id_offset
+                    scores = np.asarray(d["detection_scores"][0][:n], np.float32)
+                    if submission:
+                        results.append((image_id, abs_boxes, scores, classes1))
+                    if n_img < n_vis:
+                        gtb = np.asarray(b["groundtruth_boxes"][0], np.float32).reshape(-1, 4) * ohw
+                        eval_workflow.visualize_detection_results(original, image_id, abs_boxes, scores, classes1, gtb,
+                                                                  cats, vis_dir, dev)
+            if not metrics:
+                n_img += 1
+                continue
+            if win is not None:
+                mm.add_window(win.cpu().numpy(), b["window_classes"][0])
+            if clo is not None and closeness_error is None:
+                # the reference's absolute fp32 boxes (box_list_ops.scale / to_absolute_coordinates), all padded slots
+                hw = np.asarray([H, W, H, W], np.float32)
+                try:
+                    mm.add_closeness(clo.cpu().numpy(), b["groundtruth_closeness"][0],
+                                     np.asarray(b["groundtruth_boxes"][0], np.float32).reshape(-1, 4) * hw,
+                                     np.asarray(d["detection_boxes"][0], np.float32) * hw)
+                except ValueError as e:        # the reference stops with an IndexError; the other metrics stay valid
+                    closeness_error = str(e)
+            # evaluator.py:137-150 hands the COCO evaluator absolute boxes, the PASCAL one either (IoU is scale-free)
+            scale = np.asarray([H, W, H, W], np.float64) if coco else 1.0
+            gt_boxes = np.asarray(b["groundtruth_boxes"][0], np.float64).reshape(-1, 4) * scale
+            gt_cls = np.asarray(b["groundtruth_classes"][0]).argmax(1)
+            if coco:
+                ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls)
+            else:     # evaluator.py:196-201 -> eval_util.py:332-334: PASCAL's difficult boxes are ignored, not missed
+                diff = b.get("groundtruth_difficult")
+                ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls,
+                                                      is_difficult=None if diff is None else np.asarray(diff[0], bool))
+            if eval_nms is None:
+                ev.add_single_detected_image_info(n_img, np.asarray(d["detection_boxes"][0][:n], np.float64) * scale,
+                                                  d["detection_scores"][0][:n], d["detection_classes"][0][:n])
             else:
-                mm.add_window(np.zeros((0, K + 1), np.float32), np.zeros((0, K + 1), np.float32))
-        if use["closeness"] and closeness_error is None:
-            if b.get("groundtruth_closeness") is None:
-                missing["mtl/closeness_diff"] = "groundtruth closeness (image/object/closeness/text)"
-            else:
-                clo = pd["closeness_predictions"].clone()
-        if use["edgemask"]:
-            model.predict_edgemask(pd)
-            if b.get("groundtruth_edgemask") is None:
-                missing["mtl/edgemask_ap"] = "groundtruth edge mask (image/edgemask/masks)"
-            else:
-                gt_em = b["groundtruth_edgemask"][0]
-                gt0 = torch.from_numpy(np.ascontiguousarray(gt_em[0], np.float32)).to(dev)
-                em = ops.edgemask_agreement(pd["edgemask_predictions"][0].contiguous(), gt0)
-                em_counts.append((em, gt_em.shape[1], gt_em.shape[2]))
-        if use["refine"]:
-            pd = model.predict_with_mtl_results(pd)
-        d = {k: v.cpu().numpy() for k, v in model.postprocess(pd).items()}
-        model.check_device_flags()             # e.g. the refiner's window de-duplication ran out of slots (NaN boxes)
-        n = int(d["num_detections"][0])
-        H, W = b["images"].shape[1:3]
-        if win is not None:
-            mm.add_window(win.cpu().numpy(), b["window_classes"][0])
-        if clo is not None and closeness_error is None:
-            # the reference's absolute fp32 boxes (box_list_ops.scale / to_absolute_coordinates), all padded slots
-            hw = np.asarray([H, W, H, W], np.float32)
-            try:
-                mm.add_closeness(clo.cpu().numpy(), b["groundtruth_closeness"][0],
-                                 np.asarray(b["groundtruth_boxes"][0], np.float32).reshape(-1, 4) * hw,
-                                 np.asarray(d["detection_boxes"][0], np.float32) * hw)
-            except ValueError as e:        # the reference stops with an IndexError; the other metrics stay valid
-                closeness_error = str(e)
-        # evaluator.py:137-150 hands the COCO evaluator absolute boxes, the PASCAL one either (IoU is scale-free)
-        scale = np.asarray([H, W, H, W], np.float64) if coco else 1.0
-        gt_boxes = np.asarray(b["groundtruth_boxes"][0], np.float64).reshape(-1, 4) * scale
-        gt_cls = np.asarray(b["groundtruth_classes"][0]).argmax(1)
-        if coco:
-            ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls)
-        else:     # evaluator.py:196-201 -> eval_util.py:332-334: PASCAL's difficult boxes are ignored, not missed
-            diff = b.get("groundtruth_difficult")
-            ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls,
-                                                  is_difficult=None if diff is None else np.asarray(diff[0], bool))
-        if eval_nms is None:
-            ev.add_single_detected_image_info(n_img, np.asarray(d["detection_boxes"][0][:n], np.float64) * scale,
-                                              d["detection_scores"][0][:n], d["detection_classes"][0][:n])
-        else:
-            ev.add_single_detected_image_info(n_img, *suppress_per_class(
-                d["detection_boxes"][0][:n], d["detection_scores"][0][:n], d["detection_classes"][0][:n], scale, K,
-                nms_type, nms_thr, sigma, eval_nms, dev))
-        n_img += 1
-    if hasattr(stream, "close"):
-        stream.close()
-    if em_counts:
-        counts = torch.cat([c for c, _, _ in em_counts]).cpu().numpy()
-        for c, (_, h, w) in zip(counts, em_counts):
-            mm.add_edgemask(int(c), h, w)
-    res = ev.evaluate()
-    out = {"global_step": int(step), "num_images": n_img}
-    for k, v in res.items():
-        if k not in ("precisions", "recalls"):           # the per-class curves stay in the evaluator
-            out[k] = _plain(v)
-    mres = mm.evaluate()
-    if closeness_error is not None:
-        mres.pop("mtl/closeness_diff", None)
-        warnings.warn("mtl/closeness_diff left out: " + closeness_error)
-    for key, field in sorted(missing.items()):
-        if key not in mres:
-            warnings.warn("%s left out: no evaluated record carries the %s it needs" % (key, field))
-    out.update(mres)
-    print(json.dumps(out))
-    if f.eval_dir:
-        os.makedirs(f.eval_dir, exist_ok=True)
-        with open(os.path.join(f.eval_dir, "metrics-%d.json" % step), "w") as fh:
-            json.dump(out, fh)
-    return out
+                ev.add_single_detected_image_info(n_img, *suppress_per_class(
+                    d["detection_boxes"][0][:n], d["detection_scores"][0][:n], d["detection_classes"][0][:n], scale, K,
+                    nms_type, nms_thr, sigma, eval_nms, dev))
+            n_img += 1
+        if hasattr(stream, "close"):
+            stream.close()
+        if raw is not None:
+            raw.close()
+        if submission:
+            # eval_util.py:783-786, 838-841: no metrics, only the files of the test servers
+            paths = eval_workflow.save_detection_results_for_submission(results, cats, f.eval_dir, metrics_set)
+            print(json.dumps({"global_step": int(step), "num_images": n_img, "submission_files": paths}))
+            return {"global_step": int(step), "num_images": n_img, "submission_files": paths,
+                    "detections": [dict(image_id=r[0], boxes=r[1], scores=r[2], classes=r[3]) for r in results]}
+        if em_counts:
+            counts = torch.cat([c for c, _, _ in em_counts]).cpu().numpy()
+            for c, (_, h, w) in zip(counts, em_counts):
+                mm.add_edgemask(int(c), h, w)
+        res = ev.evaluate()
+        out = {"global_step": int(step), "num_images": n_img}
+        for k, v in res.items():
+            if k not in ("precisions", "recalls"):           # the per-class curves stay in the evaluator
+                out[k] = _plain(v)
+        mres = mm.evaluate()
+        if closeness_error is not None:
+            mres.pop("mtl/closeness_diff", None)
+            warnings.warn("mtl/closeness_diff left out: " + closeness_error)
+        for key, field in sorted(missing.items()):
+            if key not in mres:
+                warnings.warn("%s left out: no evaluated record carries the %s it needs" % (key, field))
+        out.update(mres)
+        for k, v in loss_sums.items():                       # eval_util.py:877-882 aggregated_loss: the mean over the images
+            out["Loss/" + k] = float(np.mean(v))
+        print(json.dumps(out), flush=True)
+        if f.eval_dir:
+            os.makedirs(f.eval_dir, exist_ok=True)
+            with open(os.path.join(f.eval_dir, "metrics-%d.json" % step), "w") as fh_out:
+                json.dump(out, fh_out)
+            # eval_util.py:869-870, 934-997
+            eval_workflow.save_best_ckpt(out, fh.name, step, f.eval_dir, metrics_set, str(ec.get("main_subset", "") or ""),
+                                         source=fh)
+        return out
+
+    if str(f.run_once).lower() in ("1", "true"):
+        with open(os.path.join(f.checkpoint_dir, eval_workflow.STATE_NAME), "rb") as fh:
+            return evaluate_state(fh)
+    # evaluator.py:335-350 -> eval_util.repeated_checkpoint_run
+    done = eval_workflow.repeated_checkpoint_run(
+        f.checkpoint_dir, evaluate_state, float(ec.get("eval_interval_secs", 120)),
+        eval_workflow.max_number_of_evaluations(ec), log=lambda msg: print(msg, file=sys.stderr, flush=True))
+    return done[-1]
 
 
 if __name__ == "__main__":

@@ -887,6 +887,104 @@ class FasterRCNNMetaArch:
         pd["_d"] = d
         return losses
 
+    # ------------------------------------------------------------------ loss of an inference model (eval_config.calc_loss)
+    def eval_loss(self, pd, image_index=0):
+        """model.loss(prediction_dict) of an is_training=False model, the way the evaluator calls it with calc_loss
+        (evaluator.py:123-141, 211-216) after provide_groundtruth / provide_window / provide_edgemask: the forward half
+        of loss() — the same loss_dict keys, no gradient buffer is allocated and pd gets no '_d'.
+
+        What evaluation mode changes (faster_rcnn_meta_arch.py):
+        * the anchors are clipped, none is pruned (:583-585), and _loss_rpn (:1591-1668) assigns and draws its
+          minibatch over all of them. The draw is seeded by `image_index` where training uses the step, so a rerun
+          gives the same numbers;
+        * _postprocess_rpn samples no second-stage minibatch (:1117-1132): _loss_box_classifier (:1670-1793) and
+          _loss_refined_classifier (:1795-1837) assign targets to all first_stage_max_proposals padded proposals, mask
+          the padding rows by num_proposals (:1715-1716, 1754-1757) and normalise by max(num_proposals, 1) * batch
+          (:1722-1725) — mtlssl_detector_loss_scales reads the count on the device;
+        * the closeness term (:1774-1791) is normalised by the matched proposals and is NOT masked by the padding
+          indicator; padding rows are zero boxes, match nothing and carry regression weight 0;
+        * the window term (:1839-1858) is 0 for an image without windows (tf.cond on the empty stack), the edge-mask
+          term (:1860-1881) is as in training.
+        A configured hard_example_miner is refused: its mining step zeroes gradient rows this path does not have."""
+        if self._is_training:
+            raise ValueError("eval_loss is the loss of an inference model; a training model calls loss()")
+        if self._hard_miner is not None:
+            raise ValueError("eval_config.calc_loss with a hard_example_miner is not supported")
+        c, mtl = self.cfg, self._mtl
+        B, H, W, _ = pd["image_shape"]
+        gt = self._format_groundtruth_data(H, W)
+        dev = self.ps.device
+        losses = {}
+        K, K1 = self.num_classes, self.num_classes + 1
+        if "um" not in self._consts:
+            self._consts["um"] = torch.zeros((1,), dtype=f32, device=dev)
+            self._consts["um2"] = torch.tensor([1.0] + [0.0] * (K1 - 1), dtype=f32, device=dev)
+        # ---- _loss_rpn :1591-1668
+        anchors = pd["anchors"]
+        n = anchors.shape[0]
+        tg = ops.assign_targets(anchors, gt["boxes_abs"], gt["num"], None, self._consts["um"], 0.7, 0.3, True)
+        cls_t = tg["cls_targets"].view(B, n)
+        sampled = ops.balanced_sample(tg["cls_weights"], cls_t, int(c.first_stage_minibatch_size),
+                                      c.first_stage_positive_balance_fraction, self.seed,
+                                      (2 * int(image_index) * 65536) & 0xFFFFFFFF, 2)
+        loc_s, obj_s = ops.rpn_loss_scales(sampled, tg["reg_weights"], c.first_stage_localization_loss_weight / B,
+                                           c.first_stage_objectness_loss_weight / B)
+        rl, _ = ops.smooth_l1(pd["rpn_box_encodings"], tg["reg_targets"], loc_s, 3.0, want_grad=False)
+        losses["first_stage_localization_loss"] = ops.reduce_sum(rl)
+        rl, _ = ops.softmax_ce(pd["rpn_objectness_predictions_with_background"], ops.onehot2(cls_t), obj_s,
+                               want_grad=False)
+        losses["first_stage_objectness_loss"] = ops.reduce_sum(rl)
+        pd["_rpn_targets"] = dict(tg, sampled=sampled)
+        if not self._first_stage_only:
+            # ---- _loss_box_classifier :1670-1793 over every padded proposal
+            N2 = self.max_num_proposals
+            dt = ops.assign_targets(pd["proposal_boxes"], gt["boxes_abs"], gt["num"], gt["classes_bg"],
+                                    self._consts["um2"], 0.5, 0.5, False,
+                                    gt_extra=gt["closeness"] if mtl.closeness else None)
+            cls_s, loc_s2, clo_s = ops.detector_loss_scales(
+                dt["cls_weights"], dt["reg_weights"], pd["num_proposals"],
+                dt.get("extra_targets") if mtl.closeness else None,
+                c.second_stage_classification_loss_weight, c.second_stage_localization_loss_weight,
+                mtl.closeness_loss_weight)
+            cls_targets = dt["cls_targets"].view(B * N2, K1)
+            rl, _ = ops.box_select_smooth_l1(pd["refined_box_encodings"], cls_targets,
+                                             dt["reg_targets"].view(B * N2, 4), loc_s2.view(-1), 1.0, want_grad=False)
+            losses["second_stage_localization_loss"] = ops.reduce_sum(rl)
+            rl, _ = ops.softmax_ce(pd["class_predictions_with_background"], cls_targets, cls_s.view(-1),
+                                   want_grad=False)
+            losses["second_stage_classification_loss"] = ops.reduce_sum(rl)
+            pd["_det_targets"] = dt
+            if mtl.closeness:
+                rl, _ = ops.softmax_ce(pd["closeness_predictions"], dt["extra_targets"].view(B * N2, K1),
+                                       clo_s.view(-1), col0=1, want_grad=False)
+                losses["closeness_classification_loss"] = ops.reduce_sum(rl)
+            # ---- _loss_window_class :1839-1858
+            if mtl.window:
+                wc = self._window["classes"].view(-1, K1)
+                if wc.shape[0]:
+                    ws = torch.full((wc.shape[0],), mtl.window_class_loss_weight / wc.shape[0], dtype=f32, device=dev)
+                    rl, _ = ops.softmax_ce(pd["window_class_predictions"], wc, ws, want_grad=False)
+                    losses["window_class_loss"] = ops.reduce_sum(rl)
+                else:
+                    losses["window_class_loss"] = torch.zeros((1,), dtype=f32, device=dev)
+        # ---- _loss_edgemask :1860-1881
+        if mtl.edgemask:
+            em = self._edgemask
+            mh, mw = em.shape[2], em.shape[3]
+            tgt, sc = ops.edgemask_targets(em, mtl.edgemask_loss_weight / (B * mh * mw))
+            pr = ops.resize_bilinear_fwd(pd["edgemask_predictions"], mh, mw)
+            rl, _ = ops.softmax_ce(pr, tgt, sc.view(-1), want_grad=False)
+            losses["edgemask_loss"] = ops.reduce_sum(rl)
+        # ---- _loss_refined_classifier :1795-1837
+        if mtl.refine and not self._first_stage_only:
+            rs = cls_s if c.second_stage_classification_loss_weight == mtl.refined_classification_loss_weight \
+                else ops.detector_loss_scales(dt["cls_weights"], dt["reg_weights"], pd["num_proposals"], None,
+                                              mtl.refined_classification_loss_weight, 0.0, 0.0)[0]
+            rl, _ = ops.softmax_ce(pd["mtl_refined_class_predictions_with_background"], cls_targets, rs.view(-1),
+                                   want_grad=False)
+            losses["refined_classification_loss"] = ops.reduce_sum(rl)
+        return losses
+
     # ------------------------------------------------------------------ backward
     def backward(self, pd):
         """Accumulates dLoss/dW into the flat gradient buffer (ParamStore.grads)."""

@@ -1029,6 +1029,21 @@ def edgemask_agreement(logits, gt_mask):
     return out
 
 
+def draw_boxes(image, boxes, colors, thickness):
+    """mtlssl_draw_boxes: paints the outlines of boxes [n,4] int32 (ymin, xmin, ymax, xmax absolute, half open) in
+    colors [n,3] uint8 into image, a uint8 [H,W,3] device tensor whose rows may be strided (a column slice of a wider
+    image), in place and in input order: the last box wins where outlines overlap. Returns image."""
+    assert image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3, \
+        (image.device, image.dtype, tuple(image.shape))
+    H, W = int(image.shape[0]), int(image.shape[1])
+    assert (image.stride(2) == 1 and image.stride(1) == 3 and image.stride(0) >= 3 * W) or not H * W, image.stride()
+    n = int(boxes.shape[0])
+    assert tuple(boxes.shape) == (n, 4) and tuple(colors.shape) == (n, 3), (boxes.shape, colors.shape)
+    lib().draw_boxes(ptr(image), H, W, int(image.stride(0)) if H * W else 3 * W, ptr(_chk(boxes, i32)),
+                     ptr(_chk(colors, torch.uint8)), n, int(thickness), _stream())
+    return image
+
+
 AUX_MAX_GT = 256                     # MTLSSL_AUX_MAX_GT: the label kernels hold one image's boxes in LDS
 AUX_WINDOW_ATTEMPTS = 100            # MTLSSL_AUX_WINDOW_ATTEMPTS (labels.WINDOW_ATTEMPTS)
 

@@ -5,7 +5,8 @@ R-FCN differs from Faster R-CNN only in the second stage: block4 runs ONCE on th
 map per head scope (not per ROI crop); a 1x1 `reduce_depth` conv and 1x1 score-map convs follow,
 and per-proposal predictions come from position-sensitive ROI pooling of the score maps
 (`mtlssl_psroi_fwd/bwd`). The aux heads (closeness / window) are R-FCN predictors too.
-RPN, target assignment, sampling and every loss are inherited from FasterRCNNMetaArch.
+RPN, target assignment, sampling and every loss are inherited from FasterRCNNMetaArch — loss() and the
+evaluator's eval_loss() (rfcn_meta_arch.py defines no loss of its own either).
 """
 import torch
 
