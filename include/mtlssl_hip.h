@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 14
+#define MTLSSL_ABI_VERSION 15
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -206,6 +206,29 @@ int mtlssl_conv2d_set_fp32_engine(int mode);
  * splits off a K-split tail launch) — lets a profiler relate per-call timings to
  * per-dispatch kernel traces. */
 int mtlssl_conv2d_num_dispatches(const mtlssl_conv_desc* d, int mode);
+/* Read-only report of what a call of (d, mode) will launch, from the same memoised planners the launch functions ask
+ * (a workspace is assumed; host arithmetic only, no device is touched and no decision changes). out[MTLSSL_PLAN_INFO_LEN]:
+ *   [0]  family, MTLSSL_PLAN_* below
+ *   [1]  plan code, = mtlssl_conv2d_tile_config(d, mode)
+ *   [2]  tile (0..7, CFG_BM x CFG_BN of [11] x [12]) of the GEMM that runs: the direct plan's, the one of the padded /
+ *        space-to-depth / parity sub-problem, the Winograd GEMM stack's; -1 when no tile kernel runs
+ *   [3]  nsplit: K splits of the (main) launch; wgrad: splits of the pixel range      [4] K-steps (16 deep) per split
+ *   [5]  tail_rows: tile rows of the K-split tail launch (0: none)   [6] tail_nsplit   [7] K-steps per tail split
+ *   [8]  K-steps of the whole reduction (a last split is ragged when [8] % [4] != 0)
+ *   [9]  GEMM rows M   [10] GEMM width NG (those of the padded / sub-problem)   [11] BM   [12] BN
+ *   [13] wgrad: pixels per split   [14] = mtlssl_conv2d_num_dispatches(d, mode)   [15] 0
+ * The stride-2 dgrad by input parity runs four sub-problems with a plan each: parity_class 0..3 = (ih % 2) * 2 + iw % 2
+ * selects one ([3] = 0 for a class without taps); the argument is ignored for every other family. */
+#define MTLSSL_PLAN_INFO_LEN 16
+#define MTLSSL_PLAN_DIRECT 0    /* implicit GEMM on the problem as given */
+#define MTLSSL_PLAN_PADDED 1    /* pointwise problem with its reduction (wgrad: output) width zero-padded */
+#define MTLSSL_PLAN_THIN 2      /* K <= 8 pointwise forward, one wavefront per pixel */
+#define MTLSSL_PLAN_S2D 3       /* stride-2 stem as a stride-1 problem on the space-to-depth image */
+#define MTLSSL_PLAN_PARITY 4    /* stride-2 dgrad as four stride-1 problems by input parity */
+#define MTLSSL_PLAN_WINO_F43 5
+#define MTLSSL_PLAN_WINO_M7 6
+#define MTLSSL_PLAN_VALU 7      /* a non-MFMA fallback kernel */
+int mtlssl_conv2d_plan_info(const mtlssl_conv_desc* d, int mode, int parity_class, int32_t* out);
 /* Multiply-accumulates the launch plan of (d, mode) executes on the matrix cores (on_mfma = 1) or in a VALU fallback
  * kernel (on_mfma = 0): direct problems count M*N*K of the implicit GEMM, Winograd variants the transformed-domain
  * GEMM stack, padded / space-to-depth forms their zero-padded width, the input-parity stride-2 dgrad a quarter of the

@@ -1675,6 +1675,71 @@ int mtlssl_conv2d_num_dispatches(const mtlssl_conv_desc* d, int mode) {
   return 1;
 }
 
+// What the launch ladders above will do for (d, mode), read from the same memoised planners (a workspace is assumed,
+// as in mtlssl_conv2d_executed_macs). Host arithmetic only.
+static void plan_info_gemm(const Plan& pl, int64_t M, int64_t NG, int ksteps, int32_t* out) {
+  out[2] = pl.cfg; out[3] = pl.nsplit; out[4] = pl.ks_per_split;
+  out[5] = pl.tail_rows; out[6] = pl.tail_rows > 0 ? pl.tail_nsplit : 0; out[7] = pl.tail_rows > 0 ? pl.tail_ks : 0;
+  out[8] = ksteps; out[9] = (int32_t)M; out[10] = (int32_t)NG; out[11] = CFG_BM[pl.cfg]; out[12] = CFG_BN[pl.cfg];
+}
+int mtlssl_conv2d_plan_info(const mtlssl_conv_desc* d, int mode, int parity_class, int32_t* out) {
+  MTLSSL_REQUIRE(d != nullptr && out != nullptr && mode >= MODE_FWD && mode <= MODE_WGRAD, "plan_info: bad arguments");
+  if (int rc = check_desc(d)) return rc;
+  for (int i = 0; i < MTLSSL_PLAN_INFO_LEN; ++i) out[i] = 0;
+  out[1] = mtlssl_conv2d_tile_config(d, mode);
+  out[2] = -1;
+  out[14] = mtlssl_conv2d_num_dispatches(d, mode);
+  const int64_t P = (int64_t)d->N * d->OH * d->OW;
+  WinoChoice wc;
+  if (choose_wino(d, mode, &wc)) {
+    out[0] = wc.variant == 0 ? MTLSSL_PLAN_WINO_F43 : MTLSSL_PLAN_WINO_M7;
+    out[2] = wc.tile; out[3] = 1;
+    out[9] = (int32_t)(mode == MODE_WGRAD ? d->C : (mode == MODE_FWD ? P : (int64_t)d->N * d->H * d->W));
+    out[10] = mode == MODE_DGRAD ? d->C : d->K;
+    out[11] = CFG_BM[wc.tile]; out[12] = CFG_BN[wc.tile];
+    return MTLSSL_OK;
+  }
+  if (mode == MODE_WGRAD) {
+    mtlssl_conv_desc q = *d;
+    if (mfma_wgrad_ok(d)) out[0] = MTLSSL_PLAN_DIRECT;
+    else if (padded_wgrad_ok(d)) { out[0] = MTLSSL_PLAN_PADDED; q = padded_wgrad_desc(d); }
+    else { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
+    int cfg, ns, pps;
+    wgrad_plan(&q, &cfg, &ns, &pps);
+    out[2] = cfg; out[3] = ns; out[4] = pps / CFG_BK[cfg]; out[8] = (int32_t)cdiv(P, CFG_BK[cfg]);
+    out[9] = q.C; out[10] = q.K; out[11] = CFG_BM[cfg]; out[12] = CFG_BN[cfg]; out[13] = pps;
+    return MTLSSL_OK;
+  }
+  if (mode == MODE_FWD) {
+    mtlssl_conv_desc q = *d;
+    if (mfma_fwd_ok(d)) out[0] = MTLSSL_PLAN_DIRECT;
+    else if (padded_fwd_ok(d)) { out[0] = MTLSSL_PLAN_PADDED; q.C = (int)align_up(d->C, BK); }
+    else if (thin_fwd_ok(d)) { out[0] = MTLSSL_PLAN_THIN; return MTLSSL_OK; }
+    else if (is_pointwise(d)) { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
+    else if (s2d_fwd_ok(d) && s2d_enabled()) { out[0] = MTLSSL_PLAN_S2D; q = s2d_desc(d); }
+    else { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
+    const Plan pl = plan_dir(&q, MODE_FWD);
+    plan_info_gemm(pl, P, q.K, q.R * q.S * (q.C / CFG_BK[pl.cfg]), out);
+    return MTLSSL_OK;
+  }
+  if (parity_ok(d)) {
+    out[0] = MTLSSL_PLAN_PARITY;
+    MTLSSL_REQUIRE(parity_class >= 0 && parity_class < 4, "plan_info: parity class %d of an input-parity dgrad", parity_class);
+    const ParityProblem q = parity_problem(d, parity_class >> 1, parity_class & 1);
+    if (q.Hs == 0 || q.Ws == 0 || q.Rs == 0 || q.Ss == 0) return MTLSSL_OK;        // no GEMM for this class
+    const Plan pl = parity_plan(d, q);
+    plan_info_gemm(pl, (int64_t)d->N * q.Hs * q.Ws, d->C, q.Rs * q.Ss * (d->K / CFG_BK[pl.cfg]), out);
+    return MTLSSL_OK;
+  }
+  mtlssl_conv_desc q = *d;
+  if (mfma_dgrad_ok(d)) out[0] = MTLSSL_PLAN_DIRECT;
+  else if (padded_dgrad_ok(d)) { out[0] = MTLSSL_PLAN_PADDED; q = padded_desc(d); }
+  else { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
+  const Plan pl = plan_dir(&q, MODE_DGRAD);
+  plan_info_gemm(pl, (int64_t)q.N * q.H * q.W, q.C, q.R * q.S * (q.K / CFG_BK[pl.cfg]), out);
+  return MTLSSL_OK;
+}
+
 int64_t mtlssl_conv2d_wgrad_workspace_bytes(const mtlssl_conv_desc* d) {
   if (!d) return 256;
   int64_t bias_part = align_up((int64_t)COLSUM_MAX_PARTS * d->K * 4, 256);

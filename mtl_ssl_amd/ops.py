@@ -373,6 +373,23 @@ def force_conv_config(d, mode, cfg):
     return lib().conv2d_tile_config(ctypes.byref(d), mode)
 
 
+PLAN_FAMILIES = ("direct", "padded", "thin", "space_to_depth", "input_parity", "winograd_F43", "winograd_M7", "valu_fallback")
+_PLAN_INFO_FIELDS = ("family", "code", "tile", "nsplit", "ks_per_split", "tail_rows", "tail_nsplit", "tail_ks", "ksteps",
+                     "M", "NG", "BM", "BN", "pix_per_split", "dispatches")
+
+
+def conv_plan_info(d, mode, parity_class=0):
+    """What a call of (d, mode) will launch (mtlssl_conv2d_plan_info: read-only, host arithmetic, works without a GPU):
+    family (a PLAN_FAMILIES name), plan code, GEMM tile and its BM x BN, the K split (nsplit, ks_per_split of ksteps),
+    the K-split tail launch (tail_rows, tail_nsplit, tail_ks), the GEMM shape M x NG that runs, the wgrad pixels per
+    split and the dispatch count. `parity_class` 0..3 picks the sub-problem of an input-parity stride-2 dgrad."""
+    out = (ctypes.c_int32 * 16)()
+    lib().conv2d_plan_info(ctypes.byref(d), int(mode), int(parity_class), out)
+    info = dict(zip(_PLAN_INFO_FIELDS, (int(v) for v in out)))
+    info["family"] = PLAN_FAMILIES[info["family"]]
+    return info
+
+
 def reset_tuning(use_plan_db=True, autotune=None):
     """Forget every measured / pinned plan: each (problem, mode) seen so far goes back to the library's planner, and
     the next call decides again — from conv_plans.json when `use_plan_db`, by timing when `autotune`. Tests that force
