@@ -49,8 +49,8 @@ def _apply_rccl_knobs():
     MTLSSL_COMM_MIN_CHANNELS are handed to RCCL as NCCL_MAX_NCHANNELS / NCCL_MIN_NCHANNELS (read by RCCL when the
     communicator is created; an explicit NCCL_* setting in the environment wins). tools/cu_thief_probe.py sizes what a
     given channel count costs the step on one GPU."""
-    for mine, theirs in (("MTLSSL_COMM_MAX_CHANNELS", "NCCL_MAX_NCHANNELS"), ("MTLSSL_COMM_MIN_CHANNELS", "NCCL_MIN_NCHANNELS")):
-        v = os.environ.get(mine)
+    for v, theirs in ((os.environ.get("MTLSSL_COMM_MAX_CHANNELS"), "NCCL_MAX_NCHANNELS"),
+                      (os.environ.get("MTLSSL_COMM_MIN_CHANNELS"), "NCCL_MIN_NCHANNELS")):
         if v and theirs not in os.environ:
             os.environ[theirs] = str(int(v))
 

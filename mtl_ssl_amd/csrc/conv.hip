@@ -612,23 +612,10 @@ static inline bool desc_is_pointwise(const mtlssl_conv_desc* d) {
   return d->R == 1 && d->S == 1 && d->stride == 1 && d->dilation == 1 && d->pad_t == 0 && d->pad_l == 0 && d->OH == d->H && d->OW == d->W;
 }
 
-static bool tail_split_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MTLSSL_TAIL_SPLIT");
-    v = e ? atoi(e) : 1;
-  }
-  return v != 0;
-}
 // The split-K fold kernel: a launch plus its traffic. Partials of a few tens of MB are still in the L2 / MALL when the
 // fold reads them (measured 5-6 us for 4 x 5 MB, tools/lab/mid_lab.hip); larger ones stream at the HBM rate the fold reaches.
-// cost of the fold launch behind a K-split: launch + traffic. MTLSSL_FOLD_BASE_US overrides the launch term (A/B switch:
-// on a dependent chain of small launches the fold costs its launch gap as well, which favours fewer splits)
-static inline double fold_base_us() {
-  static const double v = [] { const char* e = getenv("MTLSSL_FOLD_BASE_US"); return e ? atof(e) : 3.0; }();
-  return v;
-}
-static inline double fold_time_us(double bytes) { return fold_base_us() + bytes / (bytes < 48.0e6 ? 7.0e6 : 3.0e6); }
+// cost of the fold launch behind a K-split: launch (3 us) + traffic
+static inline double fold_time_us(double bytes) { return 3.0 + bytes / (bytes < 48.0e6 ? 7.0e6 : 3.0e6); }
 // kc = reduction channels per filter tap (C for fwd, K for dgrad), taps = R*S.
 static Plan plan_gemm(int64_t M, int64_t NG, int taps, int kc, int tuned, double* t_out = nullptr, bool pw = false) {
   const int* resident = CFG_RESIDENT;
@@ -657,7 +644,7 @@ static Plan plan_gemm(int64_t M, int64_t NG, int taps, int kc, int tuned, double
     // Un-split main launch on a whole number of waves + K-split launch of the remaining tile rows.
     const int64_t slots = 256 * resident[c];
     const int64_t R = tiles % slots;
-    if (tail_split_enabled() && !(NG & 3) && tiles >= slots && R > 0 && ksteps >= 32) {
+    if (!(NG & 3) && tiles >= slots && R > 0 && ksteps >= 32) {
       int64_t rows = cdiv(R, tiles_n);
       int64_t tail_tiles = rows * tiles_n;
       int ns = (int)(slots / tail_tiles);
@@ -1164,17 +1151,8 @@ static bool choose_wino(const mtlssl_conv_desc* d, int mode, WinoChoice* wc) {
 // so the engine runs four dense problems on a quarter of the rows each (9 taps in total instead of 36);
 // the results go through a compact buffer and are interleaved into dX by a kernel that applies the epilogue.
 struct ParityProblem { int py, px, Hs, Ws, r0, s0, Rs, Ss, a, b; };
-static bool s2d_enabled() {          // MTLSSL_STEM_S2D=0: the VALU stem kernels (A/B switch)
-  static const bool on = [] { const char* e = getenv("MTLSSL_STEM_S2D"); return !(e && e[0] == '0'); }();
-  return on;
-}
-static bool parity_enabled() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("MTLSSL_DGRAD_PARITY"); v = e ? atoi(e) : 1; }
-  return v != 0;
-}
 static bool parity_ok(const mtlssl_conv_desc* d) {
-  return parity_enabled() && d->stride == 2 && d->dilation == 1 && mfma_dgrad_ok(d) && d->R * d->S > 1 &&
+  return d->stride == 2 && d->dilation == 1 && mfma_dgrad_ok(d) && d->R * d->S > 1 &&
          d->H >= 2 && d->W >= 2;
 }
 static ParityProblem parity_problem(const mtlssl_conv_desc* d, int py, int px) {
@@ -1399,7 +1377,7 @@ int mtlssl_conv2d_fwd_keep(const mtlssl_conv_desc* d, const float* x, const floa
   } else if (is_pointwise(d)) {
     GemmArgs g{x, w, y, bias, residual, nullptr, p.M, d->K, d->C, epi, 0};
     hipLaunchKernelGGL(k_gemm_small<GM_FWD>, dim3(cdiv(g.N, 64), cdiv(g.M, 64)), dim3(256), 0, S(stream), g);
-  } else if (workspace && s2d_fwd_ok(d) && s2d_enabled()) {
+  } else if (workspace && s2d_fwd_ok(d)) {
     const mtlssl_conv_desc q = s2d_desc(d);
     float* xs = (float*)workspace;
     float* wsf = (float*)((char*)workspace + align_up((int64_t)q.N * q.H * q.W * q.C * 4, 256));
@@ -1427,11 +1405,6 @@ int mtlssl_conv2d_fwd_keep(const mtlssl_conv_desc* d, const float* x, const floa
   return check_launch("conv2d_fwd");
 }
 
-// MTLSSL_GROUPED_FWD_CFG: pin the tile of the grouped pointwise forward (0 128x128, 1 128x64, 2 64x64, 3 256x128)
-static int grouped_fwd_cfg_env() {
-  static const int v = [] { const char* e = getenv("MTLSSL_GROUPED_FWD_CFG"); return e ? atoi(e) : -1; }();
-  return v;
-}
 int mtlssl_conv2d_fwd_grouped(const mtlssl_conv_desc* d, const float* x, int n, const mtlssl_conv_group_entry* entries,
                               int max_k, int sum_k, mtlssl_stream_t stream) {
   if (n <= 0) return MTLSSL_OK;
@@ -1455,15 +1428,12 @@ int mtlssl_conv2d_fwd_grouped(const mtlssl_conv_desc* d, const float* x, int n, 
   p.NG = max_k; p.K = max_k; p.ldy = 0;
   p.nsplit = 1; p.ks_per_split = 0; p.tile_m0 = 0; p.ws_m0 = 0;
   // the tile the planner would give the summed problem, without a K split (the group fills the chip instead)
-  int cfg = grouped_fwd_cfg_env();
-  if (cfg < 0 || cfg >= NCFG) {
-    double best = 1e30;
-    cfg = 2;
-    for (int c = 0; c < NCFG; ++c) {
-      const int64_t tiles = cdiv(p.M, CFG_BM[c]) * cdiv(sum_k, CFG_BN[c]);
-      const double t = tile_time_us(c, tiles, d->C / CFG_BK[c], true);
-      if (t < best) { best = t; cfg = c; }
-    }
+  int cfg = 2;
+  double best = 1e30;
+  for (int c = 0; c < NCFG; ++c) {
+    const int64_t tiles = cdiv(p.M, CFG_BM[c]) * cdiv(sum_k, CFG_BN[c]);
+    const double t = tile_time_us(c, tiles, d->C / CFG_BK[c], true);
+    if (t < best) { best = t; cfg = c; }
   }
   p.tiles_m = (int)cdiv(p.M, CFG_BM[cfg]);
   p.tiles_n = (int)cdiv(max_k, CFG_BN[cfg]);
@@ -1621,7 +1591,7 @@ int64_t mtlssl_conv2d_executed_macs(const mtlssl_conv_desc* d, int mode, int on_
     if (mfma_fwd_ok(d)) mfma = direct;
     else if (padded_fwd_ok(d)) mfma = P_out * align_up(d->C, BK) * d->K;
     else if (is_pointwise(d)) valu = direct;
-    else if (s2d_fwd_ok(d) && s2d_enabled()) mfma = P_out * ((d->R + 1) / 2) * ((d->S + 1) / 2) * BK * d->K;
+    else if (s2d_fwd_ok(d)) mfma = P_out * ((d->R + 1) / 2) * ((d->S + 1) / 2) * BK * d->K;
     else valu = direct;
   } else if (mode == MODE_DGRAD) {
     const int64_t gathered = P_in * taps * d->C * d->K;        // every tap visited for every input pixel
@@ -1716,7 +1686,7 @@ int mtlssl_conv2d_plan_info(const mtlssl_conv_desc* d, int mode, int parity_clas
     else if (padded_fwd_ok(d)) { out[0] = MTLSSL_PLAN_PADDED; q.C = (int)align_up(d->C, BK); }
     else if (thin_fwd_ok(d)) { out[0] = MTLSSL_PLAN_THIN; return MTLSSL_OK; }
     else if (is_pointwise(d)) { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
-    else if (s2d_fwd_ok(d) && s2d_enabled()) { out[0] = MTLSSL_PLAN_S2D; q = s2d_desc(d); }
+    else if (s2d_fwd_ok(d)) { out[0] = MTLSSL_PLAN_S2D; q = s2d_desc(d); }
     else { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
     const Plan pl = plan_dir(&q, MODE_FWD);
     plan_info_gemm(pl, P, q.K, q.R * q.S * (q.C / CFG_BK[pl.cfg]), out);
@@ -1826,12 +1796,6 @@ int mtlssl_conv2d_wgrad_xf(const mtlssl_conv_desc* d, const float* x, const floa
   return mtlssl_conv2d_wgrad_ex(d, x, dy, out_scale, dw, dbias, nullptr, beta, workspace, input_xf, input_variant, stream);
 }
 
-// MTLSSL_FUSE_COLSUM=0: the bias gradient's partial column sums as a launch of their own (A/B switch)
-static bool fuse_colsum() {
-  static const bool on = [] { const char* e = getenv("MTLSSL_FUSE_COLSUM"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
 int mtlssl_conv2d_wgrad_ex(const mtlssl_conv_desc* d, const float* x, const float* dy,
                            const float* out_scale, float* dw, float* dbias, const float* dbias_scale, float beta,
                            void* workspace, const float* input_xf, int input_variant, mtlssl_stream_t stream) {
@@ -1872,7 +1836,7 @@ int mtlssl_conv2d_wgrad_ex(const mtlssl_conv_desc* d, const float* x, const floa
                        split_wgrad_plan(P, d->C, d->K, d->R * d->S, &ns, &pps);
     // bias gradient: the GEMM's own blocks of tile row 0 / tap 0 leave [split][K] column sums of dy in the column-sum
     // region of the workspace (conv_mfma.h: cs_part) — no launch of its own; the split engine keeps the partial kernel
-    const bool ride = dbias && !split && fuse_colsum() && ns <= COLSUM_MAX_PARTS;
+    const bool ride = dbias && !split && ns <= COLSUM_MAX_PARTS;
     if (dbias && !ride) colsum_partial();
     p.out = ws_main;
     p.M = d->C; p.NG = d->K; p.nsplit = ns; p.pix_per_split = pps;
@@ -1896,7 +1860,7 @@ int mtlssl_conv2d_wgrad_ex(const mtlssl_conv_desc* d, const float* x, const floa
     pq.a = x; pq.b = dy_pad; pq.out = ws_q;
     pq.a_bytes = p.a_bytes; pq.b_bytes = (unsigned)(P * q.K * 4);
     pq.M = q.C; pq.NG = q.K; pq.nsplit = ns; pq.pix_per_split = pps;
-    const bool ride = dbias && fuse_colsum() && (int64_t)ns * q.K <= (int64_t)COLSUM_MAX_PARTS * d->K;
+    const bool ride = dbias && (int64_t)ns * q.K <= (int64_t)COLSUM_MAX_PARTS * d->K;
     pq.cs_part = ride ? (float*)workspace : nullptr;
     launch_mfma<MODE_WGRAD>(cfg, pq, dim3(1, 1, ns), st);
     const int main_blocks = (int)cdiv((int64_t)d->C * d->K, 256);

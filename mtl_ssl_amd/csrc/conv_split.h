@@ -456,8 +456,7 @@ inline void launch_split(ConvArgs& p, dim3 extra, hipStream_t st, int tile_rows 
   p.tiles_m = tile_rows >= 0 ? tile_rows : (int)cdiv(p.M, SPLIT_BM);
   p.tiles_n = (int)cdiv(p.NG, SPLIT_BN);
   dim3 grid(p.tiles_m * p.tiles_n, extra.y, extra.z);
-  static const bool quad_ok = [] { const char* e = getenv("MTLSSL_SPLIT_QUAD"); return !e || atoi(e) != 0; }();
-  const bool pw = quad_ok && MODE != MODE_WGRAD && p.R == 1 && p.S == 1 && p.stride == 1 && p.pt == 0 && p.pl == 0 &&
+  const bool pw = MODE != MODE_WGRAD && p.R == 1 && p.S == 1 && p.stride == 1 && p.pt == 0 && p.pl == 0 &&
                   p.OH == p.H && p.OW == p.W;
   if (pw) hipLaunchKernelGGL((k_split256<MODE, BATCH, true>), grid, dim3(512), split_lds_bytes(256), st, p);
   else hipLaunchKernelGGL((k_split256<MODE, BATCH, false>), grid, dim3(512), split_lds_bytes(256), st, p);

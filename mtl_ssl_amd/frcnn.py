@@ -36,14 +36,6 @@ def _l2_from_hyperparams(hp):
 
 
 
-def side_stream_priority():
-    """HIP priority of the step's side streams (aux towers / losses, filter gradients). MTLSSL_SIDE_STREAM_PRIORITY:
-    0 (default) = the same as the main stream; a positive value = LOWER than the main stream where the runtime has such a
-    level (hipDeviceGetStreamPriorityRange; torch clamps to the range), so that the dispatcher serves the main stream's
-    chain first and the side streams fill what it leaves. A/B: profiles/r06_stream_priority_ab.txt."""
-    return int(os.environ.get("MTLSSL_SIDE_STREAM_PRIORITY", "0"))
-
-
 class MaskRCNNBoxPredictor:
     """core/box_predictor.py:339-611: RoI features -> (spatial mean | flatten) -> optional FC_i_depth layers, each
     followed by dropout when use_dropout -> FC heads. The depth of the extra layers is
@@ -277,7 +269,7 @@ class FasterRCNNMetaArch:
         if self.ps.device.type != "cuda" or os.environ.get("MTLSSL_AUX_STREAM", "1") == "0":
             return None
         if getattr(self, "_aux_stream_obj", None) is None:
-            self._aux_stream_obj = torch.cuda.Stream(device=self.ps.device, priority=side_stream_priority())
+            self._aux_stream_obj = torch.cuda.Stream(device=self.ps.device)
         return self._aux_stream_obj
 
     def _wgrad_exec(self):
@@ -290,8 +282,7 @@ class FasterRCNNMetaArch:
                 env is None and not getattr(self._feature_extractor, "supports_wgrad_stream", False)):
             return nn.INLINE_WGRAD
         if getattr(self, "_wgrad_stream_obj", None) is None:
-            self._wgrad_stream_obj = nn.WgradStream(torch.cuda.Stream(device=self.ps.device, priority=side_stream_priority()),
-                                                    group=os.environ.get("MTLSSL_WGRAD_GROUP", "0") == "1")
+            self._wgrad_stream_obj = nn.WgradStream(torch.cuda.Stream(device=self.ps.device))
         return self._wgrad_stream_obj
 
     def compute_streams(self):
@@ -315,8 +306,7 @@ class FasterRCNNMetaArch:
         ops.fold_scales(self.ps)
         # transformed filters of the Winograd layers are kept per optimizer step (ops.FilterXfCache); the frozen
         # layers' shadow filters were just re-created, so start from an empty cache
-        on = self.ps.device.type == "cuda" and os.environ.get("MTLSSL_FILTER_CACHE", "1") != "0"
-        self.ps.filter_cache = ops.FilterXfCache() if on else None
+        self.ps.filter_cache = ops.FilterXfCache() if self.ps.device.type == "cuda" else None
 
     def refold(self, folded=False):
         """After an optimizer step: ONE batched refresh of the normaliser constants of the layers whose
@@ -665,19 +655,14 @@ class FasterRCNNMetaArch:
 
     def _refine_stream(self):
         """Third forward stream: the refiner's window pass next to the second stage's own towers (None on CPU, without
-        the auxiliary stream, or with MTLSSL_REFINE_EARLY=0)."""
+        the auxiliary or the filter-gradient stream, or with MTLSSL_REFINE_EARLY=0)."""
         if self._aux_stream() is None or os.environ.get("MTLSSL_REFINE_EARLY", "0") != "1":
             return None
         # the filter-gradient stream is idle during the forward pass: reuse it rather than create a fourth compute
         # stream — HIP multiplexes streams onto a few hardware queues (4 by default), and with the data-parallel
         # trainer's own step and communication streams a further one ended up sharing a queue with another compute
         # stream (measured with a 1-rank communicator: 60.2 ms/step against 55.5)
-        w = self._wgrad_exec()
-        if getattr(w, "stream", None) is not None and os.environ.get("MTLSSL_REFINE_OWN_STREAM", "0") != "1":
-            return w.stream
-        if getattr(self, "_refine_stream_obj", None) is None:
-            self._refine_stream_obj = torch.cuda.Stream(device=self.ps.device)
-        return self._refine_stream_obj
+        return getattr(self._wgrad_exec(), "stream", None)
 
     def predict_with_mtl_results(self, pd):
         """faster_rcnn_meta_arch.py:764-846, executed per image."""
@@ -1035,7 +1020,7 @@ class FasterRCNNMetaArch:
                 self.ps.grad_ready_hook = hook
         crop_args = (int(c.initial_crop_size), int(c.maxpool_kernel_size), int(c.maxpool_stride))
 
-        def aux_backward(collect=None, which=("closeness", "window")):
+        def aux_backward(collect=None):
             """collect: a list that receives (crop gradient, arg-max, boxes, box indices) instead of the RoI-crop
             backward being issued here (the caller adds them to dF later, on the stream that owns dF)."""
             if shared:
@@ -1045,24 +1030,18 @@ class FasterRCNNMetaArch:
                                                    need_feat_grad=False)
                 return
             todo = []
-            # MTLSSL_AUX_TOWER_WGRAD_STREAM=1: the aux towers' filter gradients on the filter-gradient stream as well (they
-            # feed nothing but the optimizer), which leaves the aux stream the two dgrad chains only
-            awg = {}
-            if (os.environ.get("MTLSSL_AUX_TOWER_WGRAD_STREAM", "0") == "1"
-                    and getattr(self.closeness_tower if mtl.closeness else self.window_tower, "supports_wgrad_stream", False)):
-                awg = dict(wgrad=self._wgrad_exec())
-            if mtl.closeness and "closeness" in which:
+            if mtl.closeness:
                 cfeat = pd["_cfeat"]
                 g = self.closeness_predictor.backward(pd["_cp"], d["closeness_predictions"], None, cfeat.shape,
                                                       mask_ref=cfeat, mask6=m6)
-                gc = self.closeness_tower.backward(g, cfeat, pd["_cctx"], need_input_grad=not stop, masked=True, **awg)
+                gc = self.closeness_tower.backward(g, cfeat, pd["_cctx"], need_input_grad=not stop, masked=True)
                 if not stop:
                     todo.append((gc, pd["_argmax"], pd["proposal_boxes_normalized"].view(-1, 4), pd["_box_ind"]))
-            if mtl.window and "window" in which:
+            if mtl.window:                       # behind the closeness tower, on the same stream
                 wfeat = pd["_wfeat"]
                 g = self.window_predictor.backward(pd["_wp"], d["window_class_predictions"], None, wfeat.shape,
                                                    mask_ref=wfeat, mask6=m6)
-                gw = self.window_tower.backward(g, wfeat, pd["_wctx"], need_input_grad=not stop, masked=True, **awg)
+                gw = self.window_tower.backward(g, wfeat, pd["_wctx"], need_input_grad=not stop, masked=True)
                 if not stop:
                     todo.append((gw, pd["_wargmax"], pd["_wboxes"], pd["_wbox_ind"]))
             if collect is not None:
@@ -1071,39 +1050,23 @@ class FasterRCNNMetaArch:
                 for gx, am, bx, bi in todo:
                     ops.roi_crop_pool_bwd(gx, am, F.shape, bx, bi, *crop_args, dfeat=dF)
 
-        # WITHOUT stop_gradient_for_aux_tasks (MobileNet's and R-FCN's paper settings) the aux towers' crop gradients
-        # join dF, but the tower passes themselves are still independent of the main tower's: they run on the second
-        # stream next to it, and their RoI-crop backward is issued on this stream, after the main head's (which
-        # writes dF in full), in the order the single-stream form used — the same sums, bit for bit.
+        # The aux towers' backward is independent of the main tower's: with a second stream it is forked at the START of
+        # backward. With the main tower's filter gradients on the filter-gradient stream, this stream carries only the
+        # dgrad chain towards dF, and the aux towers' large tiles fill what that chain and, later, the small GEMMs of the
+        # RPN / trunk backward (4 864 pixels at B=2) leave idle (55.6 -> 55.3 ms against forking after the main tower's
+        # backward). WITHOUT stop_gradient_for_aux_tasks (MobileNet's and R-FCN's paper settings) the towers' crop
+        # gradients join dF: they are collected in `pending` and their RoI-crop backward is issued on this stream, after
+        # the main head's (which writes dF in full), in the order the single-stream form used — the same sums, bit for bit.
         cur = torch.cuda.current_stream()
-        early, pending = None, []
-        if not stop and not shared and (mtl.closeness or mtl.window):
-            early = self._aux_stream()
-        if early is not None:
-            early.wait_stream(cur)
-            with torch.cuda.stream(early):
+        aux = self._aux_stream() if (mtl.closeness or mtl.window) else None
+        pending = []
+        if aux is not None and not shared:
+            aux.wait_stream(cur)
+            with torch.cuda.stream(aux):
                 aux_backward(collect=pending)
-        side0, window_on_main = None, False
-        if (stop and not shared and (mtl.closeness or mtl.window)
-                and os.environ.get("MTLSSL_AUX_RELEASE", "start") == "start"):
-            side0 = self._aux_stream()
-            if side0 is not None:
-                # MTLSSL_WINDOW_BWD=third: the window tower's backward on the filter-gradient stream instead of behind the
-                # closeness tower's on the aux stream (A/B: profiles/r06_window_bwd_third_ab.txt)
-                wplace = os.environ.get("MTLSSL_WINDOW_BWD", "aux") if (mtl.closeness and mtl.window) else "aux"
-                third = getattr(self._wgrad_exec(), "stream", None) if wplace == "third" else None
-                window_on_main = wplace == "main"
-                side0.wait_stream(cur)
-                with torch.cuda.stream(side0):
-                    aux_backward(which=("closeness", "window") if (third is None and not window_on_main) else ("closeness",))
-                if third is not None:
-                    third.wait_stream(cur)
-                    with torch.cuda.stream(third):
-                        aux_backward(which=("window",))
-        if (getattr(self.tower, "supports_wgrad_stream", False) and not shared
-                and os.environ.get("MTLSSL_TOWER_WGRAD_STREAM", "1") == "1"):
-            # the main tower's filter gradients feed nothing but the optimizer: on the third stream (joined at the end
-            # of backward) they leave this stream the dgrad chain that the trunk's backward is waiting for
+        if getattr(self.tower, "supports_wgrad_stream", False) and not shared:
+            # the main tower's filter gradients feed nothing but the optimizer: on the filter-gradient stream (joined at
+            # the end of backward) they leave this stream the dgrad chain that the trunk's backward is waiting for
             g_crops = self.tower.backward(g_feat, feat, pd["_tower_ctx"], need_input_grad=True, masked=True,
                                           wgrad=self._wgrad_exec())
         else:
@@ -1112,30 +1075,22 @@ class FasterRCNNMetaArch:
                               pd["_box_ind"], *crop_args, dfeat=dF, accumulate=False)
         if gw_shared is not None:
             ops.roi_crop_pool_bwd(gw_shared, pd["_wargmax"], F.shape, pd["_wboxes"], pd["_wbox_ind"], *crop_args, dfeat=dF)
-        if window_on_main:              # MTLSSL_WINDOW_BWD=main: the (small) window tower's backward behind the main tower's
-            aux_backward(which=("window",))
-        if early is not None:
-            ops.wait_on(early, "backward: aux towers released early", cur)
+        if pending:                          # not stop: the forked towers' crop gradients join dF here
+            ops.wait_on(aux, "backward: aux towers released early", cur)
             for gx, am, bx, bi in pending:
                 gx.record_stream(cur)         # made on the second stream, consumed and released on this one
                 ops.roi_crop_pool_bwd(gx, am, F.shape, bx, bi, *crop_args, dfeat=dF)
-
-        # With stop_gradient_for_aux_tasks the aux towers' backward touches neither dF nor any tensor of the main path:
-        # it runs on the second HIP stream. Released at the START of backward (above): with the main tower's filter
-        # gradients on the third stream, this stream carries only the dgrad chain towards dF, and the aux towers' large
-        # tiles fill what that chain and, later, the small GEMMs of the RPN / trunk backward (4 864 pixels at B=2)
-        # leave idle (55.6 -> 55.3 ms against releasing it after the main tower's backward, MTLSSL_AUX_RELEASE=late,
-        # which was the better choice while the main tower's filter gradients still ran on this stream).
-        side = self._aux_stream() if (stop and (mtl.closeness or mtl.window)) else None
-        if side0 is not None:
-            side = side0
-        elif side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
+        if aux is None:
+            aux_backward()                   # no second stream (or CPU): inline, after the main tower
+        elif shared and stop:
+            # shared tower: what is left for the aux stream is the window head's predictor-only backward, which touches
+            # neither dF nor the main path. It is forked only now, behind the main tower's backward
+            aux.wait_stream(cur)
+            with torch.cuda.stream(aux):
                 aux_backward()
-        elif early is None:
-            aux_backward()
-        return self._backward_first_stage(pd, d, F, dF, B, side)
+        # with stop_gradient_for_aux_tasks nothing of the aux stream's work came back to this stream above:
+        # _backward_first_stage joins it at the end of backward
+        return self._backward_first_stage(pd, d, F, dF, B, aux if stop else None)
 
     def _backward_first_stage(self, pd, d, F, dF, B, side=None):
         """Edge-mask head, RPN heads and the trunk: dF holds what the second stage sent back (zeros for an RPN-only

@@ -196,7 +196,7 @@ class Branches:
             d = ch[0].desc(x.shape)
             if not (ops.desc_is_pointwise(d) and d.K % 16 == 0 and d.C % 4 == 0 and d.C >= 16):
                 return False
-        return x.shape[0] * x.shape[1] * x.shape[2] <= ops.SEG_DGRAD_MAX_ROWS
+        return True
 
     def backward(self, g_cat, acts, residual=None, mask_ref=None, need_input_grad=True, wgrad=nn.INLINE_WGRAD):
         """g_cat: dL/d(concat), already masked by (concat > 0). Returns dL/dx (+ residual), masked by
@@ -375,9 +375,7 @@ class InceptionTower:
         gp = self.conv_7b.dgrad(pre7b.shape, gp)                # Block8 has no activation: no mask
         for i in range(len(self.blocks) - 1, -1, -1):
             gp = self.blocks[i].backward(gp, ctxs[i], mask_input=True, wgrad=wgrad)
-        g = self.mixed_7a.backward(gp, c7, mask_input=False, need_input_grad=need_input_grad, wgrad=wgrad)
-        wgrad.flush()
-        return g
+        return self.mixed_7a.backward(gp, c7, mask_input=False, need_input_grad=need_input_grad, wgrad=wgrad)
 
 
 class FasterRCNNInceptionResnetV2FeatureExtractor:
@@ -474,7 +472,6 @@ class FasterRCNNInceptionResnetV2FeatureExtractor:
                 break
             prev_pool = isinstance(self.stem[i - 1], Pool)
             g = l.dgrad(xin.shape, g, mask_ref=None if prev_pool else xin)
-        wgrad.flush()
 
     def box_classifier_tower(self, scope, trainable):
         return InceptionTower(self.ps, scope, trainable and self.is_training, self.weight_decay)

@@ -9,8 +9,6 @@ Frozen BatchNorm (the reference always runs BN in inference mode during detector
 models/faster_rcnn_resnet_v1_feature_extractor.py:138,171) is folded: w_eff = w * scale[k],
 y = conv(x, w_eff) + shift[k]; dW = scale[k] * wgrad(x, g).
 """
-import os
-
 import torch
 
 from . import ops
@@ -35,62 +33,19 @@ class WgradStream:
     optimizer; taken out of that chain they fill the CUs the chain leaves idle. The caller joins the stream
     before the optimizer (FasterRCNNMetaArch.backward) and lists it in compute_streams() for the reducer."""
 
-    GROUP = int(os.environ.get("MTLSSL_WGRAD_GROUP_SIZE", "8"))   # shape-identical 1x1 layers whose filter gradients go out as ONE grouped launch
-
-    def __init__(self, stream, group=False):
-        """group: collect the 1x1 layers' filter gradients and issue GROUP of them per launch
-        (mtlssl_conv2d_wgrad_grouped). Measured on config[1]: 58.2-58.5 ms/step against 57.5 with one launch per
-        layer — the grouped launches start later and, being chip-filling, contend with the dgrad chain they are
-        supposed to hide behind — so it is off by default (MTLSSL_WGRAD_GROUP=1 turns it on)."""
+    def __init__(self, stream):
         self.stream = stream
-        self.group = group
-        self.pending = {}
-
-    def _fork(self, tensors):
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self.stream.wait_event(ev)
-        for t in tensors:                     # keep the caching allocator from recycling them under the side stream
-            t.record_stream(self.stream)
 
     def run(self, layer, x, g):
         if not layer.trainable:
             return
-        d = layer.desc(x.shape)
-        if (self.group and isinstance(layer, ConvBN) and d.R == 1 and d.S == 1 and d.stride == 1
-                and not (layer.bn_trainable and layer.gamma is None)):
-            # The 22 identical units of block3 each give a 4 864-pixel reduction — a handful of tiles, a split of the
-            # pixel range and a fold kernel per layer. GROUP of them at a time are issued as one launch whose tiles
-            # fill the chip without a split (mtlssl_conv2d_wgrad_grouped).
-            key = (x.shape, layer.w.shape)
-            q = self.pending.setdefault(key, [])
-            q.append((layer, x, g))
-            if len(q) >= self.GROUP:
-                self._flush(key)
-            return
-        self._fork((x, g))
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        self.stream.wait_event(ev)
+        for t in (x, g):                      # keep the caching allocator from recycling them under the side stream
+            t.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
             layer.wgrad(x, g)
-
-    def _flush(self, key):
-        q = self.pending.pop(key, [])
-        if not q:
-            return
-        self._fork([t for _, x, g in q for t in (x, g)])
-        with torch.cuda.stream(self.stream):
-            if len(q) == 1:
-                q[0][0].wgrad(q[0][1], q[0][2])
-                return
-            ps = q[0][0].ps
-            ops.conv2d_wgrad_grouped(q[0][0].desc(q[0][1].shape), [x for _, x, _ in q], [g for _, _, g in q],
-                                     [ps.grad(l.w.name) for l, _, _ in q], [l.scale for l, _, _ in q], beta=1.0)
-            for l, _, _ in q:
-                ps.grad_ready(l.w)
-
-    def flush(self):
-        """Issue whatever is still waiting for its group to fill (call at the end of the backward chain)."""
-        for key in list(self.pending):
-            self._flush(key)
 
 
 class _InlineWgrad:
@@ -99,10 +54,6 @@ class _InlineWgrad:
     @staticmethod
     def run(layer, x, g):
         layer.wgrad(x, g)
-
-    @staticmethod
-    def flush():
-        pass
 
 
 INLINE_WGRAD = _InlineWgrad()

@@ -500,7 +500,7 @@ class FilterXfCache:
     # of transformed filters per launch, each chunk with an event of its own: the first Winograd layer of the next forward
     # waits for the first small launch, not for the transform of every filter of the model (1.3 GB at configs[1] — a
     # 0.7-ms stall of the main stream per step, measured with ops.JoinTimer)
-    CHUNK_BYTES = int(float(os.environ.get("MTLSSL_XF_REFRESH_CHUNK_MB", "48")) * (1 << 20))
+    CHUNK_BYTES = 48 << 20
 
     def _tables(self):
         """Device pointer tables per chunk, rebuilt only when the set of entries (or the chunk size) changed."""
@@ -547,12 +547,9 @@ class FilterXfCache:
                 e["event"], e["waited"] = ev, {run_on.cuda_stream}
 
 
-KEEP_INPUT_XF = os.environ.get("MTLSSL_KEEP_INPUT_XF", "1") != "0"
-
-
 def _shared_input_variant(d):
     """The Winograd variant both the forward and the filter gradient of `d` are planned with (-1: none in common)."""
-    if not (KEEP_INPUT_XF and d.R == 3 and d.S == 3):
+    if not (d.R == 3 and d.S == 3):
         return -1
     v = lib().conv2d_filter_xf_variant(ctypes.byref(d), 0)
     return v if (v >= 0 and v == lib().conv2d_filter_xf_variant(ctypes.byref(d), 2)) else -1
@@ -676,7 +673,7 @@ GROUPED_FWD = os.environ.get("MTLSSL_GROUPED_FWD", "1") != "0"
 # problems with more rows than this fill the chip on their own and keep their tuned plans (the grouped launch runs the
 # register-staged engine without a K split). Same-box A/B on configs[4] (profiles/r06_grouped_fwd_ab.txt): separate
 # launches 108.2 ms/step, grouped up to 5 000 rows 107.9, up to 17 000 rows 107.5, every block 107.5
-GROUPED_FWD_MAX_ROWS = int(os.environ.get("MTLSSL_GROUPED_FWD_MAX_ROWS", "20000"))
+GROUPED_FWD_MAX_ROWS = 20000
 
 
 class _GroupEntry(ctypes.Structure):
@@ -721,7 +718,6 @@ def conv2d_fwd_grouped(x, problems):
 
 
 SEG_DGRAD = os.environ.get("MTLSSL_SEG_DGRAD", "1") != "0"
-SEG_DGRAD_MAX_ROWS = int(os.environ.get("MTLSSL_SEG_DGRAD_MAX_ROWS", "1000000000"))
 
 
 class _SegEntry(ctypes.Structure):

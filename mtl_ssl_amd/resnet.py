@@ -49,7 +49,6 @@ class BoxClassifierTower:
             first = i == 0
             gp = units[i].backward(gp, ctxs[i], need_input_grad=(need_input_grad or not first),
                                    mask_input=not first, wgrad=wgrad)
-        wgrad.flush()
         return gp
 
 
@@ -128,7 +127,6 @@ class FasterRCNNResnetV1FeatureExtractor:
             g1 = ops.maxpool_bwd(y1, pooled, gp, 3, 2, pads)
             self.conv1.bn_grad(y1, ops.relu_bwd(y1, g1))
             self._root_ctx = None
-        wgrad.flush()
 
     def box_classifier_tower(self, scope, trainable):
         return BoxClassifierTower(self.ps, scope, self.arch, self.cout, trainable and self.is_training,

@@ -8,6 +8,8 @@ and per-proposal predictions come from position-sensitive ROI pooling of the sco
 RPN, target assignment, sampling and every loss are inherited from FasterRCNNMetaArch — loss() and the
 evaluator's eval_loss() (rfcn_meta_arch.py defines no loss of its own either).
 """
+import os
+
 import torch
 
 from . import nn, ops
@@ -44,14 +46,10 @@ class RfcnBoxPredictor:
         return [l for l in (self.reduce, self.loc, self.cls) if l is not None]
 
     def predict(self, feat, boxes_flat, box_ind):
-        """boxes_flat: the [n,4] normalised boxes, or a callable that returns them — called after the score maps have been
-        issued and before the first pooling (the maps do not depend on the boxes: a caller whose proposal chain runs on
-        another stream joins it there)."""
+        """boxes_flat: the [n,4] normalised boxes."""
         net = self.reduce.forward(feat)
         cls_map = self.cls.forward(net)
         loc_map = self.loc.forward(net) if self.loc is not None else None
-        if callable(boxes_flat):
-            boxes_flat = boxes_flat()
         out = {"net": net, "cls_map_shape": tuple(cls_map.shape), "boxes": boxes_flat, "box_ind": box_ind,
                "class": ops.psroi_fwd(cls_map, boxes_flat, box_ind, self.crop, self.bins)}
         if loc_map is not None:
@@ -105,60 +103,28 @@ class RFCNMetaArch(FasterRCNNMetaArch):
         B, H, W, _ = pd["image_shape"]
         F = pd["rpn_features_to_crop"]
         gt = self._format_groundtruth_data(H, W) if self._is_training else None
-        import os
         N2 = self.max_num_proposals
-
-        def proposal_chain():
-            props, _scores, nprop = ops.rpn_proposals(
-                pd["rpn_box_encodings"], pd["rpn_objectness_predictions_with_background"], pd["anchors"],
-                H, W, c.first_stage_nms_score_threshold, c.first_stage_nms_iou_threshold,
-                int(c.first_stage_max_proposals))
-            return self._second_stage_proposals(props, nprop, gt, H, W)
-
         # block4 runs on the WHOLE map here: the main tower and its score maps do not depend on the proposals, only the
-        # position-sensitive pooling does. The decode -> NMS -> sampling chain (a string of latency-bound kernels, a
-        # one-wavefront greedy scan among them) therefore goes to the filter-gradient stream, idle during the forward pass,
-        # and is joined right before the first pooling — MTLSSL_RFCN_PROPOSALS_SIDE=1. OFF by default: a measured null
-        # (34.93 / 34.91 / 34.97 ms per step against 34.80 / 34.91 / 35.05 on this stream, profiles/r06_rfcn_chain_side_ab.txt):
-        # the window tower's forward on the aux stream already fills the chip under the chain.
-        pside = None
-        if self._is_training and self._aux_stream() is not None and os.environ.get("MTLSSL_RFCN_PROPOSALS_SIDE", "0") == "1":
-            pside = getattr(self._wgrad_exec(), "stream", None)
-        cur = torch.cuda.current_stream() if pside is not None else None
-        if pside is not None:
-            pside.wait_stream(cur)
-            with torch.cuda.stream(pside):
-                chain_out = proposal_chain()
-        else:
-            chain_out = proposal_chain()
-        joined = {}
-
-        def flat_boxes():
-            """The sampled boxes as the poolings take them; joins the proposal chain on first use."""
-            if "flat" not in joined:
-                if pside is not None:
-                    ops.wait_on(pside, "second stage: proposal chain", cur)
-                    for t in chain_out:                      # made on that stream, used (and released) on this one and on
-                        t.record_stream(cur)                 # the aux stream (loss terms)
-                        t.record_stream(self._aux_stream())
-                joined["flat"] = chain_out[1].view(B * N2, 4)
-            return joined["flat"]
-
+        # position-sensitive pooling does. The decode -> NMS -> sampling chain nevertheless stays on this stream: the
+        # window tower's forward on the aux stream already fills the chip under it (retired switches)
+        props, _scores, nprop = ops.rpn_proposals(
+            pd["rpn_box_encodings"], pd["rpn_objectness_predictions_with_background"], pd["anchors"],
+            H, W, c.first_stage_nms_score_threshold, c.first_stage_nms_iou_threshold,
+            int(c.first_stage_max_proposals))
+        boxes_abs, boxes_norm, num = self._second_stage_proposals(props, nprop, gt, H, W)
+        flat = boxes_norm.view(B * N2, 4)
         box_ind = self._box_ind(B, N2, F.device)
         cside = None
         if (mtl.closeness and self._is_training and not self._shared_classifier
                 and os.environ.get("MTLSSL_CLOSENESS_FWD_SIDE", "0") == "1"):
             cside = self._aux_stream()
         if cside is not None:          # the closeness tower (block4 on the whole map) next to the main tower's forward
-            flat_boxes()               # its pooling runs over there: join the proposal chain on this stream first
             cside.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(cside):
                 cfeat_s, cctx_s = self.closeness_tower.forward(F, self._is_training)
-                cp_s = self.closeness_predictor.predict(cfeat_s, flat_boxes(), box_ind)
+                cp_s = self.closeness_predictor.predict(cfeat_s, flat, box_ind)
         feat, tower_ctx = self.tower.forward(F, self._is_training)
-        bp = self.box_predictor.predict(feat, flat_boxes, box_ind)
-        flat = flat_boxes()
-        boxes_abs, boxes_norm, num = chain_out
+        bp = self.box_predictor.predict(feat, flat, box_ind)
         out = {
             "refined_box_encodings": bp["box"].view(B * N2, self.num_classes, 4),
             "class_predictions_with_background": bp["class"],
@@ -259,24 +225,21 @@ class RFCNMetaArch(FasterRCNNMetaArch):
             g_feat_closeness = self.closeness_predictor.backward(pd["_cp"], d["closeness_predictions"], None,
                                                                  pd["_cfeat"], need_feat_grad=not stop)
 
-        def aux_backward(which=("closeness", "window")):
-            import os
-            awg = {}
-            # The aux towers' filter gradients go to the filter-gradient stream (joined at the end of backward): the aux stream
-            # then carries the two towers' dgrad chains only, whose input gradients the main stream is waiting for (3.5 ms per
-            # step at that join, `whole_step.main_stream_joins`). Same-box A/B, three passes: 35.12 -> 34.79 ms/step
-            # (profiles/r06_rfcn_tower_wgrad_ab.txt); the main tower's own filter gradients there as well: no gain (35.16).
-            # MTLSSL_AUX_TOWER_WGRAD_STREAM=0 keeps them on the aux stream. (Faster R-CNN's aux towers — stop_gradient, nobody
-            # waits for them — lose with it: +1.8 ms on configs[1], +5.8 on configs[4]; off by default there.)
-            if os.environ.get("MTLSSL_AUX_TOWER_WGRAD_STREAM", "1") == "1" and getattr(self.tower, "supports_wgrad_stream", False):
-                awg = dict(wgrad=self._wgrad_exec())
-            if mtl.closeness and not shared and "closeness" in which:
+        # The aux towers' filter gradients go to the filter-gradient stream (joined at the end of backward): the aux stream
+        # then carries the two towers' dgrad chains only, whose input gradients the main stream is waiting for (3.5 ms per
+        # step at that join, `whole_step.main_stream_joins`). Same-box A/B, three passes: 35.12 -> 34.79 ms/step
+        # (profiles/r06_rfcn_tower_wgrad_ab.txt); the main tower's own filter gradients there as well: no gain (35.16), so
+        # they stay inline. (Faster R-CNN's aux towers — stop_gradient, nobody waits for them — lose with it.)
+        awg = dict(wgrad=self._wgrad_exec()) if getattr(self.tower, "supports_wgrad_stream", False) else {}
+
+        def aux_backward():
+            if mtl.closeness and not shared:
                 cfeat = pd["_cfeat"]
                 g = self.closeness_predictor.backward(pd["_cp"], d["closeness_predictions"], None, cfeat)
                 g_c = self.closeness_tower.backward(g, cfeat, pd["_cctx"], need_input_grad=not stop, **awg)
                 if not stop:
                     held.append(g_c)
-            if mtl.window and "window" in which:
+            if mtl.window:                        # behind the closeness tower, on the same stream
                 wfeat = pd["_wfeat"]
                 if shared and stop:               # gradient stopped at the window tower's output: the predictor alone trains
                     self.window_predictor.backward(pd["_wp"], d["window_class_predictions"], None, wfeat,
@@ -297,46 +260,21 @@ class RFCNMetaArch(FasterRCNNMetaArch):
         # stream once the second one has been joined — before the RPN / trunk backward, which needs the sum.
         cur = torch.cuda.current_stream()
         side = self._aux_stream() if (mtl.closeness or mtl.window) else None
-        import os
-        # MTLSSL_RFCN_WINDOW_BWD: where the window tower's backward runs when both aux towers have one — "aux" (default:
-        # behind the closeness tower's on the aux stream), "main" (on this stream, behind the main tower's) or "third" (on
-        # the filter-gradient stream). A/B: profiles/r06_rfcn_window_bwd_ab.txt.
-        wplace = os.environ.get("MTLSSL_RFCN_WINDOW_BWD", "aux")
-        third = None
-        if side is None or shared or not (mtl.closeness and mtl.window):
-            wplace = "aux"
         if side is not None:
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                aux_backward(("closeness", "window") if wplace == "aux" else ("closeness",))
-            if wplace == "third":
-                third = getattr(self._wgrad_exec(), "stream", None)
-                if third is None:
-                    wplace = "main"
-                else:
-                    third.wait_stream(cur)
-                    with torch.cuda.stream(third):
-                        aux_backward(("window",))
+                aux_backward()
         feat = pd["_feat"]
         g_feat = self.box_predictor.backward(pd["_bp"], d_cls,
                                              d["refined_box_encodings"].view(d_cls.shape[0], -1), feat)
         if g_feat_closeness is not None:
             ops.axpby(g_feat_closeness, g_feat, 1.0, 1.0)
-        if os.environ.get("MTLSSL_RFCN_TOWER_WGRAD_STREAM", "0") == "1" and getattr(self.tower, "supports_wgrad_stream", False):
-            # the main tower's filter gradients on the filter-gradient stream (joined at the end of backward)
-            g_F = self.tower.backward(g_feat, feat, pd["_tower_ctx"], need_input_grad=True, wgrad=self._wgrad_exec())
-        else:
-            g_F = self.tower.backward(g_feat, feat, pd["_tower_ctx"], need_input_grad=True)
+        g_F = self.tower.backward(g_feat, feat, pd["_tower_ctx"], need_input_grad=True)
         ops.axpby(g_F, dF, 1.0, 1.0)
         if side is None:
             aux_backward()
-        else:
-            if wplace == "main":
-                aux_backward(("window",))
-            if not stop:
-                ops.wait_on(side, "backward: aux stream", cur)
-                if third is not None:
-                    ops.wait_on(third, "backward: window tower on the third stream", cur)
+        elif not stop:
+            ops.wait_on(side, "backward: aux stream", cur)
         for g in held:
             g.record_stream(cur)            # produced on the second stream, consumed (and then released) on this one
             ops.axpby(g, dF, 1.0, 1.0)

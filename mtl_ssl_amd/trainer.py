@@ -326,7 +326,7 @@ class Trainer:
         self.split_loss = os.environ.get("MTLSSL_SPLIT_LOSS", "1") != "0" and self.ps.device.type == "cuda"
         # the momentum update is the gradient buffer's last reader of a step: it leaves zeros behind, which saves the
         # next step's memset launch over every parameter (the first step starts from ParamStore's zero-initialised buffer)
-        self.zero_in_update = os.environ.get("MTLSSL_ZERO_IN_UPDATE", "1") != "0" and self.ps.device.type == "cuda"
+        self.zero_in_update = self.ps.device.type == "cuda"
         self.max_steps_in_flight = int(os.environ.get("MTLSSL_MAX_STEPS_IN_FLIGHT", "2"))     # 0: unbounded (rounds 1-4)
         self._step_events = []
         # momentum update and shadow-weight fold in one launch: only when no SCALE vector trains — frozen BatchNorm, or a
@@ -344,9 +344,7 @@ class Trainer:
         self.update_order = []             # bucket ids in the order their slices were updated (diagnostics / tests)
         own = os.environ.get("MTLSSL_STEP_STREAM", "auto")
         use = (self.reducer.active if own == "auto" else own == "1") and self.ps.device.type == "cuda"
-        # MTLSSL_STEP_STREAM_PRIORITY: HIP priority of the step's own (main) stream when it has one (-1 = above the side streams)
-        self.step_stream = (torch.cuda.Stream(device=self.ps.device, priority=int(os.environ.get("MTLSSL_STEP_STREAM_PRIORITY", "0")))
-                            if use else None)
+        self.step_stream = torch.cuda.Stream(device=self.ps.device) if use else None
         # builders/optimizer_builder.py:105-111: tf.contrib.opt.MovingAverageOptimizer keeps an exponential
         # moving average of every variable beside it (the trainer's plain Saver stores both); decay as given.
         self.ema = None
@@ -408,7 +406,7 @@ class Trainer:
         m = self.model
         m.step = self.global_step
         self.provide(batch)
-        if not self.ps.grads_clean:          # the momentum update leaves zeros behind (MTLSSL_ZERO_IN_UPDATE, default on)
+        if not self.ps.grads_clean:          # the momentum update leaves zeros behind (zero_in_update)
             self.ps.grads.zero_()
         elif os.environ.get("MTLSSL_CHECK_GRADS_CLEAN") == "1":      # debug / test suite: the skipped memset was safe
             assert float(self.ps.grads.abs().max().item()) == 0.0, \

@@ -38,8 +38,7 @@ CONFIGS = (("frcnn_resnet101_coco_mtl.config", 600, 1024), ("rfcn_resnet101_voc_
            ("frcnn_mobilenet_v1_voc_mtl.config", 600, 1024), ("frcnn_inception_resnet_v2_coco_mtl.config", 800, 1333))
 LONG_SIDES, SHORT_MIN, SHORT_STEP = (500, 640), 160, 20
 LEVELS = 6                      # halvings of the frame looked at (the extractors stop at 4)
-PLANNING_SWITCHES = ("MTLSSL_FORCE_CFG", "MTLSSL_TAIL_SPLIT", "MTLSSL_FOLD_BASE_US", "MTLSSL_WINOGRAD", "MTLSSL_DGRAD_PARITY",
-                     "MTLSSL_STEM_S2D", "MTLSSL_PLAN_FILE", "MTLSSL_PLAN_DB", "MTLSSL_FP32_ENGINE")
+PLANNING_SWITCHES = ("MTLSSL_FORCE_CFG", "MTLSSL_WINOGRAD", "MTLSSL_PLAN_FILE", "MTLSSL_PLAN_DB", "MTLSSL_FP32_ENGINE")
 SIGNATURE_FIELDS = ("mode", "family", "code", "tile", "nsplit", "ragged_last_split", "tail", "tail_nsplit", "M_mod_BM",
                     "NG_mod_BN", "NG_mod_4", "pointwise", "stride", "wino_ragged_frame", "parity_classes")
 

@@ -47,10 +47,10 @@ def run(name, steps, main_priority=None, side_priority=None, free_per_xcd=0):
     model = model_builder.build(cfg.model, True, "cuda", seed=0)
     if free_per_xcd:
         model._aux_stream_obj = masked_stream(free_per_xcd)
-        model._wgrad_stream_obj = nn.WgradStream(masked_stream(free_per_xcd), group=False)
+        model._wgrad_stream_obj = nn.WgradStream(masked_stream(free_per_xcd))
     elif side_priority is not None:
         model._aux_stream_obj = torch.cuda.Stream(priority=side_priority)
-        model._wgrad_stream_obj = nn.WgradStream(torch.cuda.Stream(priority=side_priority), group=False)
+        model._wgrad_stream_obj = nn.WgradStream(torch.cuda.Stream(priority=side_priority))
     tr = trainer.Trainer(model, cfg.train_config, 1)
     ring = [tr.stage_batch(synthetic.make_batch(B, 600, 1024, K, seed=1234 + i, device="cuda")) for i in range(8)]
     main = torch.cuda.Stream(priority=main_priority) if main_priority is not None else torch.cuda.current_stream()
