@@ -75,7 +75,9 @@ typedef struct {
 
 /* Scratch needed by a call in the given mode (0 fwd, 1 dgrad, 2 wgrad); fwd/dgrad use it for
  * split-K partials when the tile grid alone would not fill the 256 CUs (0 when not split).
- * A null workspace is allowed for fwd/dgrad and simply disables split-K. */
+ * A null workspace is allowed for fwd/dgrad and disables everything that lives in one: Winograd, the input-parity
+ * dgrad, the zero-padded pointwise and space-to-depth forms (their problems run on the direct engine or a VALU
+ * fallback kernel instead), and the K split and K-split tail of a direct plan (an unsplit tile plan runs). */
 int64_t mtlssl_conv2d_workspace_bytes(const mtlssl_conv_desc* d, int mode);
 /* y = epilogue(conv(x, w)). */
 int mtlssl_conv2d_fwd(const mtlssl_conv_desc* d, const float* x, const float* w,

@@ -662,51 +662,19 @@ static Plan plan_gemm(int64_t M, int64_t NG, int taps, int kc, int tuned, double
   if (t_out) *t_out = best_t;
   return best;
 }
-// Direct-path plan of a fwd / dgrad problem, memoised per (problem, mode): every conv call asks two or
-// three times (workspace size, launch, profiler attribution) and the planner is a loop over tiles x splits.
-// The memo is cleared whenever the plan registry or the algorithm policy changes (plans_clear).
-struct DescKey {
-  mtlssl_conv_desc d; int mode;
-  bool operator==(const DescKey& o) const { return mode == o.mode && memcmp(&d, &o.d, sizeof(d)) == 0; }
-};
-struct DescHash {
-  size_t operator()(const DescKey& k) const {
-    uint64_t h = 1469598103934665603ull ^ (uint64_t)k.mode;
-    const int32_t* p = reinterpret_cast<const int32_t*>(&k.d);
-    for (size_t i = 0; i < sizeof(k.d) / 4; ++i) { h ^= (uint32_t)p[i]; h *= 1099511628211ull; }
-    return (size_t)h;
-  }
-};
-static DescKey desc_key(const mtlssl_conv_desc* d, int mode) {
-  DescKey k;
-  memset(&k, 0, sizeof(k));
-  k.d = *d; k.mode = mode;
-  k.d.ldy = 0;                   // plans do not depend on the row stride of y / dy
-  return k;
-}
-struct PlanMemo { Plan plan; double t; };
-static std::unordered_map<DescKey, PlanMemo, DescHash>& plan_map() {
-  static std::unordered_map<DescKey, PlanMemo, DescHash> m;
-  return m;
-}
-static std::mutex& memo_mutex() { static std::mutex m; return m; }
+// Direct-path plan of a fwd / dgrad problem on the tile engine (route() memoises it with the rest of the decision).
 static Plan plan_dir(const mtlssl_conv_desc* d, int mode, double* t_out = nullptr) {
-  const DescKey k = desc_key(d, mode);
-  {
-    std::lock_guard<std::mutex> g(memo_mutex());
-    auto it = plan_map().find(k);
-    if (it != plan_map().end()) { if (t_out) *t_out = it->second.t; return it->second.plan; }
-  }
   const int64_t M = mode == MODE_FWD ? (int64_t)d->N * d->OH * d->OW : (int64_t)d->N * d->H * d->W;
-  PlanMemo pm;
-  pm.plan = plan_gemm(M, mode == MODE_FWD ? d->K : d->C, d->R * d->S, mode == MODE_FWD ? d->C : d->K,
-                      tuned_direct_tile(d, mode), &pm.t, desc_is_pointwise(d));
-  {
-    std::lock_guard<std::mutex> g(memo_mutex());
-    plan_map()[k] = pm;
+  return plan_gemm(M, mode == MODE_FWD ? d->K : d->C, d->R * d->S, mode == MODE_FWD ? d->C : d->K,
+                   tuned_direct_tile(d, mode), t_out, desc_is_pointwise(d));
+}
+// workspace bytes of a fwd / dgrad plan's K-split partials (whole matrix, or the tail rows only)
+static int64_t split_bytes(const Plan& pl, int64_t M, int64_t NG) {
+  if (pl.tail_rows > 0) {
+    const int64_t m_tail0 = (cdiv(M, CFG_BM[pl.cfg]) - pl.tail_rows) * CFG_BM[pl.cfg];
+    return align_up((M - m_tail0) * NG * 4 * pl.tail_nsplit, 256);
   }
-  if (t_out) *t_out = pm.t;
-  return pm.plan;
+  return pl.nsplit > 1 ? align_up(M * NG * 4 * pl.nsplit, 256) : 0;
 }
 
 static bool is_pointwise(const mtlssl_conv_desc* d) {
@@ -725,19 +693,11 @@ static mtlssl_conv_desc padded_desc(const mtlssl_conv_desc* d) {
   q.K = (int)align_up(d->K, BK);
   return q;
 }
-static int64_t padded_dgrad_bytes(const mtlssl_conv_desc* d) {
-  const int64_t Kp = align_up(d->K, BK), M = (int64_t)d->N * d->H * d->W;
-  return align_up(M * Kp * 4, 256) + align_up((int64_t)d->C * Kp * 4, 256);
-}
 // The same for a pointwise forward whose input width C is not a multiple of 16 (the refiner's first FC layer reads the
 // tower features concatenated with the expanded class predictions): x -> [M, Cp] with zero columns, w -> [Cp, K] with
 // zero rows.
 static bool padded_fwd_ok(const mtlssl_conv_desc* d) {
   return is_pointwise(d) && d->C % BK != 0 && d->C >= 32 && d->K >= 16;
-}
-static int64_t padded_fwd_bytes(const mtlssl_conv_desc* d) {
-  const int64_t Cp = align_up(d->C, BK), M = (int64_t)d->N * d->H * d->W;
-  return align_up(M * Cp * 4, 256) + align_up(Cp * d->K * 4, 256);
 }
 // Pointwise wgrad whose output width K is not a multiple of 4 (R-FCN's 189-wide position-sensitive class map,
 // core/box_predictor.py:215-337: 21 classes x 9 bins): dy [P, K] is copied into a zero-padded [P, Kp] image (Kp = K
@@ -840,10 +800,6 @@ static mtlssl_conv_desc s2d_desc(const mtlssl_conv_desc* d) {
   q.H = d->OH + q.R - 1; q.W = d->OW + q.S - 1;
   q.C = BK; q.stride = 1; q.dilation = 1; q.pad_t = 0; q.pad_l = 0;
   return q;
-}
-static int64_t s2d_bytes(const mtlssl_conv_desc* d) {
-  const mtlssl_conv_desc q = s2d_desc(d);
-  return align_up((int64_t)q.N * q.H * q.W * q.C * 4, 256) + align_up((int64_t)q.R * q.S * q.C * q.K * 4, 256);
 }
 // one thread per (pixel of X', 2x2 phase): writes C (<= 4) channels; phase 0 also clears the channels 4C..15
 __global__ void __launch_bounds__(256) k_s2d_pack(const float* __restrict__ x, int N, int H, int W, int C, int pt, int pl,
@@ -1007,11 +963,12 @@ static void launch_planned(const Plan& pl, ConvArgs& p, float* ws, hipStream_t s
   hipLaunchKernelGGL(k_splitk_epilogue<MODE>, dim3(cdiv((int64_t)f.M * f.NG / 4, 256)), dim3(256), 0, st, f);
 }
 
-static void wgrad_plan_uncached(const mtlssl_conv_desc* d, int* cfg, int* nsplit, int* pps, double* t_out) {
+struct WgradPlan { int cfg, nsplit, pps; };
+static WgradPlan wgrad_plan(const mtlssl_conv_desc* d, double* t_out = nullptr) {
   int64_t P = (int64_t)d->N * d->OH * d->OW;
   int RS = d->R * d->S;
   double best_t = 1e30;
-  *cfg = 2; *nsplit = 1; *pps = (int)align_up(P, 16);
+  WgradPlan best{2, 1, (int)align_up(P, 16)};
   const int force = tuned_direct_tile(d, MODE_WGRAD);
   for (int c = 0; c < NTILE; ++c) {
     if (force >= 0 ? c != force : c >= NCFG) continue;
@@ -1026,33 +983,11 @@ static void wgrad_plan_uncached(const mtlssl_conv_desc* d, int* cfg, int* nsplit
       // partial tiles written + read once by the fold kernel
       double t = tile_time_us(c, tiles * ns, per, desc_is_pointwise(d)) +
                  2.0 + (double)RS * d->C * d->K * 4.0 * (ns + 1) / 3.0e6;
-      if (t < best_t) { best_t = t; *cfg = c; *nsplit = ns; *pps = per * bk; }
+      if (t < best_t) { best_t = t; best = WgradPlan{c, ns, per * bk}; }
     }
   }
   if (t_out) *t_out = best_t;
-}
-
-struct WgradMemo { int cfg, ns, pps; double t; };
-static std::unordered_map<DescKey, WgradMemo, DescHash>& wgrad_map() {
-  static std::unordered_map<DescKey, WgradMemo, DescHash> m;
-  return m;
-}
-static void wgrad_plan(const mtlssl_conv_desc* d, int* cfg, int* nsplit, int* pps, double* t_out = nullptr) {
-  const DescKey k = desc_key(d, MODE_WGRAD);
-  WgradMemo w;
-  bool hit = false;
-  {
-    std::lock_guard<std::mutex> g(memo_mutex());
-    auto it = wgrad_map().find(k);
-    if (it != wgrad_map().end()) { w = it->second; hit = true; }
-  }
-  if (!hit) {
-    wgrad_plan_uncached(d, &w.cfg, &w.ns, &w.pps, &w.t);
-    std::lock_guard<std::mutex> g(memo_mutex());
-    wgrad_map()[k] = w;
-  }
-  *cfg = w.cfg; *nsplit = w.ns; *pps = w.pps;
-  if (t_out) *t_out = w.t;
+  return best;
 }
 
 // Direct or Winograd? MTLSSL_WINOGRAD / mtlssl_conv2d_set_winograd: 0 never, 1 (default) by the plan
@@ -1088,10 +1023,10 @@ static int wino_env() {
   }
   return v;
 }
-static bool choose_wino_uncached(const mtlssl_conv_desc* d, int mode, WinoChoice* wc) {
+// `t_direct`: the time model's figure for the direct plan of an MFMA-eligible (d, mode)
+static bool choose_wino(const mtlssl_conv_desc* d, int mode, double t_direct, WinoChoice* wc) {
   const int env = wino_env();
   if (env == 0 || !wino_eligible(d, WINO_F43)) return false;     // F43's domain contains M7's
-  if (mode == MODE_FWD ? !mfma_fwd_ok(d) : (mode == MODE_DGRAD ? !mfma_dgrad_ok(d) : !mfma_wgrad_ok(d))) return false;
   const int force = tuned_cfg(d, mode);
   if (code_alg(force) >= 1) {
     const int variant = code_alg(force) - 1, tile = code_tile(force);
@@ -1106,41 +1041,7 @@ static bool choose_wino_uncached(const mtlssl_conv_desc* d, int mode, WinoChoice
   }
   if (env == 2) return true;
   if (code_alg(force) == 0) return false;
-  double td;
-  if (mode == MODE_WGRAD) { int c, ns, pps; wgrad_plan(d, &c, &ns, &pps, &td); }
-  else plan_dir(d, mode, &td);
-  return tw < td;
-}
-
-// Memo of the direct-vs-Winograd decisions (same life cycle as the plan memo).
-struct Decision { bool wino; WinoChoice wc; };
-static std::unordered_map<DescKey, Decision, DescHash>& decision_map() {
-  static std::unordered_map<DescKey, Decision, DescHash> m;
-  return m;
-}
-static void plans_clear() {
-  std::lock_guard<std::mutex> g(memo_mutex());
-  decision_map().clear();
-  plan_map().clear();
-  wgrad_map().clear();
-}
-static bool choose_wino(const mtlssl_conv_desc* d, int mode, WinoChoice* wc) {
-  if (!(d->R == 3 && d->S == 3 && d->stride == 1)) return false;       // cheap reject: most layers are 1x1
-  const DescKey k = desc_key(d, mode);
-  {
-    std::lock_guard<std::mutex> g(memo_mutex());
-    auto it = decision_map().find(k);
-    if (it != decision_map().end()) { *wc = it->second.wc; return it->second.wino; }
-  }
-  Decision dec;
-  dec.wc = WinoChoice{0, 0};
-  dec.wino = choose_wino_uncached(d, mode, &dec.wc);
-  {
-    std::lock_guard<std::mutex> g(memo_mutex());
-    decision_map()[k] = dec;
-  }
-  *wc = dec.wc;
-  return dec.wino;
+  return tw < t_direct;
 }
 
 // ---- stride-2 dgrad by input parity. dX[ih][iw] only receives the taps r with (ih + pt - r) even, so
@@ -1194,36 +1095,184 @@ __global__ void k_parity_scatter(const float* tmp, float* dx, const float* resid
   }
   reinterpret_cast<floatx4*>(dx)[o] = val;
 }
-static Plan parity_plan(const mtlssl_conv_desc* d, const ParityProblem& q) {
-  return plan_gemm((int64_t)d->N * q.Hs * q.Ws, d->C, q.Rs * q.Ss, d->K, tuned_direct_tile(d, MODE_DGRAD));
+
+// ------------------------------------------------------------------------------ the plan resolver
+// Which kernel family serves (descriptor, mode), and with what plan: decided here and nowhere else. The workspace
+// queries, the plan queries and the three launchers below all read a Route; DESIGN.md "Conv plan resolution" lists the
+// families in the order resolve() tries them.
+enum Family {
+  FAM_WINO,         // Winograd F43 / M7 (wc)
+  FAM_DIRECT,       // the tile engine on the problem as given
+  FAM_PARITY,       // stride-2 dgrad as four stride-1 problems by input parity
+  FAM_PADDED,       // pointwise problem, reduction (wgrad: output) width zero-padded in the workspace
+  FAM_S2D,          // stride-2 stem forward on the space-to-depth image
+  FAM_THIN,         // k_pw_thin_fwd
+  FAM_GEMM_SMALL,   // k_gemm_small
+  FAM_STEM_FWD,     // k_conv_smallc_fwd; bias / ReLU epilogues only (stem_fwd_family refines at launch)
+  FAM_STEM3_WGRAD,  // k_conv_stem_wgrad<3, 3, 3>
+  FAM_SCALAR,       // k_conv_direct_*
+};
+struct Route {
+  int family;
+  WinoChoice wc;
+  mtlssl_conv_desc q;            // what the tile engine runs: the problem itself, its channel-padded or its space-to-depth form
+  Plan plan;                     // fwd / dgrad: plan of q. FAM_PARITY / FAM_WINO: the direct plan of the problem as given
+  WgradPlan wg;                  // wgrad: plan of q; FAM_GEMM_SMALL (split, rows per split), FAM_STEM3_WGRAD (chunks, pixels per chunk)
+  int split_ns, split_pps;       // wgrad FAM_DIRECT: the split engine's plan, 0 = not its problem (wgrad_on_split_engine)
+  Plan parity[4];                // FAM_PARITY: plan of each class that has taps
+  int64_t front_a, front_bytes;  // packed operands at the front of the workspace: the first one, all of them
+  int64_t bytes;                 // whole workspace (wgrad: behind the column-sum region, colsum_bytes)
+};
+static inline int64_t colsum_bytes(const mtlssl_conv_desc* d) { return align_up((int64_t)COLSUM_MAX_PARTS * d->K * 4, 256); }
+// wgrad partials [split][R*S][C][K] of `d`; the split engine may be switched on between the size query and the call, so
+// the larger of the two engines' split counts is what gets sized
+static int64_t wgrad_partial_bytes(const mtlssl_conv_desc* d, int ns, int* split_ns, int* split_pps) {
+  if (!split_wgrad_plan((int64_t)d->N * d->OH * d->OW, d->C, d->K, d->R * d->S, split_ns, split_pps)) *split_ns = *split_pps = 0;
+  if (*split_ns > ns) ns = *split_ns;
+  return align_up((int64_t)ns * d->R * d->S * d->C * d->K * 4, 256);
 }
-static int64_t parity_split_bytes(const mtlssl_conv_desc* d, const ParityProblem& q) {
-  if (q.Rs == 0 || q.Ss == 0) return 0;
-  Plan pl = parity_plan(d, q);
-  const int64_t M = (int64_t)d->N * q.Hs * q.Ws;
-  if (pl.tail_rows > 0) {
-    int64_t m_tail0 = (cdiv(M, CFG_BM[pl.cfg]) - pl.tail_rows) * CFG_BM[pl.cfg];
-    return align_up((M - m_tail0) * d->C * 4 * pl.tail_nsplit, 256);
+static bool wgrad_on_split_engine(const Route& r, const mtlssl_conv_desc* d) {
+  return fp32_engine() == 1 && (r.wg.cfg == 0 || r.wg.cfg == 3) && desc_dense(d) && r.split_ns > 0;
+}
+// the small-C stem kernel has no residual / ReLU6 / tanh epilogue: those calls take the scalar kernel
+static inline int stem_fwd_family(int epi) { return (epi & ~(MTLSSL_EPI_BIAS | MTLSSL_EPI_RELU)) ? FAM_SCALAR : FAM_STEM_FWD; }
+
+static void resolve_wgrad(const mtlssl_conv_desc* d, Route* r) {
+  const int64_t P = (int64_t)d->N * d->OH * d->OW;
+  int ns, pps;
+  if (mfma_wgrad_ok(d)) {
+    double t;
+    r->wg = wgrad_plan(d, &t);
+    if (choose_wino(d, MODE_WGRAD, t, &r->wc)) {
+      r->family = FAM_WINO;
+      r->bytes = wino_workspace_bytes(d, r->wc.variant, MODE_WGRAD);
+    } else {
+      r->family = FAM_DIRECT;
+      r->bytes = wgrad_partial_bytes(d, r->wg.nsplit, &r->split_ns, &r->split_pps);
+    }
+  } else if (padded_wgrad_ok(d)) {
+    r->family = FAM_PADDED;
+    r->q = padded_wgrad_desc(d);
+    r->wg = wgrad_plan(&r->q);
+    r->front_a = r->front_bytes = align_up(P * r->q.K * 4, 256);
+    r->bytes = r->front_bytes + wgrad_partial_bytes(&r->q, r->wg.nsplit, &ns, &pps);   // sized for both engines, runs on the native one
+  } else if (is_pointwise(d)) {
+    r->family = FAM_GEMM_SMALL;
+    small_wgrad_plan(d, &r->wg.nsplit, &r->wg.pps);
+    r->bytes = align_up((int64_t)r->wg.nsplit * d->C * d->K * 4, 256);
+  } else if (is_stem3(d)) {
+    r->family = FAM_STEM3_WGRAD;
+    stem_plan(d, &r->wg.nsplit, &r->wg.pps);
+    r->bytes = align_up((int64_t)STEM_MAX_CHUNKS * 27 * d->K * 4, 256);
+  } else {
+    r->family = FAM_SCALAR;
   }
-  return pl.nsplit > 1 ? align_up(M * d->C * 4 * pl.nsplit, 256) : 0;
 }
-// workspace: [sub-filter: R*S*C*K floats][compact result of one class][split-K partials of one class]
-static int64_t parity_workspace_bytes(const mtlssl_conv_desc* d) {
-  int64_t wsub = align_up((int64_t)d->R * d->S * d->C * d->K * 4, 256);
-  int64_t tmp = align_up((int64_t)d->N * ((d->H + 1) / 2) * ((d->W + 1) / 2) * d->C * 4, 256);
-  int64_t split = 0;
-  for (int c = 0; c < 4; ++c) {
-    int64_t b = parity_split_bytes(d, parity_problem(d, c >> 1, c & 1));
-    if (b > split) split = b;
+// `ws` false: the call has no workspace, so the families that pack operands or keep partials there are not available
+static Route resolve(const mtlssl_conv_desc* d, int mode, bool ws) {
+  Route r;
+  memset(&r, 0, sizeof(r));
+  r.q = *d;
+  if (mode == MODE_WGRAD) { resolve_wgrad(d, &r); return r; }
+  const bool fwd = mode == MODE_FWD;
+  const int64_t M = fwd ? (int64_t)d->N * d->OH * d->OW : (int64_t)d->N * d->H * d->W, NG = fwd ? d->K : d->C;
+  if (fwd ? mfma_fwd_ok(d) : mfma_dgrad_ok(d)) {
+    double t;
+    r.plan = plan_dir(d, mode, &t);
+    if (ws && choose_wino(d, mode, t, &r.wc)) {
+      r.family = FAM_WINO;
+      r.bytes = wino_workspace_bytes(d, r.wc.variant, mode);
+    } else if (ws && !fwd && parity_ok(d)) {
+      // workspace: [sub-filter: R*S*C*K floats][compact result of one class][split-K partials of one class]
+      r.family = FAM_PARITY;
+      r.front_a = align_up((int64_t)d->R * d->S * d->C * d->K * 4, 256);
+      r.front_bytes = r.front_a + align_up((int64_t)d->N * ((d->H + 1) / 2) * ((d->W + 1) / 2) * d->C * 4, 256);
+      int64_t split = 0;
+      for (int c = 0; c < 4; ++c) {
+        const ParityProblem q = parity_problem(d, c >> 1, c & 1);
+        if (q.Rs == 0 || q.Ss == 0) continue;
+        r.parity[c] = plan_gemm((int64_t)d->N * q.Hs * q.Ws, d->C, q.Rs * q.Ss, d->K, tuned_direct_tile(d, MODE_DGRAD));
+        const int64_t b = split_bytes(r.parity[c], (int64_t)d->N * q.Hs * q.Ws, d->C);
+        if (b > split) split = b;
+      }
+      r.bytes = r.front_bytes + split;
+    } else {
+      r.family = FAM_DIRECT;
+      if (!ws && (r.plan.nsplit > 1 || r.plan.tail_rows > 0)) r.plan = Plan{pick_tile(M, NG, 1), 1, 0, 0, 1, 0};
+      r.bytes = split_bytes(r.plan, M, NG);
+    }
+    return r;
   }
-  return wsub + tmp + split;
+  if (ws && (fwd ? padded_fwd_ok(d) : padded_dgrad_ok(d))) {
+    r.family = FAM_PADDED;
+    if (fwd) r.q.C = (int)align_up(d->C, BK); else r.q = padded_desc(d);
+    r.front_a = align_up(M * (fwd ? r.q.C : r.q.K) * 4, 256);
+    r.front_bytes = r.front_a + align_up((int64_t)r.q.C * r.q.K * 4, 256);
+  } else if (fwd && thin_fwd_ok(d)) {
+    r.family = FAM_THIN;
+  } else if (is_pointwise(d)) {
+    r.family = FAM_GEMM_SMALL;
+  } else if (ws && fwd && s2d_fwd_ok(d)) {
+    r.family = FAM_S2D;
+    r.q = s2d_desc(d);
+    r.front_a = align_up((int64_t)r.q.N * r.q.H * r.q.W * r.q.C * 4, 256);
+    r.front_bytes = r.front_a + align_up((int64_t)r.q.R * r.q.S * r.q.C * r.q.K * 4, 256);
+  } else if (fwd && d->K == 64 && d->C <= 4 && stem_lds_bytes(d) <= 160 * 1024) {
+    r.family = FAM_STEM_FWD;
+  } else {
+    r.family = FAM_SCALAR;
+  }
+  if (r.family == FAM_PADDED || r.family == FAM_S2D) {
+    r.plan = plan_dir(&r.q, mode);
+    r.bytes = r.front_bytes + split_bytes(r.plan, M, NG);
+  }
+  return r;
 }
-static void parity_dgrad(const mtlssl_conv_desc* d, const float* dy, const float* w, const float* residual,
+
+// One memo for the whole decision, per (descriptor, mode, workspace or none); cleared whenever the plan registry or the
+// algorithm policy changes (routes_clear).
+struct DescKey {
+  mtlssl_conv_desc d; int mode;
+  bool operator==(const DescKey& o) const { return mode == o.mode && memcmp(&d, &o.d, sizeof(d)) == 0; }
+};
+struct DescHash {
+  size_t operator()(const DescKey& k) const {
+    uint64_t h = 1469598103934665603ull ^ (uint64_t)k.mode;
+    const int32_t* p = reinterpret_cast<const int32_t*>(&k.d);
+    for (size_t i = 0; i < sizeof(k.d) / 4; ++i) { h ^= (uint32_t)p[i]; h *= 1099511628211ull; }
+    return (size_t)h;
+  }
+};
+static std::unordered_map<DescKey, Route, DescHash>& route_map() {
+  static std::unordered_map<DescKey, Route, DescHash> m;
+  return m;
+}
+static std::mutex& memo_mutex() { static std::mutex m; return m; }
+static void routes_clear() {
+  std::lock_guard<std::mutex> g(memo_mutex());
+  route_map().clear();
+}
+static Route route(const mtlssl_conv_desc* d, int mode, bool have_workspace = true) {
+  DescKey k;
+  memset(&k, 0, sizeof(k));
+  k.d = *d; k.mode = have_workspace ? mode : mode + 4;
+  {
+    std::lock_guard<std::mutex> g(memo_mutex());
+    auto it = route_map().find(k);
+    if (it != route_map().end()) return it->second;
+  }
+  const Route r = resolve(d, mode, have_workspace);
+  std::lock_guard<std::mutex> g(memo_mutex());
+  route_map()[k] = r;
+  return r;
+}
+
+static void parity_dgrad(const Route& r, const mtlssl_conv_desc* d, const float* dy, const float* w, const float* residual,
                          const float* mask_ref, float* dx, int epi, void* workspace, hipStream_t st) {
   const int64_t CK = (int64_t)d->C * d->K;
   float* wsub = (float*)workspace;
-  float* tmp = (float*)((char*)wsub + align_up((int64_t)d->R * d->S * CK * 4, 256));
-  float* split = (float*)((char*)tmp + align_up((int64_t)d->N * ((d->H + 1) / 2) * ((d->W + 1) / 2) * d->C * 4, 256));
+  float* tmp = (float*)((char*)workspace + r.front_a);
+  float* split = (float*)((char*)workspace + r.front_bytes);
   for (int c = 0; c < 4; ++c) {
     ParityProblem q = parity_problem(d, c >> 1, c & 1);
     if (q.Hs == 0 || q.Ws == 0) continue;
@@ -1241,12 +1290,24 @@ static void parity_dgrad(const mtlssl_conv_desc* d, const float* dy, const float
       p.a_bytes = ydy_bytes(d);
       p.b_bytes = (unsigned)((int64_t)q.Rs * q.Ss * CK * 4);
       p.M = (int)M; p.NG = d->C;
-      launch_planned<MODE_DGRAD>(parity_plan(d, q), p, split, st);
+      launch_planned<MODE_DGRAD>(r.parity[c], p, split, st);
     }
     const int64_t total4 = M * d->C / 4;
     hipLaunchKernelGGL(k_parity_scatter, dim3(cdiv(total4, 256)), dim3(256), 0, st, taps ? (const float*)tmp : nullptr,
                        dx, residual, mask_ref, epi, d->H, d->W, d->C / 4, q.Hs, q.Ws, q.py, q.px, total4);
   }
+}
+// The packed form r.q of a padded / space-to-depth problem on the tile engine: operands a, b at the front of the
+// workspace, the caller's epilogue.
+template <int MODE>
+static void launch_packed(const Route& r, const ConvArgs& p, const float* a, const float* b, void* workspace, hipStream_t st) {
+  const mtlssl_conv_desc& q = r.q;
+  ConvArgs pq = make_args(&q);
+  pq.a = a; pq.b = b; pq.out = p.out; pq.bias = p.bias; pq.residual = p.residual; pq.mask = p.mask; pq.epi = p.epi;
+  pq.a_bytes = (unsigned)((MODE == MODE_FWD ? (int64_t)q.N * q.H * q.W * q.C : (int64_t)q.N * q.OH * q.OW * q.K) * 4);
+  pq.b_bytes = (unsigned)((int64_t)q.R * q.S * q.C * q.K * 4);
+  pq.M = p.M; pq.NG = p.NG;
+  launch_planned<MODE>(r.plan, pq, (float*)((char*)workspace + r.front_bytes), st);
 }
 
 }  // namespace mtlssl
@@ -1256,44 +1317,20 @@ using namespace mtlssl;
 extern "C" {
 
 int64_t mtlssl_conv2d_workspace_bytes(const mtlssl_conv_desc* d, int mode) {
-  if (!d) return 0;
+  if (!d || mode < MODE_FWD || mode > MODE_WGRAD) return 0;            // no check_desc here: callers size before they validate
   if (mode == MODE_WGRAD) return mtlssl_conv2d_wgrad_workspace_bytes(d);
-  int64_t M = mode == MODE_FWD ? (int64_t)d->N * d->OH * d->OW : (int64_t)d->N * d->H * d->W;
-  int64_t NG = mode == MODE_FWD ? d->K : d->C;
-  if (mode == MODE_FWD && !mfma_fwd_ok(d) && padded_fwd_ok(d)) {
-    mtlssl_conv_desc q = *d;
-    q.C = (int)align_up(d->C, BK);
-    return padded_fwd_bytes(d) + mtlssl_conv2d_workspace_bytes(&q, MODE_FWD);
-  }
-  if (mode == MODE_DGRAD && !mfma_dgrad_ok(d) && padded_dgrad_ok(d)) {
-    const mtlssl_conv_desc q = padded_desc(d);
-    return padded_dgrad_bytes(d) + mtlssl_conv2d_workspace_bytes(&q, MODE_DGRAD);
-  }
-  if (mode == MODE_FWD && !mfma_fwd_ok(d) && s2d_fwd_ok(d)) {
-    const mtlssl_conv_desc q = s2d_desc(d);
-    return s2d_bytes(d) + mtlssl_conv2d_workspace_bytes(&q, MODE_FWD);
-  }
-  if (!(mode == MODE_FWD ? mfma_fwd_ok(d) : mfma_dgrad_ok(d))) return 0;
-  WinoChoice wc;
-  if (choose_wino(d, mode, &wc)) return wino_workspace_bytes(d, wc.variant, mode);
-  if (mode == MODE_DGRAD && parity_ok(d)) return parity_workspace_bytes(d);
-  Plan pl = plan_dir(d, mode);
-  if (pl.tail_rows > 0) {
-    int64_t m_tail0 = (cdiv(M, CFG_BM[pl.cfg]) - pl.tail_rows) * CFG_BM[pl.cfg];
-    return align_up((M - m_tail0) * NG * 4 * pl.tail_nsplit, 256);
-  }
-  return pl.nsplit > 1 ? align_up(M * NG * 4 * pl.nsplit, 256) : 0;
+  return route(d, mode).bytes;
 }
 
 int64_t mtlssl_conv2d_filter_xf_bytes(const mtlssl_conv_desc* d, int mode) {
   if (!d || (mode != MODE_FWD && mode != MODE_DGRAD) || check_desc(d)) return 0;
-  WinoChoice wc;
-  return choose_wino(d, mode, &wc) ? wino_filter_bytes(d, wc.variant) : 0;
+  const Route r = route(d, mode);
+  return r.family == FAM_WINO ? wino_filter_bytes(d, r.wc.variant) : 0;
 }
 int mtlssl_conv2d_filter_xf_variant(const mtlssl_conv_desc* d, int mode) {
-  WinoChoice wc;
-  if (!d || mode < MODE_FWD || mode > MODE_WGRAD || check_desc(d) || !choose_wino(d, mode, &wc)) return -1;
-  return wc.variant;
+  if (!d || mode < MODE_FWD || mode > MODE_WGRAD || check_desc(d)) return -1;
+  const Route r = route(d, mode);
+  return r.family == FAM_WINO ? r.wc.variant : -1;
 }
 int64_t mtlssl_conv2d_input_xf_bytes(const mtlssl_conv_desc* d, int variant) {
   if (!d || check_desc(d) || variant < 0 || variant >= WINO_VARIANTS || !wino_eligible(d, variant)) return 0;
@@ -1343,64 +1380,52 @@ int mtlssl_conv2d_fwd_keep(const mtlssl_conv_desc* d, const float* x, const floa
   p.b_bytes = (unsigned)((int64_t)d->R * d->S * d->C * d->K * 4);
   p.M = d->N * d->OH * d->OW;
   p.NG = d->K;
-  const bool dense = desc_dense(d);
-  WinoChoice wc;
-  MTLSSL_REQUIRE(dense || mfma_fwd_ok(d), "conv_fwd: a strided output (ldy = %d) needs C %% 16 == 0 and K >= 16", d->ldy);
-  if (workspace && choose_wino(d, MODE_FWD, &wc)) {
-    wino_fwd(d, wc.variant, wc.tile, x, w, bias, residual, y, epi, workspace, S(stream),
-             (filter_xf && xf_variant == wc.variant) ? filter_xf : nullptr,
-             (input_xf && input_variant == wc.variant) ? input_xf : nullptr);
-  } else if (mfma_fwd_ok(d)) {
-    Plan pl = plan_dir(d, MODE_FWD);
-    if ((pl.nsplit > 1 || pl.tail_rows > 0) && !workspace) pl = Plan{pick_tile(p.M, p.NG, 1), 1, 0, 0, 1, 0};
-    launch_planned<MODE_FWD>(pl, p, (float*)workspace, S(stream));
-  } else if (workspace && padded_fwd_ok(d)) {
-    mtlssl_conv_desc q = *d;
-    q.C = (int)align_up(d->C, BK);
-    const int64_t M = p.M;
-    float* x_pad = (float*)workspace;
-    float* w_pad = (float*)((char*)workspace + align_up(M * q.C * 4, 256));
-    void* ws_conv = (char*)workspace + padded_fwd_bytes(d);
-    hipLaunchKernelGGL(k_pad_rows, dim3(cdiv(M * q.C, 256)), dim3(256), 0, S(stream), x, M, d->C, q.C, x_pad);
-    (void)hipMemcpyAsync(w_pad, w, (size_t)d->C * d->K * 4, hipMemcpyDeviceToDevice, S(stream));
-    (void)hipMemsetAsync(w_pad + (int64_t)d->C * d->K, 0, (size_t)(q.C - d->C) * d->K * 4, S(stream));
-    ConvArgs pq = make_args(&q);
-    pq.a = x_pad; pq.b = w_pad; pq.out = y; pq.bias = bias; pq.residual = residual; pq.epi = epi;
-    pq.a_bytes = (unsigned)(M * q.C * 4);
-    pq.b_bytes = (unsigned)((int64_t)q.C * q.K * 4);
-    pq.M = (int)M;
-    pq.NG = q.K;
-    Plan pl = plan_dir(&q, MODE_FWD);
-    launch_planned<MODE_FWD>(pl, pq, (float*)ws_conv, S(stream));
-  } else if (thin_fwd_ok(d)) {
-    hipLaunchKernelGGL(k_pw_thin_fwd, dim3(cdiv(p.M, 4)), dim3(256), 0, S(stream), x, w, bias, residual, y, p.M, d->C, d->K, epi);
-  } else if (is_pointwise(d)) {
-    GemmArgs g{x, w, y, bias, residual, nullptr, p.M, d->K, d->C, epi, 0};
-    hipLaunchKernelGGL(k_gemm_small<GM_FWD>, dim3(cdiv(g.N, 64), cdiv(g.M, 64)), dim3(256), 0, S(stream), g);
-  } else if (workspace && s2d_fwd_ok(d)) {
-    const mtlssl_conv_desc q = s2d_desc(d);
-    float* xs = (float*)workspace;
-    float* wsf = (float*)((char*)workspace + align_up((int64_t)q.N * q.H * q.W * q.C * 4, 256));
-    void* ws_conv = (char*)workspace + s2d_bytes(d);
-    hipLaunchKernelGGL(k_s2d_pack, dim3(cdiv((int64_t)q.N * q.H * q.W * 4, 256)), dim3(256), 0, S(stream), x, d->N, d->H, d->W,
-                       d->C, d->pad_t, d->pad_l, q.H, q.W, xs);
-    hipLaunchKernelGGL(k_s2d_filter, dim3(cdiv((int64_t)q.R * q.S * q.C * q.K, 256)), dim3(256), 0, S(stream), w, d->R, d->S,
-                       d->C, d->K, q.R, q.S, wsf);
-    ConvArgs pq = make_args(&q);
-    pq.a = xs; pq.b = wsf; pq.out = y; pq.bias = bias; pq.residual = residual; pq.epi = epi;
-    pq.a_bytes = (unsigned)((int64_t)q.N * q.H * q.W * q.C * 4);
-    pq.b_bytes = (unsigned)((int64_t)q.R * q.S * q.C * q.K * 4);
-    pq.M = p.M;
-    pq.NG = q.K;
-    Plan pl = plan_dir(&q, MODE_FWD);
-    launch_planned<MODE_FWD>(pl, pq, (float*)ws_conv, S(stream));
-  } else if (d->K == 64 && d->C <= 4 && !(epi & ~(MTLSSL_EPI_BIAS | MTLSSL_EPI_RELU)) &&
-             stem_lds_bytes(d) <= 160 * 1024) {
-    dim3 grid(cdiv(d->OW, STEM_T), cdiv(d->OH, STEM_T), d->N);
-    hipLaunchKernelGGL(k_conv_smallc_fwd, grid, dim3(256), stem_lds_bytes(d), S(stream), p);
-  } else {
-    int64_t total = (int64_t)p.M * p.K;
-    hipLaunchKernelGGL(k_conv_direct_fwd, dim3(cdiv(total, 256)), dim3(256), 0, S(stream), p);
+  MTLSSL_REQUIRE(desc_dense(d) || mfma_fwd_ok(d), "conv_fwd: a strided output (ldy = %d) needs C %% 16 == 0 and K >= 16", d->ldy);
+  const Route r = route(d, MODE_FWD, workspace != nullptr);
+  const mtlssl_conv_desc& q = r.q;
+  switch (r.family == FAM_STEM_FWD ? stem_fwd_family(epi) : r.family) {
+    case FAM_WINO:
+      wino_fwd(d, r.wc.variant, r.wc.tile, x, w, bias, residual, y, epi, workspace, S(stream),
+               (filter_xf && xf_variant == r.wc.variant) ? filter_xf : nullptr,
+               (input_xf && input_variant == r.wc.variant) ? input_xf : nullptr);
+      break;
+    case FAM_DIRECT:
+      launch_planned<MODE_FWD>(r.plan, p, (float*)workspace, S(stream));
+      break;
+    case FAM_PADDED: {        // x -> [M, Cp] with zero columns, w -> [Cp, K] with zero rows
+      float* x_pad = (float*)workspace;
+      float* w_pad = (float*)((char*)workspace + r.front_a);
+      hipLaunchKernelGGL(k_pad_rows, dim3(cdiv((int64_t)p.M * q.C, 256)), dim3(256), 0, S(stream), x, (int64_t)p.M, d->C, q.C, x_pad);
+      (void)hipMemcpyAsync(w_pad, w, (size_t)d->C * d->K * 4, hipMemcpyDeviceToDevice, S(stream));
+      (void)hipMemsetAsync(w_pad + (int64_t)d->C * d->K, 0, (size_t)(q.C - d->C) * d->K * 4, S(stream));
+      launch_packed<MODE_FWD>(r, p, x_pad, w_pad, workspace, S(stream));
+      break;
+    }
+    case FAM_THIN:
+      hipLaunchKernelGGL(k_pw_thin_fwd, dim3(cdiv(p.M, 4)), dim3(256), 0, S(stream), x, w, bias, residual, y, p.M, d->C, d->K, epi);
+      break;
+    case FAM_GEMM_SMALL: {
+      GemmArgs g{x, w, y, bias, residual, nullptr, p.M, d->K, d->C, epi, 0};
+      hipLaunchKernelGGL(k_gemm_small<GM_FWD>, dim3(cdiv(g.N, 64), cdiv(g.M, 64)), dim3(256), 0, S(stream), g);
+      break;
+    }
+    case FAM_S2D: {
+      float* xs = (float*)workspace;
+      float* wsf = (float*)((char*)workspace + r.front_a);
+      hipLaunchKernelGGL(k_s2d_pack, dim3(cdiv((int64_t)q.N * q.H * q.W * 4, 256)), dim3(256), 0, S(stream), x, d->N, d->H, d->W,
+                         d->C, d->pad_t, d->pad_l, q.H, q.W, xs);
+      hipLaunchKernelGGL(k_s2d_filter, dim3(cdiv((int64_t)q.R * q.S * q.C * q.K, 256)), dim3(256), 0, S(stream), w, d->R, d->S,
+                         d->C, d->K, q.R, q.S, wsf);
+      launch_packed<MODE_FWD>(r, p, xs, wsf, workspace, S(stream));
+      break;
+    }
+    case FAM_STEM_FWD: {
+      dim3 grid(cdiv(d->OW, STEM_T), cdiv(d->OH, STEM_T), d->N);
+      hipLaunchKernelGGL(k_conv_smallc_fwd, grid, dim3(256), stem_lds_bytes(d), S(stream), p);
+      break;
+    }
+    default:
+      hipLaunchKernelGGL(k_conv_direct_fwd, dim3(cdiv((int64_t)p.M * p.K, 256)), dim3(256), 0, S(stream), p);
   }
   return check_launch("conv2d_fwd");
 }
@@ -1523,88 +1548,70 @@ int mtlssl_conv2d_dgrad_xf(const mtlssl_conv_desc* d, const float* dy, const flo
   p.NG = d->C;
   MTLSSL_REQUIRE(desc_dense(d) || mfma_dgrad_ok(d),
                  "conv_dgrad: a strided dy (ldy = %d) needs K %% 16 == 0, C %% 4 == 0 and C >= 16", d->ldy);
-  WinoChoice wc;
-  if (workspace && choose_wino(d, MODE_DGRAD, &wc)) {
-    wino_dgrad(d, wc.variant, wc.tile, dy, w, residual, mask_ref, dx, epi, workspace, S(stream),
-               (filter_xf && xf_variant == wc.variant) ? filter_xf : nullptr);
-  } else if (workspace && parity_ok(d)) {
-    parity_dgrad(d, dy, w, residual, mask_ref, dx, epi, workspace, S(stream));
-  } else if (mfma_dgrad_ok(d)) {
-    Plan pl = plan_dir(d, MODE_DGRAD);
-    if ((pl.nsplit > 1 || pl.tail_rows > 0) && !workspace) pl = Plan{pick_tile(p.M, p.NG, 1), 1, 0, 0, 1, 0};
-    launch_planned<MODE_DGRAD>(pl, p, (float*)workspace, S(stream));
-  } else if (workspace && padded_dgrad_ok(d)) {
-    const mtlssl_conv_desc q = padded_desc(d);
-    const int64_t M = p.M;
-    float* dy_pad = (float*)workspace;
-    float* w_pad = (float*)((char*)workspace + align_up(M * q.K * 4, 256));
-    void* ws_conv = (char*)workspace + padded_dgrad_bytes(d);
-    hipLaunchKernelGGL(k_pad_rows, dim3(cdiv(M * q.K, 256)), dim3(256), 0, S(stream), dy, M, d->K, q.K, dy_pad);
-    hipLaunchKernelGGL(k_pad_rows, dim3(cdiv((int64_t)d->C * q.K, 256)), dim3(256), 0, S(stream), w, (int64_t)d->C, d->K, q.K, w_pad);
-    ConvArgs pq = make_args(&q);
-    pq.a = dy_pad; pq.b = w_pad; pq.out = dx; pq.residual = residual; pq.mask = mask_ref; pq.epi = epi;
-    pq.a_bytes = (unsigned)(M * q.K * 4);
-    pq.b_bytes = (unsigned)((int64_t)q.C * q.K * 4);
-    pq.M = (int)M;
-    pq.NG = q.C;
-    Plan pl = plan_dir(&q, MODE_DGRAD);
-    launch_planned<MODE_DGRAD>(pl, pq, (float*)ws_conv, S(stream));
-  } else if (is_pointwise(d)) {
-    GemmArgs g{dy, w, dx, nullptr, residual, mask_ref, p.M, d->C, d->K, epi, 0};
-    hipLaunchKernelGGL(k_gemm_small<GM_DGRAD>, dim3(cdiv(g.N, 64), cdiv(g.M, 64)), dim3(256), 0, S(stream), g);
-  } else {
-    int64_t total = (int64_t)p.M * p.C;
-    hipLaunchKernelGGL(k_conv_direct_dgrad, dim3(cdiv(total, 256)), dim3(256), 0, S(stream), p);
+  const Route r = route(d, MODE_DGRAD, workspace != nullptr);
+  switch (r.family) {
+    case FAM_WINO:
+      wino_dgrad(d, r.wc.variant, r.wc.tile, dy, w, residual, mask_ref, dx, epi, workspace, S(stream),
+                 (filter_xf && xf_variant == r.wc.variant) ? filter_xf : nullptr);
+      break;
+    case FAM_PARITY:
+      parity_dgrad(r, d, dy, w, residual, mask_ref, dx, epi, workspace, S(stream));
+      break;
+    case FAM_DIRECT:
+      launch_planned<MODE_DGRAD>(r.plan, p, (float*)workspace, S(stream));
+      break;
+    case FAM_PADDED: {        // dy -> [M, Kp], w -> [C, Kp], zero columns
+      float* dy_pad = (float*)workspace;
+      float* w_pad = (float*)((char*)workspace + r.front_a);
+      hipLaunchKernelGGL(k_pad_rows, dim3(cdiv((int64_t)p.M * r.q.K, 256)), dim3(256), 0, S(stream), dy, (int64_t)p.M, d->K, r.q.K, dy_pad);
+      hipLaunchKernelGGL(k_pad_rows, dim3(cdiv((int64_t)d->C * r.q.K, 256)), dim3(256), 0, S(stream), w, (int64_t)d->C, d->K, r.q.K, w_pad);
+      launch_packed<MODE_DGRAD>(r, p, dy_pad, w_pad, workspace, S(stream));
+      break;
+    }
+    case FAM_GEMM_SMALL: {
+      GemmArgs g{dy, w, dx, nullptr, residual, mask_ref, p.M, d->C, d->K, epi, 0};
+      hipLaunchKernelGGL(k_gemm_small<GM_DGRAD>, dim3(cdiv(g.N, 64), cdiv(g.M, 64)), dim3(256), 0, S(stream), g);
+      break;
+    }
+    default:
+      hipLaunchKernelGGL(k_conv_direct_dgrad, dim3(cdiv((int64_t)p.M * p.C, 256)), dim3(256), 0, S(stream), p);
   }
   return check_launch("conv2d_dgrad");
 }
 
 int mtlssl_conv2d_tile_config(const mtlssl_conv_desc* d, int mode) {
   if (!d || mode < MODE_FWD || mode > MODE_WGRAD) return -1;
-  if (!(mode == MODE_FWD ? mfma_fwd_ok(d) : (mode == MODE_DGRAD ? mfma_dgrad_ok(d) : mfma_wgrad_ok(d)))) return -1;
-  WinoChoice wc;
-  if (choose_wino(d, mode, &wc)) return make_code(1 + wc.variant, wc.tile);
-  if (mode == MODE_WGRAD) {
-    int cfg, ns, pps;
-    wgrad_plan(d, &cfg, &ns, &pps);
-    return make_code(0, cfg);
-  }
-  return make_code(0, plan_dir(d, mode).cfg);
+  const Route r = route(d, mode);
+  if (r.family == FAM_WINO) return make_code(1 + r.wc.variant, r.wc.tile);
+  // the padded and space-to-depth forms answer -1 although they run on the tile engine: ops._autotune skips them by it
+  if (r.family != FAM_DIRECT && r.family != FAM_PARITY) return -1;
+  return make_code(0, mode == MODE_WGRAD ? r.wg.cfg : r.plan.cfg);     // input parity: the tile of its strided-gather plan
 }
 
 // Multiply-accumulates the launch plan of (d, mode) executes, on the matrix cores (on_mfma = 1) or in a VALU
-// fallback kernel (on_mfma = 0): the branch ladder of mtlssl_conv2d_fwd / _dgrad / _wgrad (a workspace is assumed),
-// with the reduction widths the kernels really run — transformed-domain GEMM stacks for the Winograd variants
-// (36 or 121 products per tile, clipped tiles included), zero-padded channels / taps of the padded and
-// space-to-depth forms, a quarter of the taps for the input-parity stride-2 dgrad. Rows that only pad the last
-// MFMA tile are not counted. bench.py sums these over a step for `whole_step.executed_tflops`.
+// fallback kernel (on_mfma = 0), a workspace assumed, with the reduction widths the kernels really run —
+// transformed-domain GEMM stacks for the Winograd variants (36 or 121 products per tile, clipped tiles included),
+// zero-padded channels / taps of the padded and space-to-depth forms, a quarter of the taps for the input-parity
+// stride-2 dgrad. Rows that only pad the last MFMA tile are not counted. bench.py sums these over a step for
+// `whole_step.executed_tflops`.
 int64_t mtlssl_conv2d_executed_macs(const mtlssl_conv_desc* d, int mode, int on_mfma) {
   if (!d || mode < MODE_FWD || mode > MODE_WGRAD || check_desc(d)) return 0;
   const int64_t P_out = (int64_t)d->N * d->OH * d->OW, P_in = (int64_t)d->N * d->H * d->W;
   const int64_t taps = (int64_t)d->R * d->S;
   const int64_t direct = (mode == MODE_DGRAD && d->stride == 1 ? P_in : P_out) * taps * d->C * d->K;
-  int64_t mfma = 0, valu = 0;
-  WinoChoice wc;
-  if (choose_wino(d, mode, &wc)) {
-    mfma = wino_input_bytes(d, wc.variant) / 4 * d->K;        // planes * tiles * C * K
-  } else if (mode == MODE_FWD) {
-    if (mfma_fwd_ok(d)) mfma = direct;
-    else if (padded_fwd_ok(d)) mfma = P_out * align_up(d->C, BK) * d->K;
-    else if (is_pointwise(d)) valu = direct;
-    else if (s2d_fwd_ok(d)) mfma = P_out * ((d->R + 1) / 2) * ((d->S + 1) / 2) * BK * d->K;
-    else valu = direct;
-  } else if (mode == MODE_DGRAD) {
-    const int64_t gathered = P_in * taps * d->C * d->K;        // every tap visited for every input pixel
-    if (parity_ok(d)) mfma = gathered / ((int64_t)d->stride * d->stride);
-    else if (mfma_dgrad_ok(d)) mfma = gathered;
-    else if (padded_dgrad_ok(d)) mfma = P_in * d->C * align_up(d->K, BK);
-    else valu = direct;
-  } else {
-    if (mfma_wgrad_ok(d)) mfma = direct;
-    else if (padded_wgrad_ok(d)) mfma = P_out * d->C * align_up(d->K, 4);
-    else valu = direct;
+  const int64_t gathered = P_in * taps * d->C * d->K;          // dgrad: every tap visited for every input pixel
+  const Route r = route(d, mode);
+  const mtlssl_conv_desc& q = r.q;
+  int64_t mfma = 0;
+  switch (r.family) {
+    case FAM_WINO: mfma = wino_input_bytes(d, r.wc.variant) / 4 * d->K; break;       // planes * tiles * C * K
+    case FAM_DIRECT: mfma = mode == MODE_DGRAD ? gathered : direct; break;
+    case FAM_PARITY: mfma = gathered / ((int64_t)d->stride * d->stride); break;       // odd extents not told apart
+    case FAM_PADDED: mfma = (mode == MODE_DGRAD ? P_in : P_out) * q.C * q.K; break;
+    case FAM_S2D: mfma = P_out * q.R * q.S * q.C * q.K; break;
+    default: return on_mfma ? 0 : direct;                                             // every VALU kernel alike
   }
-  return on_mfma ? mfma : valu;
+  return on_mfma ? mfma : 0;
 }
 
 int mtlssl_conv2d_force_config(const mtlssl_conv_desc* d, int mode, int cfg) {
@@ -1615,7 +1622,7 @@ int mtlssl_conv2d_force_config(const mtlssl_conv_desc* d, int mode, int cfg) {
     std::lock_guard<std::mutex> g(tuned_mutex());
     if (cfg < 0) tuned_map().erase(k); else tuned_map()[k] = cfg;
   }
-  plans_clear();
+  routes_clear();
   return MTLSSL_OK;
 }
 
@@ -1627,7 +1634,7 @@ int mtlssl_conv2d_set_fp32_engine(int mode) {
 
 int mtlssl_conv2d_set_winograd(int mode) {
   const int prev = wino_env();
-  if (mode >= 0 && mode <= 2) { wino_mode_ref().store(mode); plans_clear(); }
+  if (mode >= 0 && mode <= 2) { wino_mode_ref().store(mode); routes_clear(); }
   return prev;
 }
 
@@ -1639,14 +1646,13 @@ int mtlssl_conv2d_set_pointwise(int on) {
 
 int mtlssl_conv2d_num_dispatches(const mtlssl_conv_desc* d, int mode) {
   if (!d) return 0;
-  WinoChoice wc;
-  if ((mode == MODE_FWD && mfma_fwd_ok(d)) || (mode == MODE_DGRAD && mfma_dgrad_ok(d)))
-    return !choose_wino(d, mode, &wc) && plan_dir(d, mode).tail_rows > 0 ? 2 : 1;
-  return 1;
+  if (mode != MODE_FWD && mode != MODE_DGRAD) return 1;
+  // 2 = a main launch and a K-split tail. The input-parity dgrad answers for its strided-gather plan, not for its up
+  // to four GEMMs, and the padded / space-to-depth forms answer 1 whatever tail their inner plan has.
+  const Route r = route(d, mode);
+  return (r.family == FAM_DIRECT || r.family == FAM_PARITY) && r.plan.tail_rows > 0 ? 2 : 1;
 }
 
-// What the launch ladders above will do for (d, mode), read from the same memoised planners (a workspace is assumed,
-// as in mtlssl_conv2d_executed_macs). Host arithmetic only.
 static void plan_info_gemm(const Plan& pl, int64_t M, int64_t NG, int ksteps, int32_t* out) {
   out[2] = pl.cfg; out[3] = pl.nsplit; out[4] = pl.ks_per_split;
   out[5] = pl.tail_rows; out[6] = pl.tail_rows > 0 ? pl.tail_nsplit : 0; out[7] = pl.tail_rows > 0 ? pl.tail_ks : 0;
@@ -1655,83 +1661,49 @@ static void plan_info_gemm(const Plan& pl, int64_t M, int64_t NG, int ksteps, in
 int mtlssl_conv2d_plan_info(const mtlssl_conv_desc* d, int mode, int parity_class, int32_t* out) {
   MTLSSL_REQUIRE(d != nullptr && out != nullptr && mode >= MODE_FWD && mode <= MODE_WGRAD, "plan_info: bad arguments");
   if (int rc = check_desc(d)) return rc;
+  static const int32_t PUBLIC[] = {MTLSSL_PLAN_WINO_F43, MTLSSL_PLAN_DIRECT, MTLSSL_PLAN_PARITY, MTLSSL_PLAN_PADDED, MTLSSL_PLAN_S2D,
+                                   MTLSSL_PLAN_THIN,     MTLSSL_PLAN_VALU,   MTLSSL_PLAN_VALU,   MTLSSL_PLAN_VALU,   MTLSSL_PLAN_VALU};
+  const Route r = route(d, mode);
+  const mtlssl_conv_desc& q = r.q;
   for (int i = 0; i < MTLSSL_PLAN_INFO_LEN; ++i) out[i] = 0;
+  out[0] = PUBLIC[r.family];
   out[1] = mtlssl_conv2d_tile_config(d, mode);
   out[2] = -1;
   out[14] = mtlssl_conv2d_num_dispatches(d, mode);
-  const int64_t P = (int64_t)d->N * d->OH * d->OW;
-  WinoChoice wc;
-  if (choose_wino(d, mode, &wc)) {
-    out[0] = wc.variant == 0 ? MTLSSL_PLAN_WINO_F43 : MTLSSL_PLAN_WINO_M7;
-    out[2] = wc.tile; out[3] = 1;
-    out[9] = (int32_t)(mode == MODE_WGRAD ? d->C : (mode == MODE_FWD ? P : (int64_t)d->N * d->H * d->W));
-    out[10] = mode == MODE_DGRAD ? d->C : d->K;
-    out[11] = CFG_BM[wc.tile]; out[12] = CFG_BN[wc.tile];
-    return MTLSSL_OK;
+  const int64_t P = (int64_t)d->N * d->OH * d->OW, M = mode == MODE_FWD ? P : (int64_t)d->N * d->H * d->W;
+  switch (r.family) {
+    case FAM_WINO:
+      if (r.wc.variant != 0) out[0] = MTLSSL_PLAN_WINO_M7;
+      out[2] = r.wc.tile; out[3] = 1;
+      out[9] = (int32_t)(mode == MODE_WGRAD ? d->C : M);
+      out[10] = mode == MODE_DGRAD ? d->C : d->K;
+      out[11] = CFG_BM[r.wc.tile]; out[12] = CFG_BN[r.wc.tile];
+      break;
+    case FAM_PARITY: {
+      MTLSSL_REQUIRE(parity_class >= 0 && parity_class < 4, "plan_info: parity class %d of an input-parity dgrad", parity_class);
+      const ParityProblem c = parity_problem(d, parity_class >> 1, parity_class & 1);
+      if (c.Hs == 0 || c.Ws == 0 || c.Rs == 0 || c.Ss == 0) break;                  // no GEMM for this class
+      const Plan& pl = r.parity[parity_class];
+      plan_info_gemm(pl, (int64_t)d->N * c.Hs * c.Ws, d->C, c.Rs * c.Ss * (d->K / CFG_BK[pl.cfg]), out);
+      break;
+    }
+    case FAM_DIRECT: case FAM_PADDED: case FAM_S2D:
+      if (mode == MODE_WGRAD) {
+        const int cfg = r.wg.cfg;
+        out[2] = cfg; out[3] = r.wg.nsplit; out[4] = r.wg.pps / CFG_BK[cfg]; out[8] = (int32_t)cdiv(P, CFG_BK[cfg]);
+        out[9] = q.C; out[10] = q.K; out[11] = CFG_BM[cfg]; out[12] = CFG_BN[cfg]; out[13] = r.wg.pps;
+      } else {
+        plan_info_gemm(r.plan, M, mode == MODE_FWD ? q.K : q.C, q.R * q.S * ((mode == MODE_FWD ? q.C : q.K) / CFG_BK[r.plan.cfg]), out);
+      }
+      break;
+    default: break;
   }
-  if (mode == MODE_WGRAD) {
-    mtlssl_conv_desc q = *d;
-    if (mfma_wgrad_ok(d)) out[0] = MTLSSL_PLAN_DIRECT;
-    else if (padded_wgrad_ok(d)) { out[0] = MTLSSL_PLAN_PADDED; q = padded_wgrad_desc(d); }
-    else { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
-    int cfg, ns, pps;
-    wgrad_plan(&q, &cfg, &ns, &pps);
-    out[2] = cfg; out[3] = ns; out[4] = pps / CFG_BK[cfg]; out[8] = (int32_t)cdiv(P, CFG_BK[cfg]);
-    out[9] = q.C; out[10] = q.K; out[11] = CFG_BM[cfg]; out[12] = CFG_BN[cfg]; out[13] = pps;
-    return MTLSSL_OK;
-  }
-  if (mode == MODE_FWD) {
-    mtlssl_conv_desc q = *d;
-    if (mfma_fwd_ok(d)) out[0] = MTLSSL_PLAN_DIRECT;
-    else if (padded_fwd_ok(d)) { out[0] = MTLSSL_PLAN_PADDED; q.C = (int)align_up(d->C, BK); }
-    else if (thin_fwd_ok(d)) { out[0] = MTLSSL_PLAN_THIN; return MTLSSL_OK; }
-    else if (is_pointwise(d)) { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
-    else if (s2d_fwd_ok(d)) { out[0] = MTLSSL_PLAN_S2D; q = s2d_desc(d); }
-    else { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
-    const Plan pl = plan_dir(&q, MODE_FWD);
-    plan_info_gemm(pl, P, q.K, q.R * q.S * (q.C / CFG_BK[pl.cfg]), out);
-    return MTLSSL_OK;
-  }
-  if (parity_ok(d)) {
-    out[0] = MTLSSL_PLAN_PARITY;
-    MTLSSL_REQUIRE(parity_class >= 0 && parity_class < 4, "plan_info: parity class %d of an input-parity dgrad", parity_class);
-    const ParityProblem q = parity_problem(d, parity_class >> 1, parity_class & 1);
-    if (q.Hs == 0 || q.Ws == 0 || q.Rs == 0 || q.Ss == 0) return MTLSSL_OK;        // no GEMM for this class
-    const Plan pl = parity_plan(d, q);
-    plan_info_gemm(pl, (int64_t)d->N * q.Hs * q.Ws, d->C, q.Rs * q.Ss * (d->K / CFG_BK[pl.cfg]), out);
-    return MTLSSL_OK;
-  }
-  mtlssl_conv_desc q = *d;
-  if (mfma_dgrad_ok(d)) out[0] = MTLSSL_PLAN_DIRECT;
-  else if (padded_dgrad_ok(d)) { out[0] = MTLSSL_PLAN_PADDED; q = padded_desc(d); }
-  else { out[0] = MTLSSL_PLAN_VALU; return MTLSSL_OK; }
-  const Plan pl = plan_dir(&q, MODE_DGRAD);
-  plan_info_gemm(pl, (int64_t)q.N * q.H * q.W, q.C, q.R * q.S * (q.K / CFG_BK[pl.cfg]), out);
   return MTLSSL_OK;
 }
 
 int64_t mtlssl_conv2d_wgrad_workspace_bytes(const mtlssl_conv_desc* d) {
-  if (!d) return 256;
-  int64_t bias_part = align_up((int64_t)COLSUM_MAX_PARTS * d->K * 4, 256);
-  if (!mfma_wgrad_ok(d) && padded_wgrad_ok(d)) {
-    const mtlssl_conv_desc q = padded_wgrad_desc(d);
-    return bias_part + align_up((int64_t)d->N * d->OH * d->OW * q.K * 4, 256) + (mtlssl_conv2d_wgrad_workspace_bytes(&q) -
-                                                                                   align_up((int64_t)COLSUM_MAX_PARTS * q.K * 4, 256));
-  }
-  if (!mfma_wgrad_ok(d)) {
-    if (is_stem3(d)) return bias_part + align_up((int64_t)STEM_MAX_CHUNKS * 27 * d->K * 4, 256);
-    if (!is_pointwise(d)) return bias_part;
-    int ns, kps;
-    small_wgrad_plan(d, &ns, &kps);
-    return bias_part + align_up((int64_t)ns * d->C * d->K * 4, 256);
-  }
-  int cfg, ns, pps;
-  WinoChoice wc;
-  if (choose_wino(d, MODE_WGRAD, &wc)) return bias_part + wino_workspace_bytes(d, wc.variant, MODE_WGRAD);
-  wgrad_plan(d, &cfg, &ns, &pps);
-  int sns = 0, spps;
-  if (split_wgrad_plan((int64_t)d->N * d->OH * d->OW, d->C, d->K, d->R * d->S, &sns, &spps) && sns > ns) ns = sns;
-  return bias_part + align_up((int64_t)ns * d->R * d->S * d->C * d->K * 4, 256);
+  if (!d) return 256;                                                   // no check_desc here either
+  return colsum_bytes(d) + route(d, MODE_WGRAD).bytes;
 }
 
 // Plan of a grouped wgrad: the tile and the split of the pixel range that fill the chip with n problems' tiles.
@@ -1810,7 +1782,7 @@ int mtlssl_conv2d_wgrad_ex(const mtlssl_conv_desc* d, const float* x, const floa
                  "conv_wgrad: a strided dy (ldy = %d) needs C, K %% 4 == 0 and C, K >= 16", d->ldy);
   int64_t P = (int64_t)d->N * d->OH * d->OW;
   MTLSSL_REQUIRE(workspace != nullptr, "conv_wgrad: workspace required");
-  float* ws_main = (float*)((char*)workspace + align_up((int64_t)COLSUM_MAX_PARTS * d->K * 4, 256));
+  float* ws_main = (float*)((char*)workspace + colsum_bytes(d));
   // bias gradient = column sums of dy: the partial pass runs first (its region of the workspace is its own); on the
   // MFMA path the fold rides on the filter gradient's reduce kernel, elsewhere k_colsum_fold closes it below
   ColsumPlan cp = colsum_plan(P, d->K);
@@ -1825,67 +1797,69 @@ int mtlssl_conv2d_wgrad_ex(const mtlssl_conv_desc* d, const float* x, const floa
       hipLaunchKernelGGL(k_colsum_partial<floatx4>, grid, dim3(256), 0, st, dy, (int)P, d->K, ldy, cp.per_chunk, cp.CQ,
                          (float*)workspace);
   };
-  WinoChoice wc;
-  if (choose_wino(d, MODE_WGRAD, &wc)) {
-    wino_wgrad(d, wc.variant, wc.tile, x, dy, out_scale, dw, beta, ws_main, st,
-               (input_xf && input_variant == wc.variant) ? input_xf : nullptr);
-  } else if (mfma_wgrad_ok(d)) {
-    int cfg, ns, pps;
-    wgrad_plan(d, &cfg, &ns, &pps);
-    const bool split = fp32_engine() == 1 && (cfg == 0 || cfg == 3) && desc_dense(d) &&
-                       split_wgrad_plan(P, d->C, d->K, d->R * d->S, &ns, &pps);
-    // bias gradient: the GEMM's own blocks of tile row 0 / tap 0 leave [split][K] column sums of dy in the column-sum
-    // region of the workspace (conv_mfma.h: cs_part) — no launch of its own; the split engine keeps the partial kernel
-    const bool ride = dbias && !split && ns <= COLSUM_MAX_PARTS;
-    if (dbias && !ride) colsum_partial();
-    p.out = ws_main;
-    p.M = d->C; p.NG = d->K; p.nsplit = ns; p.pix_per_split = pps;
-    p.cs_part = ride ? (float*)workspace : nullptr;
-    if (split) launch_split<MODE_WGRAD, false>(p, dim3(1, d->R * d->S, ns), st);
-    else launch_mfma<MODE_WGRAD>(cfg, p, dim3(1, d->R * d->S, ns), st);
-    int64_t total4 = (int64_t)d->R * d->S * d->C * d->K / 4;
-    const int main_blocks = (int)cdiv(total4 * 4, 256);
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3(main_blocks + (dbias ? (int)cdiv(d->K, 4) : 0)), dim3(256), 0, st,
-                       (const float*)ws_main, ns, total4, d->K, out_scale, dw, beta, main_blocks,
-                       (const float*)workspace, ride ? ns : cp.chunks, dbias, dbias_scale);
-    colsum_folded = dbias != nullptr;
-  } else if (padded_wgrad_ok(d)) {
-    const mtlssl_conv_desc q = padded_wgrad_desc(d);
-    float* dy_pad = ws_main;
-    float* ws_q = (float*)((char*)ws_main + align_up(P * q.K * 4, 256));
-    hipLaunchKernelGGL(k_pad_rows, dim3(cdiv(P * q.K, 256)), dim3(256), 0, st, dy, P, d->K, q.K, dy_pad);
-    int cfg, ns, pps;
-    wgrad_plan(&q, &cfg, &ns, &pps);
-    ConvArgs pq = make_args(&q);
-    pq.a = x; pq.b = dy_pad; pq.out = ws_q;
-    pq.a_bytes = p.a_bytes; pq.b_bytes = (unsigned)(P * q.K * 4);
-    pq.M = q.C; pq.NG = q.K; pq.nsplit = ns; pq.pix_per_split = pps;
-    const bool ride = dbias && (int64_t)ns * q.K <= (int64_t)COLSUM_MAX_PARTS * d->K;
-    pq.cs_part = ride ? (float*)workspace : nullptr;
-    launch_mfma<MODE_WGRAD>(cfg, pq, dim3(1, 1, ns), st);
-    const int main_blocks = (int)cdiv((int64_t)d->C * d->K, 256);
-    hipLaunchKernelGGL(k_wgrad_reduce_unpad, dim3(main_blocks + (ride ? (int)cdiv(d->K, 256) : 0)), dim3(256), 0, st,
-                       (const float*)ws_q, ns, d->C, q.K, d->K, out_scale, dw, beta, main_blocks, (const float*)workspace,
-                       dbias, dbias_scale);
-    colsum_folded = ride;
-  } else if (is_pointwise(d)) {
-    int ns, kps;
-    small_wgrad_plan(d, &ns, &kps);
-    GemmArgs g{x, dy, ws_main, nullptr, nullptr, nullptr, d->C, d->K, (int)P, 0, kps};
-    hipLaunchKernelGGL(k_gemm_small<GM_WGRAD>, dim3(cdiv(g.N, 64), cdiv(g.M, 64), ns), dim3(256), 0, st, g);
-    int64_t total = (int64_t)d->C * d->K;
-    hipLaunchKernelGGL(k_small_reduce, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)ws_main, ns,
-                       total, d->K, out_scale, dw, beta);
-  } else if (is_stem3(d)) {
-    int chunks, ppc;
-    stem_plan(d, &chunks, &ppc);
-    hipLaunchKernelGGL((k_conv_stem_wgrad<3, 3, 3>), dim3(chunks), dim3(256), 0, st, p, ppc, ws_main);
-    int64_t total = (int64_t)27 * d->K;
-    hipLaunchKernelGGL(k_small_reduce, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)ws_main, chunks,
-                       total, d->K, out_scale, dw, beta);
-  } else {
-    hipLaunchKernelGGL(k_conv_direct_wgrad, dim3(d->C, d->R * d->S), dim3(64), 0, st, p, out_scale,
-                       dw, beta);
+  const Route r = route(d, MODE_WGRAD);
+  switch (r.family) {
+    case FAM_WINO:
+      wino_wgrad(d, r.wc.variant, r.wc.tile, x, dy, out_scale, dw, beta, ws_main, st,
+                 (input_xf && input_variant == r.wc.variant) ? input_xf : nullptr);
+      break;
+    case FAM_DIRECT: {
+      const bool split = wgrad_on_split_engine(r, d);
+      const int ns = split ? r.split_ns : r.wg.nsplit, pps = split ? r.split_pps : r.wg.pps;
+      // bias gradient: the GEMM's own blocks of tile row 0 / tap 0 leave [split][K] column sums of dy in the column-sum
+      // region of the workspace (conv_mfma.h: cs_part) — no launch of its own; the split engine keeps the partial kernel
+      const bool ride = dbias && !split && ns <= COLSUM_MAX_PARTS;
+      if (dbias && !ride) colsum_partial();
+      p.out = ws_main;
+      p.M = d->C; p.NG = d->K; p.nsplit = ns; p.pix_per_split = pps;
+      p.cs_part = ride ? (float*)workspace : nullptr;
+      if (split) launch_split<MODE_WGRAD, false>(p, dim3(1, d->R * d->S, ns), st);
+      else launch_mfma<MODE_WGRAD>(r.wg.cfg, p, dim3(1, d->R * d->S, ns), st);
+      int64_t total4 = (int64_t)d->R * d->S * d->C * d->K / 4;
+      const int main_blocks = (int)cdiv(total4 * 4, 256);
+      hipLaunchKernelGGL(k_wgrad_reduce, dim3(main_blocks + (dbias ? (int)cdiv(d->K, 4) : 0)), dim3(256), 0, st,
+                         (const float*)ws_main, ns, total4, d->K, out_scale, dw, beta, main_blocks,
+                         (const float*)workspace, ride ? ns : cp.chunks, dbias, dbias_scale);
+      colsum_folded = dbias != nullptr;
+      break;
+    }
+    case FAM_PADDED: {
+      const mtlssl_conv_desc& q = r.q;
+      const int ns = r.wg.nsplit;
+      float* dy_pad = ws_main;
+      float* ws_q = (float*)((char*)ws_main + r.front_bytes);
+      hipLaunchKernelGGL(k_pad_rows, dim3(cdiv(P * q.K, 256)), dim3(256), 0, st, dy, P, d->K, q.K, dy_pad);
+      ConvArgs pq = make_args(&q);
+      pq.a = x; pq.b = dy_pad; pq.out = ws_q;
+      pq.a_bytes = p.a_bytes; pq.b_bytes = (unsigned)(P * q.K * 4);
+      pq.M = q.C; pq.NG = q.K; pq.nsplit = ns; pq.pix_per_split = r.wg.pps;
+      const bool ride = dbias && (int64_t)ns * q.K <= (int64_t)COLSUM_MAX_PARTS * d->K;
+      pq.cs_part = ride ? (float*)workspace : nullptr;
+      launch_mfma<MODE_WGRAD>(r.wg.cfg, pq, dim3(1, 1, ns), st);
+      const int main_blocks = (int)cdiv((int64_t)d->C * d->K, 256);
+      hipLaunchKernelGGL(k_wgrad_reduce_unpad, dim3(main_blocks + (ride ? (int)cdiv(d->K, 256) : 0)), dim3(256), 0, st,
+                         (const float*)ws_q, ns, d->C, q.K, d->K, out_scale, dw, beta, main_blocks, (const float*)workspace,
+                         dbias, dbias_scale);
+      colsum_folded = ride;
+      break;
+    }
+    case FAM_GEMM_SMALL: {
+      GemmArgs g{x, dy, ws_main, nullptr, nullptr, nullptr, d->C, d->K, (int)P, 0, r.wg.pps};
+      hipLaunchKernelGGL(k_gemm_small<GM_WGRAD>, dim3(cdiv(g.N, 64), cdiv(g.M, 64), r.wg.nsplit), dim3(256), 0, st, g);
+      int64_t total = (int64_t)d->C * d->K;
+      hipLaunchKernelGGL(k_small_reduce, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)ws_main, r.wg.nsplit,
+                         total, d->K, out_scale, dw, beta);
+      break;
+    }
+    case FAM_STEM3_WGRAD: {
+      hipLaunchKernelGGL((k_conv_stem_wgrad<3, 3, 3>), dim3(r.wg.nsplit), dim3(256), 0, st, p, r.wg.pps, ws_main);
+      int64_t total = (int64_t)27 * d->K;
+      hipLaunchKernelGGL(k_small_reduce, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)ws_main, r.wg.nsplit,
+                         total, d->K, out_scale, dw, beta);
+      break;
+    }
+    default:
+      hipLaunchKernelGGL(k_conv_direct_wgrad, dim3(d->C, d->R * d->S), dim3(64), 0, st, p, out_scale, dw, beta);
   }
   if (dbias && !colsum_folded) {
     colsum_partial();

@@ -555,6 +555,12 @@ def _shared_input_variant(d):
     return v if (v >= 0 and v == lib().conv2d_filter_xf_variant(ctypes.byref(d), 2)) else -1
 
 
+def _conv_ws(d, mode, device):
+    """The workspace a conv call of (d, mode) needs, or None where it needs none."""
+    nb = lib().conv2d_workspace_bytes(ctypes.byref(d), mode)
+    return workspace(nb, "wgrad" if mode == 2 else "splitk", device) if nb else None
+
+
 def conv2d_fwd(d, x, w, bias=None, residual=None, epilogue=0, out=None, xf_cache=None, keep_input_xf=None):
     """keep_input_xf: a dict (owned by the layer) that receives {x.data_ptr(): (V, variant)} when the forward
     and the filter gradient of this problem share a Winograd input transform; conv2d_wgrad takes it back."""
@@ -564,16 +570,13 @@ def conv2d_fwd(d, x, w, bias=None, residual=None, epilogue=0, out=None, xf_cache
     y = out if out is not None else torch.empty((d.N, d.OH, d.OW, d.K), dtype=f32, device=x.device)
     if PROFILER is None:
         def run():
-            nb_ = lib().conv2d_workspace_bytes(ctypes.byref(d), 0)
-            ws_ = workspace(nb_, "splitk", x.device) if nb_ else None
             lib().conv2d_fwd(ctypes.byref(d), ptr(_chk(x)), ptr(_chk(w)), ptr(bias), ptr(residual), ptr(y), epilogue,
-                             ptr(ws_), _stream())
+                             ptr(_conv_ws(d, 0, x.device)), _stream())
         _autotune(d, 0, run)
     t0 = PROFILER.begin(d, 0) if PROFILER is not None else None
     if ACCOUNT is not None:
         ACCOUNT.add(d, 0)
-    nb = lib().conv2d_workspace_bytes(ctypes.byref(d), 0)
-    ws = workspace(nb, "splitk", x.device) if nb else None
+    ws = _conv_ws(d, 0, x.device)
     U, variant = xf_cache.get(d, 0, w) if (xf_cache is not None and d.R == 3 and d.S == 3) else (None, -1)
     V, vvar = None, -1
     if keep_input_xf is not None:
@@ -593,16 +596,13 @@ def conv2d_dgrad(d, dy, w, residual=None, mask_ref=None, epilogue=0, out=None, x
     if PROFILER is None:
         def run():                                    # scratch output; no accumulate into it
             tmp = workspace(4 * d.N * d.H * d.W * d.C, "tune_out", dy.device)
-            nb_ = lib().conv2d_workspace_bytes(ctypes.byref(d), 1)
-            ws_ = workspace(nb_, "splitk", dy.device) if nb_ else None
             lib().conv2d_dgrad(ctypes.byref(d), ptr(_chk_y(d, dy)), ptr(_chk(w)), ptr(residual), ptr(mask_ref), ptr(tmp),
-                               epilogue & ~EPI_ACCUM, ptr(ws_), _stream())
+                               epilogue & ~EPI_ACCUM, ptr(_conv_ws(d, 1, dy.device)), _stream())
         _autotune(d, 1, run)
     t0 = PROFILER.begin(d, 1) if PROFILER is not None else None
     if ACCOUNT is not None:
         ACCOUNT.add(d, 1)
-    nb = lib().conv2d_workspace_bytes(ctypes.byref(d), 1)
-    ws = workspace(nb, "splitk", dy.device) if nb else None
+    ws = _conv_ws(d, 1, dy.device)
     U, variant = xf_cache.get(d, 1, w) if (xf_cache is not None and d.R == 3 and d.S == 3) else (None, -1)
     lib().conv2d_dgrad_xf(ctypes.byref(d), ptr(_chk_y(d, dy)), ptr(_chk(w)), ptr(residual), ptr(mask_ref),
                           ptr(dx), epilogue, ptr(ws), ptr(U), variant, _stream())
@@ -617,13 +617,10 @@ def conv2d_wgrad(d, x, dy, dw, out_scale=None, dbias=None, beta=0.0, input_xf=No
     if PROFILER is None:
         def run():                                    # scratch filter gradient, beta = 0
             tmp = workspace(4 * d.R * d.S * d.C * d.K, "tune_out", x.device)
-            nb_ = lib().conv2d_wgrad_workspace_bytes(ctypes.byref(d))
-            ws_ = workspace(nb_, "wgrad", x.device)
             lib().conv2d_wgrad(ctypes.byref(d), ptr(_chk(x)), ptr(_chk_y(d, dy)), ptr(out_scale), ptr(tmp), None, 0.0,
-                               ptr(ws_), _stream())
+                               ptr(_conv_ws(d, 2, x.device)), _stream())
         _autotune(d, 2, run)
-    nbytes = lib().conv2d_wgrad_workspace_bytes(ctypes.byref(d))
-    ws = workspace(nbytes, "wgrad", x.device)
+    ws = _conv_ws(d, 2, x.device)
     t0 = PROFILER.begin(d, 2) if PROFILER is not None else None
     if ACCOUNT is not None:
         ACCOUNT.add(d, 2)

@@ -412,6 +412,108 @@ def test_strided_maxpool_branch_is_bit_identical_to_dense(ops):
         assert torch.equal(dx, ops.maxpool_bwd(x, yv, gv, 3, 2, pads))
 
 
+# mtlssl_conv2d_fwd / _dgrad with a NULL workspace (documented in include/mtlssl_hip.h; ops.conv2d_* pass one whenever the
+# size query is not 0, so only a direct call gets there): (id, mode, x shape, filter, stride, forward epilogue, set_winograd
+# mode or None, what conv_plan_info must say the call would do WITH a workspace, kernel that runs without one).
+NULL_WS_CASES = [
+    ("ksplit3-fwd", 0, (1, 4, 4, 64), (3, 3, 64, 64), 1, "BIAS|RESIDUAL", None, dict(family="direct", nsplit=3), "unsplit tile plan"),
+    ("ksplit3-dgrad", 1, (1, 4, 4, 64), (3, 3, 64, 64), 1, None, None, dict(family="direct", nsplit=3), "unsplit tile plan"),
+    ("winograd-fwd", 0, (1, 4, 4, 64), (3, 3, 64, 64), 1, "BIAS|RESIDUAL", 2, dict(family="winograd_F43"), "direct"),
+    ("winograd-dgrad", 1, (1, 4, 4, 64), (3, 3, 64, 64), 1, None, 2, dict(family="winograd_F43"), "direct"),
+    ("ksplit5-fwd", 0, (1, 2, 2, 1024), (1, 1, 1024, 16), 1, "BIAS|RESIDUAL", None, dict(family="direct", nsplit=5), "unsplit tile plan"),
+    ("parity-dgrad", 1, (1, 8, 8, 16), (3, 3, 16, 16), 2, None, None, dict(family="input_parity"), "strided gather"),
+    ("padded-fwd", 0, (1, 8, 8, 40), (1, 1, 40, 16), 1, "BIAS|RESIDUAL", None, dict(family="padded"), "k_gemm_small"),
+    ("padded-dgrad", 1, (1, 8, 8, 16), (1, 1, 16, 24), 1, None, None, dict(family="padded"), "k_gemm_small"),
+    ("s2d7-relu-fwd", 0, (1, 16, 16, 3), (7, 7, 3, 64), 2, "BIAS|RELU", None, dict(family="space_to_depth"), "k_conv_smallc_fwd"),
+    ("s2d7-tanh-fwd", 0, (1, 16, 16, 3), (7, 7, 3, 64), 2, "BIAS|TANH", None, dict(family="space_to_depth"), "k_conv_direct_fwd"),
+    ("s2d3-fwd", 0, (1, 16, 16, 3), (3, 3, 3, 32), 2, "BIAS", None, dict(family="space_to_depth"), "k_conv_direct_fwd"),
+    # the cheapest forward problem with a K-split tail launch a host search over conv_plan_info found (2.5 GMAC)
+    ("tail-fwd", 0, (64, 38, 55, 128), (3, 3, 128, 16), 1, "BIAS|RESIDUAL", None, dict(family="direct", tail=True), "unsplit tile plan"),
+]
+
+
+@pytest.mark.parametrize("case", NULL_WS_CASES, ids=[c[0] for c in NULL_WS_CASES])
+def test_null_workspace_routes_match_float64(ops, case):
+    """Every fallback a null workspace selects, against the float64 references of tests/conv_ref.py. All of them are direct
+    summations (tile engine, k_gemm_small, the small-C stem kernel, the scalar kernels), so the bound is the plan tests' one
+    for a direct plan: 8 units of 2^-24 * (sum |a*b| + |addends|); behind the TANH epilogue, plus the device tanhf's
+    distance from a correctly rounded tanh as tests/test_gpu_offtable_plans.py bounds it."""
+    import ctypes
+    from mtl_ssl_amd.lib import lib, ptr
+    from tests.conv_ref import DIRECT_BOUND, _dgrad_reference, _fwd_reference, _rows
+    from tests.parity_report import dot_err
+    from tests.test_gpu_offtable_plans import TANH_ULPS
+    name, mode, xs, ws, stride, epi_name, wino, want, _ = case
+    d = ops.conv_desc(xs, ws, stride, 1, "SAME")
+    N, H, W, C, K, R, S, OH, OW = d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.OH, d.OW
+    prob = (N, H, W, C, K, R, S, OH, OW, d.stride, d.dilation, d.pad_t, d.pad_l)
+    seed = zlib.crc32(repr(case[:5]).encode())
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    x, w, dy = rand(N, H, W, C) * 2 - 0.6, (rand(R, S, C, K) - 0.5) * (2.0 / np.sqrt(R * S * C)), rand(N, OH, OW, K) - 0.5
+    w64, rng, stream = w.double().cpu(), np.random.default_rng(seed), ops._stream()
+    ops.reset_tuning(False, False)
+    prev_wino = ops.set_winograd(wino) if wino is not None else None
+    try:
+        info = ops.conv_plan_info(d, mode)
+        assert info["family"] == want["family"] and info["nsplit"] == want.get("nsplit", info["nsplit"]), (name, info)
+        assert (info["tail_rows"] > 0) == bool(want.get("tail")), (name, info)
+        assert lib().conv2d_workspace_bytes(ctypes.byref(d), mode) > 0, name      # so ops.conv2d_* never gets here
+        if mode == 0:
+            epi = sum(getattr(ops, "EPI_" + e) for e in epi_name.split("|"))
+            bias, res = rand(K) - 0.5, (rand(N, OH, OW, K) - 0.5 if "RESIDUAL" in epi_name else None)
+            rows = _rows(N, OH, OW, rng)
+            rows_t = torch.from_numpy(rows).cuda()
+            ref, mag = _fwd_reference(prob, x, w64, rows)
+            for a in [bias.double().cpu()[None, :]] + ([res.reshape(-1, K)[rows_t].double().cpu()] if res is not None else []):
+                ref, mag = ref + a, mag + a.abs()
+            out = torch.full((N, OH, OW, K), float("nan"), device="cuda")
+            lib().conv2d_fwd(ctypes.byref(d), ptr(x), ptr(w), ptr(bias), ptr(res), ptr(out), epi, None, stream)
+        else:
+            resd, old = rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5
+            rows = _rows(N, H, W, rng)
+            rows_t = torch.from_numpy(rows).cuda()
+            ref, mag = _dgrad_reference(prob, dy, w64, rows)
+            for a in (t.reshape(-1, C)[rows_t].double().cpu() for t in (resd, old)):
+                ref, mag = ref + a, mag + a.abs()
+            out = old.clone()
+            lib().conv2d_dgrad(ctypes.byref(d), ptr(dy), ptr(w), ptr(resd), None, ptr(out), ops.EPI_RESIDUAL | ops.EPI_ACCUM,
+                               None, stream)
+        torch.cuda.synchronize()
+    finally:
+        if prev_wino is not None:
+            ops.set_winograd(prev_wino)
+        ops.reset_tuning()
+    assert bool(torch.isfinite(out).all()), name
+    got = out.reshape(-1, out.shape[-1])[rows_t]
+    if mode == 0 and "TANH" in epi_name:
+        t64 = torch.tanh(ref)
+        unit = torch.from_numpy(np.spacing(np.maximum(t64.abs().numpy(), np.finfo(np.float32).tiny).astype(np.float32)).astype(np.float64))
+        err = (got.double().cpu() - t64).abs()                      # tanh' <= 1: the linear bound carries over
+        worst = float((err / (DIRECT_BOUND * 2.0 ** -24 * mag + TANH_ULPS * unit)).max())
+        print("%s: worst error %.3f of the bound" % (name, worst))
+        assert worst <= 1.0, (name, worst)
+        return
+    if mode == 0 and "RELU" in epi_name:
+        ref = torch.relu(ref)                                       # |relu(a) - relu(b)| <= |a - b|
+    e = dot_err(got, ref, mag)
+    print("%s: error %.2f of %.0f (2^-24 * sum|ab| units)" % (name, e, DIRECT_BOUND))
+    assert e <= DIRECT_BOUND, (name, e)
+
+
+def test_wgrad_refuses_a_null_workspace(ops):
+    """The filter gradient always needs its workspace: the library's error, before any launch (dw is left untouched)."""
+    import ctypes
+    from mtl_ssl_amd.lib import MtlsslError, lib, ptr
+    d = ops.conv_desc((1, 4, 4, 64), (3, 3, 64, 64), 1, 1, "SAME")
+    x, dy = torch.ones(1, 4, 4, 64, device="cuda"), torch.ones(1, 4, 4, 64, device="cuda")
+    dw = torch.full((3, 3, 64, 64), 7.0, device="cuda")
+    with pytest.raises(MtlsslError, match="workspace required"):
+        lib().conv2d_wgrad(ctypes.byref(d), ptr(x), ptr(dy), None, ptr(dw), None, 0.0, None, ops._stream())
+    torch.cuda.synchronize()
+    assert bool((dw == 7.0).all())
+
+
 def test_conv_same_padding_matches_reference_known_answer(ops):
     """Known answers of slim/nets/resnet_v1_test.py:72-111 (testConv2DSameEven): x[i,j] = i+j on
     4x4, w[i,j] = i+j on 3x3; SAME stride 1, conv2d_same stride 2 (== subsample of the former)

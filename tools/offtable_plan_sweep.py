@@ -2,8 +2,8 @@
 
 mtl_ssl_amd/conv_plans.json pins every convolution of the four shipped configurations at ONE frame, the benchmark's. The
 keep-aspect-ratio resizer and the bucketing of input_reader.batches / InputPipeline hand the model other frames and
-smaller batches, and every such problem is planned by the library's time models (csrc/conv.hip plan_gemm, wgrad_plan,
-choose_wino, parity_plan). This tool enumerates those problems on the host, asks the planner what each would launch
+smaller batches, and every such problem is planned by the library's time models (csrc/conv.hip route: plan_gemm,
+wgrad_plan, choose_wino). This tool enumerates those problems on the host, asks the planner what each would launch
 (ops.conv_plan_info: no GPU), reduces the answer to a signature and keeps, for every signature the table's own 359 pairs do
 not already show, the cheapest problem that has it: tests/golden/offtable_conv_problems.json, which
 tests/test_gpu_offtable_plans.py runs against float64 on an MI355X and tests/test_offtable_plans.py regenerates on a CPU.
