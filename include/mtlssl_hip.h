@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 15
+#define MTLSSL_ABI_VERSION 16
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -810,6 +810,37 @@ int mtlssl_debug_cu_thief(int workgroups, int threads, int lds_bytes, int64_t mi
  *   pixels that no outline covers are not written. thickness >= 1. */
 int mtlssl_draw_boxes(uint8_t* image, int height, int width, int64_t row_stride, const int32_t* boxes,
                       const uint8_t* colors, int n, int thickness, mtlssl_stream_t stream);
+
+/* ------------------------------------------------------------------ training summaries
+ * Replaces the variable histograms of object_detection/trainer.py:440-441 (`for model_var in slim.get_model_variables():
+ * global_summaries.add(tf.summary.histogram(model_var.op.name, model_var))`): TensorFlow's HistogramSummary op runs
+ * histogram::Histogram::Add (tensorflow/core/lib/histogram/histogram.cc) over each variable on the host; here one pass
+ * over a flat parameter buffer (ParamStore.weights / .frozen) does it for every variable at once.
+ *   buf            the flat fp32 buffer; variable v is buf[offsets[v] .. offsets[v] + sizes[v]) — what lies between two
+ *                  variables (alignment padding) is never read into a result. offsets are multiples of 4 floats off a
+ *                  16-byte aligned buf (ParamStore aligns them to 64) for the 16-byte loads; others are read by element.
+ *   chunk_table    int32 [num_vars + 1 + 2 * num_chunks], built once per buffer by the host: first the index of every
+ *                  variable's first chunk and num_chunks at [num_vars] (a variable of size s has
+ *                  ceil(s / MTLSSL_HISTOGRAM_CHUNK) consecutive chunks, none when empty), then per chunk the pair
+ *                  (variable, chunk index within the variable). One workgroup per chunk.
+ *   bucket_limits  double [num_limits], increasing; num_limits <= MTLSSL_HISTOGRAM_MAX_LIMITS (the table and one
+ *                  workgroup's uint32 counts live in LDS). A finite x is counted in the first bucket whose limit is
+ *                  strictly greater than double(x) (std::upper_bound, compared in double; denormals as themselves), in
+ *                  the last one when no limit is.
+ *   moments        double [num_vars, 6]: min, max, num, sum (of double(x)), sum_squares (of double(x) * double(x)),
+ *                  nonfinite. NaN and +-inf are counted in nonfinite and left out of everything else. An empty variable,
+ *                  or one with no finite value, has min = DBL_MAX, max = -DBL_MAX, num = 0.
+ *   counts         uint32 [num_vars, num_limits], zeroed by the call.
+ *   workspace      mtlssl_variable_histograms_workspace_bytes(num_chunks) bytes (the chunks' moment partials).
+ * All pointers are device memory. No floating-point atomics: bins are added with integer atomics and the moments are
+ * folded in a fixed order (thread, wave, chunk ascending), so two calls on the same data agree bit for bit. */
+#define MTLSSL_HISTOGRAM_CHUNK 16384
+#define MTLSSL_HISTOGRAM_MAX_LIMITS 4096
+int64_t mtlssl_variable_histograms_workspace_bytes(int num_chunks);
+int mtlssl_variable_histograms(const float* buf, const int32_t* offsets, const int32_t* sizes, int num_vars,
+                               const int32_t* chunk_table, int num_chunks, const double* bucket_limits, int num_limits,
+                               double* moments, uint32_t* counts, void* workspace, int64_t workspace_bytes,
+                               mtlssl_stream_t stream);
 
 /* CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start): the checksum of the reference's
  * data containers — TFRecord framing (tensorflow/core/lib/io/record_writer.cc; the create_records scripts write them,

@@ -25,7 +25,8 @@ SOURCES = {
     "depthwise.hip": [], "pool_concat.hip": [], "winograd.hip": [],
     "eval_metrics.hip": ["-ffp-contract=off"],   # evaluator NMS / edge-mask metric: numpy's double arithmetic
     "aux_labels.hip": ["-ffp-contract=off"],     # labels from boxes: the host definitions' double arithmetic
-    "visualize.hip": [],                # box overlay of the evaluator's visualisations (integer work only)
+    "summaries.hip": ["-ffp-contract=off"],      # variable histograms: the bucket rule and moments are double arithmetic
+    "visualize.hip": [],               # box overlay of the evaluator's visualisations (integer work only)
     "comm.hip": [],                     # RCCL wrappers (host code only; RCCL itself is bound with dlopen)
 }
 

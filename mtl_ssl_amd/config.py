@@ -137,7 +137,10 @@ DEFAULTS = {
                     "restore_mtl_refine": False, "restore_window": False, "restore_closeness": False,
                     "restore_edgemask": False, "data_augmentation_options": [],
                     "divide_grad_by_batch": False, "grad_multiplier": 0.0, "freeze_variables": [],
-                    "replicas_to_aggregate": 1, "log_every_n_steps": 1, "optimizer": "@Optimizer"},
+                    "replicas_to_aggregate": 1, "log_every_n_steps": 1, "optimizer": "@Optimizer",
+                    # train.proto:84-86: summaries (trainer.train writes them; show_image_summary feeds nothing in the
+                    # reference and is accepted and ignored)
+                    "show_image_summary": False, "save_summaries_secs": 120},
     # protos/optimizer.proto
     "Optimizer": {"use_moving_average": True, "moving_average_decay": 0.9999},
     "MomentumOptimizer": {"momentum_optimizer_value": 0.9, "learning_rate": "@LearningRate"},

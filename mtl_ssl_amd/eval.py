@@ -10,7 +10,8 @@ eval_config.calc_loss adds the model's losses (Loss/<name>, FasterRCNNMetaArch.e
 submission_format_output writes the test servers' files instead of metrics; a metrics run with --eval_dir keeps the
 best state under <eval_dir>/best/ (main_subset); --run_once=false evaluates every new state of --checkpoint_dir
 (eval_interval_secs, max_evals) with the model built once; num_visualizations / visualization_export_dir export
-annotated images (mtl_ssl_amd/eval_workflow.py).
+annotated images (mtl_ssl_amd/eval_workflow.py). A metrics run with --eval_dir also leaves a TensorBoard event file there:
+one scalar per metric at the state's global step and one image per visualisation (mtl_ssl_amd/summaries.py).
 
     python -m mtl_ssl_amd.eval --checkpoint_dir=/runs/a --eval_dir=/runs/a/eval --pipeline_config_path=..."""
 import argparse
@@ -181,6 +182,7 @@ def main(argv=None):
         closeness_error = None
         loss_sums = {}
         results = []
+        images = []
         n_img = 0
         raw = _raw_records(record_paths(reader)) if (submission or n_vis) else None
         stream = record_batches(f.input_pipeline, record_paths(reader), K, 1, (), None, dev, reader,
@@ -260,8 +262,10 @@ def main(argv=None):
                         results.append((image_id, abs_boxes, scores, classes1))
                     if n_img < n_vis:
                         gtb = np.asarray(b["groundtruth_boxes"][0], np.float32).reshape(-1, 4) * ohw
-                        eval_workflow.visualize_detection_results(original, image_id, abs_boxes, scores, classes1, gtb,
-                                                                  cats, vis_dir, dev)
+                        png = eval_workflow.visualize_detection_results(original, image_id, abs_boxes, scores, classes1,
+                                                                        gtb, cats, vis_dir, dev)
+                        if png and f.eval_dir:         # eval_util.py:660-669: the drawn image as a summary, too
+                            images.append((image_id, png, original.shape[0], original.shape[1]))
             if not metrics:
                 n_img += 1
                 continue
@@ -328,6 +332,7 @@ def main(argv=None):
             os.makedirs(f.eval_dir, exist_ok=True)
             with open(os.path.join(f.eval_dir, "metrics-%d.json" % step), "w") as fh_out:
                 json.dump(out, fh_out)
+            eval_workflow.write_eval_summaries(f.eval_dir, out, images, step)
             # eval_util.py:869-870, 934-997
             eval_workflow.save_best_ckpt(out, fh.name, step, f.eval_dir, metrics_set, str(ec.get("main_subset", "") or ""),
                                          source=fh)

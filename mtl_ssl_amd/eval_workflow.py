@@ -257,8 +257,8 @@ def draw_labels(image, labels, names):
 def visualize_detection_results(image, tag, detection_boxes, detection_scores, detection_classes, groundtruth_boxes,
                                 cats, export_dir, device):
     """eval_util.py:553-672 for one image: outlines on the device (mtlssl_draw_boxes), label text on the host, PNG to
-    <export_dir>/export-<tag>.png. Without an export_dir nothing is drawn (there is no summary writer here). image:
-    uint8 [H,W,3] as decoded. Returns the path or None."""
+    <export_dir>/export-<tag>.png. Without an export_dir nothing is drawn (write_eval_summaries adds the files that were
+    drawn to eval_dir's event file). image: uint8 [H,W,3] as decoded. Returns the path or None."""
     if not export_dir:
         return None
     import torch
@@ -272,3 +272,25 @@ def visualize_detection_results(image, tag, detection_boxes, detection_scores, d
     path = os.path.join(export_dir, "export-{}.png".format(tag))
     Image.fromarray(out).save(path, format="PNG")
     return path
+
+
+# ------------------------------------------------------------------------------ summaries
+def scalar_metrics(metrics):
+    """The (key, value) pairs of a metrics dict that are plain numbers, keys sorted (eval_util.py:58-80 write_metrics)."""
+    return [(k, float(metrics[k])) for k in sorted(metrics)
+            if isinstance(metrics[k], (int, float, np.floating, np.integer)) and not isinstance(metrics[k], bool)]
+
+
+def write_eval_summaries(eval_dir, metrics, images, global_step):
+    """eval_util.py:58-80 and :660-669: one event file in eval_dir per evaluated state, holding a scalar per numeric key
+    of `metrics` (Loss/* and mtl/* among them) and an image summary `<tag>/image` per drawn visualisation — images:
+    [(tag, path of the PNG visualize_detection_results wrote, height, width)] — all at the state's global step.
+    Returns the file's path."""
+    from . import summaries
+    with summaries.SummaryWriter(eval_dir) as w:
+        for k, v in scalar_metrics(metrics):
+            w.add_scalar(k, v, global_step)
+        for tag, path, height, width in images:
+            with open(path, "rb") as fh:
+                w.add_image("%s/image" % tag, fh.read(), height, width, global_step)
+        return w.path

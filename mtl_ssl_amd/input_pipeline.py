@@ -408,6 +408,11 @@ class InputPipeline:
             self.close()
             raise
 
+    def queue_fill(self):
+        """(batches staged ahead of the consumer, capacity): the prefetch queue's fill for the training summaries
+        (the reference's queue/fraction_of_<capacity>_full of its prefetch queue)."""
+        return len(self._staged), self.prefetch
+
     def device_times(self):
         return self._preparer.device_times() if isinstance(self._preparer, _DevicePreparer) else None
 

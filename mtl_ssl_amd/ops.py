@@ -1054,6 +1054,58 @@ def draw_boxes(image, boxes, colors, thickness):
     return image
 
 
+HISTOGRAM_CHUNK = 16384              # MTLSSL_HISTOGRAM_CHUNK: floats one workgroup of mtlssl_variable_histograms reads
+HISTOGRAM_MAX_LIMITS = 4096          # MTLSSL_HISTOGRAM_MAX_LIMITS
+_hist_limits = {}
+
+
+class HistogramTables:
+    """The device tables mtlssl_variable_histograms reads for one set of variables (offsets / sizes in floats): built
+    once per flat buffer (ParamStore keeps one per buffer) — the variables cut into HISTOGRAM_CHUNK-float chunks."""
+
+    def __init__(self, offsets, sizes, device):
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        sz = np.ascontiguousarray(sizes, np.int64).reshape(-1)
+        assert off.shape == sz.shape and (sz >= 0).all() and (off >= 0).all(), (off.shape, sz.shape)
+        assert not len(off) or int((off + sz).max()) < 2 ** 31, "offsets are int32"
+        per = -(-sz // HISTOGRAM_CHUNK)
+        first = np.concatenate([[0], np.cumsum(per)])
+        pairs = np.stack([np.repeat(np.arange(len(sz)), per),
+                          np.concatenate([np.arange(p) for p in per] + [np.zeros(0, np.int64)])], 1)
+        self.num_vars, self.num_chunks = len(sz), int(first[-1])
+        self.extent = int((off + sz).max()) if len(off) else 0            # floats of the buffer the variables reach
+        self.offsets = torch.from_numpy(off.astype(np.int32)).to(device)
+        self.sizes = torch.from_numpy(sz.astype(np.int32)).to(device)
+        self.chunk_table = torch.from_numpy(np.concatenate([first, pairs.reshape(-1)]).astype(np.int32)).to(device)
+
+
+def variable_histograms(buf, offsets, sizes, limits=None, tables=None):
+    """mtlssl_variable_histograms over the variables buf[offsets[v] : offsets[v] + sizes[v]] of a flat fp32 device
+    buffer (host int sequences; what lies between variables is not counted): TensorFlow's histogram of every variable
+    (summaries.histogram_numpy per variable, bit for bit in the counts, min, max and num). limits: float64 bucket limits
+    (default summaries.default_bucket_limits()); tables: a HistogramTables of (offsets, sizes) to reuse.
+    -> (moments float64 [V,6] = min, max, num, sum, sum_squares, nonfinite; counts uint32 [V,len(limits)]) as host
+    arrays: the launch goes to the current stream, each result comes back in one copy."""
+    from . import summaries
+    dev = buf.device
+    t = tables if tables is not None else HistogramTables(offsets, sizes, dev)
+    assert t.extent <= buf.numel(), (t.extent, buf.numel())
+    if limits is None:
+        lim = _hist_limits.get(dev)
+        if lim is None:
+            lim = _hist_limits[dev] = torch.from_numpy(np.array(summaries.default_bucket_limits())).to(dev)
+    else:
+        lim = torch.from_numpy(np.ascontiguousarray(limits, np.float64)).to(dev)
+    L, V = int(lim.numel()), t.num_vars
+    moments = torch.empty((V, 6), dtype=torch.float64, device=dev)
+    counts = torch.empty((V, L), dtype=i32, device=dev)
+    nbytes = int(lib().variable_histograms_workspace_bytes(t.num_chunks))
+    ws = workspace(nbytes, "histograms", dev) if nbytes else None
+    lib().variable_histograms(ptr(_chk(buf)), ptr(t.offsets), ptr(t.sizes), V, ptr(t.chunk_table), t.num_chunks,
+                              ptr(lim), L, ptr(moments), ptr(counts), ptr(ws), nbytes, _stream())
+    return moments.cpu().numpy(), counts.cpu().numpy().view(np.uint32)
+
+
 AUX_MAX_GT = 256                     # MTLSSL_AUX_MAX_GT: the label kernels hold one image's boxes in LDS
 AUX_WINDOW_ATTEMPTS = 100            # MTLSSL_AUX_WINDOW_ATTEMPTS (labels.WINDOW_ATTEMPTS)
 

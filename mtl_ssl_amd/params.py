@@ -181,6 +181,33 @@ class ParamStore:
     def state_dict(self):
         return {s.name: self.value(s.name).detach().cpu().numpy().copy() for s in self.specs}
 
+    def histograms(self):
+        """{variable name: (moments float64 [6] = min, max, num, sum, sum_squares, nonfinite; counts uint32 [buckets])}
+        for every variable, trainable or not — the histogram summaries of the reference's trainer
+        (object_detection/trainer.py:440-441) over TensorFlow's default buckets (summaries.default_bucket_limits()). On a
+        GPU one launch of ops.variable_histograms per flat buffer and two small copies back; alignment padding is never
+        counted. A store on the CPU (tests of the host plumbing) runs the numpy restatement of the same rule."""
+        from . import summaries
+        out = {}
+        groups = ((self.weights, self.trainable_specs), (self.frozen, [s for s in self.specs if not s.trainable]))
+        if self.device.type != "cuda":
+            for buf, specs in groups:
+                host = buf.numpy()
+                for s in specs:
+                    out[s.name] = summaries.histogram_numpy(host[s.offset:s.offset + s.size])
+            return {s.name: out[s.name] for s in self.specs}
+        from . import ops
+        tabs = self.__dict__.setdefault("_hist_tables", {})
+        for k, (buf, specs) in enumerate(groups):
+            if not specs:
+                continue
+            if k not in tabs:                 # the chunk table depends on the layout alone: built once per store
+                tabs[k] = ops.HistogramTables([s.offset for s in specs], [s.size for s in specs], self.device)
+            moments, counts = ops.variable_histograms(buf, None, None, tables=tabs[k])
+            for i, s in enumerate(specs):
+                out[s.name] = (moments[i], counts[i])
+        return {s.name: out[s.name] for s in self.specs}
+
     def mark_grads_dirty(self):
         """Tell the store that `grads` was written outside Trainer.forward_backward / apply_gradients."""
         self.grads_clean = False

@@ -39,6 +39,9 @@ def _flags(argv):
                     help="record: window / closeness / edge-mask labels are read from the records (frozen when they were "
                          "written); generate: they are made on the device at every step from the boxes and classes "
                          "alone, with fresh windows per step, so plain detection records train the auxiliary heads")
+    ap.add_argument("--save_summaries_secs", type=float, default=None,
+                    help="overrides train_config.save_summaries_secs (default 120): seconds between two summaries in "
+                         "train_dir's TensorBoard event file; 0 writes none")
     return ap.parse_args(argv)
 
 
@@ -137,6 +140,11 @@ def main(argv=None):
     torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
     dev = torch.device("cuda", torch.cuda.current_device())
     model_config, train_config, input_config = read_configs(f)
+    total_configs = (model_config, train_config, input_config)        # train.py:200-204: five with a pipeline file
+    if f.pipeline_config_path:
+        from . import config
+        whole = config.parse_pipeline_config(open(f.pipeline_config_path).read())
+        total_configs += (whole.get("eval_config"), whole.get("eval_input_reader"))
     K = int(model_config.faster_rcnn.num_classes)
     B = int(train_config.batch_size)
     if world > 1:                                    # train_config.batch_size is the GLOBAL batch: every clone of the
@@ -168,7 +176,8 @@ def main(argv=None):
     try:
         trainer.train(next_batch, lambda: probe, train_config, master=f.master, task=rank, num_clones=1,
                       worker_replicas=world, is_chief=rank == 0, train_dir=f.train_dir, model_config=model_config,
-                      num_steps=f.num_steps, aux_labels=f.aux_labels)
+                      num_steps=f.num_steps, aux_labels=f.aux_labels, save_summaries_secs=f.save_summaries_secs,
+                      total_configs=total_configs, input_queue=stream)
     finally:
         if hasattr(stream, "close"):
             stream.close()

@@ -552,12 +552,21 @@ def collective_verdict(comm, code, device):
 def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=0, num_clones=1,
           worker_replicas=1, clone_on_cpu=False, ps_tasks=0, worker_job_name="lonely_worker",
           is_chief=True, train_dir=None, num_examples=0, total_configs=None, model_config=None,
-          is_first_training=True, num_steps=None, log_every=10, save_interval_secs=600, aux_labels="record"):
+          is_first_training=True, num_steps=None, log_every=10, save_interval_secs=600, aux_labels="record",
+          save_summaries_secs=None, input_queue=None):
     """object_detection/trainer.py:217-219 signature. `create_tensor_dict_fn()` yields one batch
     dict per call (see mtl_ssl_amd.synthetic.make_batch for the field contract);
     `create_model_fn()` returns a built FasterRCNNMetaArch. Parameter-server arguments
     (master, ps_tasks, worker_job_name, clone_on_cpu) are accepted and ignored: data parallelism
-    here is one process per GPU over RCCL."""
+    here is one process per GPU over RCCL.
+
+    Summaries (trainer.py:431-454, :482): the chief writes a TensorBoard event file into train_dir — after the first
+    completed step, then on the first log step at least train_config.save_summaries_secs (save_summaries_secs overrides;
+    0 = none) after the previous one. total_configs (the reference's tuple of model / train / train input / eval /
+    eval input configs) adds the five config texts once; input_queue: an object with queue_fill() -> (batches staged,
+    capacity) for the queue/fraction_of_<capacity>_full tag (input_pipeline.InputPipeline).
+    train_config.show_image_summary is accepted and ignored: the reference hands the images to
+    DetectionModel.provide_image_infos (trainer.py:175-176, core/model.py:288-290), which nothing ever reads."""
     import os
     import torch.distributed as dist
     from . import checkpoint
@@ -589,7 +598,6 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
     # num_steps == 0 trains indefinitely (train.proto:42-44; slim.learning.train number_of_steps=None)
     steps = num_steps if num_steps is not None else (int(train_config.num_steps) or None)
     save_secs = float(save_interval_secs) if save_interval_secs else 0.0
-    last_save = time.time()
 
     def save_state():
         if state and is_chief:
@@ -598,11 +606,80 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
             checkpoint.save(tmp, model.ps, trainer.global_step, trainer)
             os.replace(tmp, state)             # a crash mid-write never clobbers the previous state
 
+    secs = train_config.save_summaries_secs if save_summaries_secs is None else save_summaries_secs
+    writer = None
+    if is_chief and train_dir and float(secs or 0) > 0:
+        writer = _TrainSummaries(train_dir, trainer, float(secs), total_configs, input_queue)
+    try:
+        return _train_loop(trainer, model, create_tensor_dict_fn, steps, log_every, is_chief, save_secs, save_state,
+                           writer)
+    finally:
+        if writer is not None:
+            writer.close()
+
+
+class _TrainSummaries:
+    """The chief's event file in train_dir: what the reference's summary_op holds (trainer.py:440-445 a histogram of
+    every model variable, a scalar per loss, TotalLoss; optimizer_builder.py:117 Learning_Rate; slim's supervisor adds
+    global_step/sec, the prefetch queue its fill fraction). Everything is read after Trainer.step() has returned and
+    the device is idle: the histogram kernel only reads the weights, on the main stream."""
+
+    def __init__(self, train_dir, trainer, secs, total_configs, input_queue):
+        from . import summaries
+        self.trainer, self.secs, self.input_queue = trainer, secs, input_queue
+        self.limits = summaries.default_bucket_limits()
+        self.writer = summaries.SummaryWriter(train_dir)
+        self.last = None                                   # time of the previous summary
+        self.mark = (time.time(), trainer.global_step)     # (time, step) global_step/sec counts from
+        if total_configs:                                  # trainer.py:570-574, written once per run
+            names = ("ModelConfig", "TrainConfig", "TrainInputConfig", "EvalConfig", "EvalInputConfig")
+            cfgs = list(total_configs) + [None] * (len(names) - len(total_configs))
+            for name, cfg in zip(names, cfgs):
+                self.writer.add_text(name, summaries.config_md_text(cfg), trainer.global_step)
+            self.writer.flush()
+
+    def due(self, is_log_step):
+        return self.last is None or (is_log_step and time.time() - self.last >= self.secs)
+
+    def write(self, losses):
+        tr, w = self.trainer, self.writer
+        ps = tr.ps
+        if ps.device.type == "cuda":
+            torch.cuda.synchronize()
+        step, now = tr.global_step, time.time()
+        vals = {k: float(v.item()) for k, v in losses.items()}
+        hist = ps.histograms()
+        for k, v in vals.items():
+            w.add_scalar("Loss/" + k, v, step)
+        # the L2 regularisers (slim.l2_regularizer: weight * sum(w^2) / 2 per variable) from the sum of squares the
+        # histogram pass has just returned for every variable: no reduction of its own
+        reg = sum(0.5 * s.weight_decay * float(hist[s.name][0][4]) for s in ps.trainable_specs if s.weight_decay)
+        w.add_scalar("TotalLoss", sum(vals.values()) + reg, step)
+        w.add_scalar("Learning_Rate", tr.lr_fn(step), step)
+        t0, s0 = self.mark
+        if step > s0 and now > t0:
+            w.add_scalar("global_step/sec", (step - s0) / (now - t0), step)
+        if self.input_queue is not None and hasattr(self.input_queue, "queue_fill"):
+            n, cap = self.input_queue.queue_fill()
+            w.add_scalar("queue/fraction_of_%d_full" % cap, n / float(cap), step)
+        for s in ps.specs:
+            moments, counts = hist[s.name]
+            w.add_histogram(s.name, moments, counts, self.limits, step)
+        w.flush()
+        self.last, self.mark = time.time(), (now, step)
+
+    def close(self):
+        self.writer.close()
+
+
+def _train_loop(trainer, model, create_tensor_dict_fn, steps, log_every, is_chief, save_secs, save_state, writer):
+    last_save = time.time()
     log = []
     while steps is None or trainer.global_step < steps:
         t0 = time.time()
         losses = trainer.step(create_tensor_dict_fn())
-        if trainer.global_step % log_every == 0 or trainer.global_step == steps:
+        is_log_step = trainer.global_step % log_every == 0 or trainer.global_step == steps
+        if is_log_step:
             if model.ps.device.type == "cuda":
                 torch.cuda.synchronize()
             total = float(sum(v.item() for v in losses.values()))
@@ -630,6 +707,13 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
             log.append({"step": trainer.global_step, "loss": total, "sec_per_step": dt})
             if is_chief:
                 print("global step %d: loss = %.4f (%.3f sec/step)" % (trainer.global_step, total, dt))
+        if writer is not None and writer.due(is_log_step):
+            try:
+                writer.write(losses)
+            except FloatingPointError:               # a variable holds NaN / inf: the other ranks must not wait for this one
+                if trainer.comm is not None:
+                    trainer.comm.close()
+                raise
         if save_secs and time.time() - last_save >= save_secs:          # trainer.py:464-466 save_interval_secs
             save_state()
             last_save = time.time()
