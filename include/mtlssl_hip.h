@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 16
+#define MTLSSL_ABI_VERSION 17
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -554,34 +554,26 @@ typedef struct {
 } mtlssl_image_desc;         /* 32 bytes */
 int mtlssl_prepare_images(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW, float* out,
                           mtlssl_stream_t stream);
-/* mtlssl_prepare_images with the photometric augmentations of core/preprocessor.py (normalize_image :120,
- * subtract_channel_mean :1490, random_adjust_brightness / contrast / hue / saturation :459-540, random_distort_color
- * :542, random_rgb_to_gray :430, random_pixel_value_scale :347, random_black_patches :1189) and random_horizontal_flip
- * applied at the source resolution before the resize, in config order. `prog` (HOST memory) holds n_ops <= 128 op
- * codes, the same for every image; `params` (device) holds B x P float32 parameters, P the sum of the ops' parameter
- * counts (mtl_ssl_amd.preprocessor: OP_* codes, OP_PARAMS counts, plan() fills them, apply_program restates every op
- * on the host). desc[n].flip mirrors the source before the program. Each contrast op adds two small launches that
- * compute its per-channel means in float64 (row sums, then rows ascending) into `workspace`, which must hold
- * mtlssl_prepare_images_aug_workspace(B, contrast ops, max_H) bytes, max_H >= every image's H. An empty program
- * gives mtlssl_prepare_images's output. */
-int64_t mtlssl_prepare_images_aug_workspace(int B, int n_contrast, int max_H);
-int mtlssl_prepare_images_aug(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
-                              const int32_t* prog, int n_ops, const float* params, int P, int max_H, void* workspace,
-                              int64_t workspace_bytes, float* out, mtlssl_stream_t stream);
-/* mtlssl_prepare_images_aug generalised to programs that move the frame (ABI 13): two more op codes, OP_CROP (y0, x0,
- * h, w: integers held exactly in float32; the identity crop is 0, 0, H, W) and OP_PAD (offset y, offset x, target h,
- * target w, colour mode, r, g, b; mode 0: the given colour, otherwise the mean of the frame the pad receives), for
- * random_crop_image :757, random_pad_image :856, random_crop_pad_image :959 and ssd_random_crop :1548. desc[n].H / W
- * stay the SOURCE size; desc[n].sy / sx are float32(final H / OH), float32(final W / OW) of the frame after the whole
- * program. Each output tap is walked back through the program to a source pixel or a pad colour and takes the ops of
+/* mtlssl_prepare_images with the augmentations of core/preprocessor.py (normalize_image :120, subtract_channel_mean
+ * :1490, random_adjust_brightness / contrast / hue / saturation :459-540, random_distort_color :542, random_rgb_to_gray
+ * :430, random_pixel_value_scale :347, random_black_patches :1189, random_crop_image :757, random_pad_image :856,
+ * random_crop_pad_image :959, ssd_random_crop :1548) and random_horizontal_flip applied at the source resolution before
+ * the resize, in config order. `prog` (HOST memory) holds n_ops <= 128 op codes, the same for every image; `params`
+ * (device) holds B x P float32 parameters, P the sum of the ops' parameter counts (mtl_ssl_amd.preprocessor: OP_*
+ * codes, OP_PARAMS counts, plan() fills them, apply_program restates every op on the host). Two ops move the frame:
+ * OP_CROP (y0, x0, h, w: integers held exactly in float32; the identity crop is 0, 0, H, W) and OP_PAD (offset y,
+ * offset x, target h, target w, colour mode, r, g, b; mode 0: the given colour, otherwise the mean of the frame the pad
+ * receives). desc[n].flip mirrors the source before the program; desc[n].H / W stay the SOURCE size; desc[n].sy / sx
+ * are float32(final H / OH), float32(final W / OW) of the frame after the whole program (the source size when no op
+ * moves it). Each output tap is walked back through the program to a source pixel or a pad colour and takes the ops of
  * the stages it passes, each with the coordinate and frame width of its own stage, so the result equals
  * resize_bilinear_legacy(apply_program(image)) to the bit and no read leaves the H x W source. Every contrast op and
- * every pad op is a mean slot with the two pre-pass launches of mtlssl_prepare_images_aug over the frame of its stage
- * (a pad with a given colour returns at once); `workspace` holds mtlssl_prepare_images_geo_workspace(B, contrast ops +
- * pad ops, max_H) bytes, max_H >= the tallest frame of any stage of any image. A program without crop / pad ops gives
- * mtlssl_prepare_images_aug's output. */
-int64_t mtlssl_prepare_images_geo_workspace(int B, int n_slots, int max_H);
-int mtlssl_prepare_images_geo(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
+ * every pad op is a mean slot: two small launches compute the per-channel means of the frame of its stage in float64
+ * (row sums, then rows ascending; a pad with a given colour returns at once) into `workspace`, which must hold
+ * mtlssl_prepare_images_aug_workspace(B, contrast ops + pad ops, max_H) bytes, max_H >= the tallest frame of any stage
+ * of any image. An empty program gives mtlssl_prepare_images's output. */
+int64_t mtlssl_prepare_images_aug_workspace(int B, int n_slots, int max_H);
+int mtlssl_prepare_images_aug(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
                               const int32_t* prog, int n_ops, const float* params, int P, int max_H, void* workspace,
                               int64_t workspace_bytes, float* out, mtlssl_stream_t stream);
 

@@ -668,23 +668,20 @@ __global__ void k_prepare_images(const uint8_t* __restrict__ pixels, const mtlss
     o[c] = resize_blend((float)r0[x0 * 3 + c], (float)r0[x1 * 3 + c], (float)r1[x0 * 3 + c], (float)r1[x1 * 3 + c],
                         yl, xl);
 }
-// Photometric augmentation inside the preparation (core/preprocessor.py normalize_image, subtract_channel_mean,
+// Augmentation inside the preparation (core/preprocessor.py normalize_image, subtract_channel_mean,
 // random_adjust_{brightness,contrast,saturation,hue}, random_distort_color, random_rgb_to_gray,
-// random_pixel_value_scale, random_black_patches): a program of primitive ops, the same for every image, with B x P
-// float32 parameters, evaluated on each source tap before the legacy resize. The float32 sequence of every op is
-// restated on the host by mtl_ssl_amd.preprocessor.apply_program (op codes and parameter counts: OP_* / OP_PARAMS
-// there); this file is built with -ffp-contract=off, so the two agree to the bit.
+// random_pixel_value_scale, random_black_patches, and the crops and pads further down): a program of primitive ops,
+// the same for every image, with B x P float32 parameters, evaluated on each source tap before the legacy resize. The
+// float32 sequence of every op is restated on the host by mtl_ssl_amd.preprocessor.apply_program (op codes and
+// parameter counts: OP_* / OP_PARAMS there); this file is built with -ffp-contract=off, so the two agree to the bit.
 enum : int {
   kAugFlip = 0, kAugNormalize, kAugSubMean, kAugAdd, kAugContrast, kAugSaturation, kAugHue, kAugClip, kAugGray,
-  kAugPixelScale, kAugPatch, kAugNumOps,               // what mtlssl_prepare_images_aug takes
-  kAugCrop = kAugNumOps, kAugPad, kAugNumGeoOps         // + the ops that move the frame (mtlssl_prepare_images_geo)
+  kAugPixelScale, kAugPatch,
+  kAugCrop, kAugPad,                                   // the ops that move the frame
+  kAugNumOps
 };
 constexpr int kAugMaxOps = 128;
 constexpr uint32_t kAugPixelScaleStream = 0x50584C53u;
-struct AugProgram {            // passed by value: the host validates it and plans the contrast pre-passes
-  int n;
-  int8_t code[kAugMaxOps];
-};
 __host__ __device__ __forceinline__ int aug_nparams(int code) {
   return code == kAugNormalize || code == kAugSubMean || code == kAugPixelScale ? 3
          : code == kAugClip                                                      ? 0
@@ -813,144 +810,47 @@ __device__ __forceinline__ void aug_apply(int code, const float* __restrict__ p,
     default: break;
   }
 }
-// The 3 channels of pixel (y, x) of image n after the first `n_ops` ops, (y, x) in that stage's coordinates (flips
-// mirror the columns). prm: the image's P parameters; means: its contrast means, [contrast op][3].
-__device__ __forceinline__ void aug_pixel(const uint8_t* __restrict__ src, int H, int W, bool src_flip, int y, int x,
-                                          const AugProgram& pr, int n_ops, const float* __restrict__ prm,
-                                          const float* __restrict__ means, float v[3]) {
-  int k = 0, cx = x;
-  for (int i = 0; i < n_ops; ++i) {                      // the column at stage 0
-    const int code = pr.code[i];
-    if (code == kAugFlip && prm[k] != 0.f) cx = W - 1 - cx;
-    k += aug_nparams(code);
-  }
-  const int sx = src_flip ? W - 1 - cx : cx;
-  const uint8_t* s = src + ((int64_t)y * W + sx) * 3;
-  v[0] = (float)s[0]; v[1] = (float)s[1]; v[2] = (float)s[2];
-  k = 0;
-  int nc = 0;
-  for (int i = 0; i < n_ops; ++i) {
-    const int code = pr.code[i];
-    const float* p = prm + k;
-    k += aug_nparams(code);
-    if (code == kAugFlip) {
-      if (p[0] != 0.f) cx = W - 1 - cx;
-      continue;
-    }
-    const float* m = means + nc * 3;
-    nc += code == kAugContrast;
-    aug_apply(code, p, m, y, cx, W, v);
-  }
-}
-// Contrast pre-pass, one launch pair per contrast op of the program (op index `stage`): k_aug_rowsum sums each row
-// of the image after the ops before it in float64, x ascending (one thread per row); k_aug_mean adds the row sums
-// ascending and writes float32(sum / (H * W)) per channel — preprocessor.contrast_mean's order.
-__global__ void k_aug_rowsum(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
-                             AugProgram pr, int stage, const float* __restrict__ params, int P,
-                             const float* __restrict__ means, int n_contrast, int max_H, double* __restrict__ rows) {
-  const int n = blockIdx.y;
-  const int y = blockIdx.x * blockDim.x + threadIdx.x;
-  const mtlssl_image_desc d = desc[n];
-  if (y >= d.H || y >= max_H) return;
-  const uint8_t* src = pixels + d.offset;
-  const float* prm = params + (int64_t)n * P;
-  const float* mn = means + (int64_t)n * n_contrast * 3;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  for (int x = 0; x < d.W; ++x) {
-    float v[3];
-    aug_pixel(src, d.H, d.W, d.flip != 0, y, x, pr, stage, prm, mn, v);
-    s0 += (double)v[0]; s1 += (double)v[1]; s2 += (double)v[2];
-  }
-  double* o = rows + ((int64_t)n * max_H + y) * 3;
-  o[0] = s0; o[1] = s1; o[2] = s2;
-}
-__global__ void k_aug_mean(const mtlssl_image_desc* __restrict__ desc, int slot, int n_contrast, int max_H,
-                           const double* __restrict__ rows, float* __restrict__ means) {
-  const int n = blockIdx.x, c = threadIdx.x;
-  if (c >= 3) return;
-  const mtlssl_image_desc d = desc[n];
-  float m = __builtin_nanf("");                          // an image taller than max_H: visibly wrong, never a stray read
-  if (d.H <= max_H) {
-    const double* r = rows + (int64_t)n * max_H * 3 + c;
-    double t = 0.0;
-    for (int y = 0; y < d.H; ++y) t += r[(int64_t)y * 3];
-    m = (float)(t / (double)((int64_t)d.H * d.W));
-  }
-  means[((int64_t)n * n_contrast + slot) * 3 + c] = m;
-}
-// k_prepare_images with the program applied to each of the four taps before the blend (and to the single tap of the
-// no-resize case). desc.flip mirrors the source before the program, as in k_prepare_images.
-__global__ void k_prepare_images_aug(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
-                                     int OH, int OW, AugProgram pr, const float* __restrict__ params, int P,
-                                     const float* __restrict__ means, int n_contrast, float* __restrict__ out) {
-  const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (p >= (int64_t)OH * OW) return;
-  const int n = blockIdx.y;
-  const mtlssl_image_desc d = desc[n];
-  const int H = d.H, W = d.W;
-  const bool fl = d.flip != 0;
-  const uint8_t* src = pixels + d.offset;
-  const float* prm = params + (int64_t)n * P;
-  const float* mn = means + (int64_t)n * n_contrast * 3;
-  const int oy = (int)(p / OW), ox = (int)(p % OW);
-  float* o = out + ((int64_t)n * OH * OW + p) * 3;
-  if (H == OH && W == OW) {
-    float v[3];
-    aug_pixel(src, H, W, fl, oy, ox, pr, pr.n, prm, mn, v);
-    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
-    return;
-  }
-  int y0, y1, x0, x1;
-  float yl, xl;
-  resize_taps(oy, d.sy, H, y0, y1, yl);
-  resize_taps(ox, d.sx, W, x0, x1, xl);
-  y0 = min(y0, H - 1); x0 = min(x0, W - 1);
-  float tl[3], tr[3], bl[3], br[3];
-  aug_pixel(src, H, W, fl, y0, x0, pr, pr.n, prm, mn, tl);
-  aug_pixel(src, H, W, fl, y0, x1, pr, pr.n, prm, mn, tr);
-  aug_pixel(src, H, W, fl, y1, x0, pr, pr.n, prm, mn, bl);
-  aug_pixel(src, H, W, fl, y1, x1, pr, pr.n, prm, mn, br);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) o[c] = resize_blend(tl[c], tr[c], bl[c], br[c], yl, xl);
-}
-// Geometric augmentation (core/preprocessor.py random_crop_image :757, random_pad_image :856, random_crop_pad_image
-// :959, ssd_random_crop :1548) inside the preparation: kAugCrop (y0, x0, h, w) and kAugPad (offset y, offset x,
-// target h, target w, colour mode, r, g, b) change the frame between ops, so every op has the frame of its own stage.
+// The one evaluator of a program. The geometric ops (core/preprocessor.py random_crop_image :757, random_pad_image :856,
+// random_crop_pad_image :959, ssd_random_crop :1548), kAugCrop (y0, x0, h, w) and kAugPad (offset y, offset x,
+// target h, target w, colour mode, r, g, b), change the frame between ops, so every op has the frame of its own stage.
 // An output tap is walked BACKWARDS from the final frame to the source (a flip mirrors within its stage's width, a crop
 // adds its offset, a pad subtracts its offset); a tap that lands in the padding of op s starts there with the pad
 // colour and takes only the ops after s, any other tap reads the uint8 source and takes them all. No intermediate
 // image exists. Host restatement: preprocessor.apply_program.
-struct GeoProgram {            // passed by value; built and validated by the host entry point
+struct AugProgram {            // passed by value; built and validated by the host entry point
   int n;
   int n_slots;                       // mean slots: one per contrast op and per pad op, in program order
-  int8_t code[kAugMaxOps];
-  uint8_t slot[kAugMaxOps];          // mean slot of op i (contrast and pad ops)
-  uint16_t koff[kAugMaxOps + 1];     // offset of op i's parameters in an image's P
+  // op i in one word, so that a wave fetches it with one scalar load: its code, << 8 its mean slot (contrast and pad
+  // ops), << 16 the offset of its parameters in an image's P
+  uint32_t op[kAugMaxOps];
+  __host__ __device__ int code(int i) const { return (int)(op[i] & 0xFFu); }
+  __host__ __device__ int slot(int i) const { return (int)(op[i] >> 8 & 0xFFu); }
+  __host__ __device__ int koff(int i) const { return (int)(op[i] >> 16); }
 };
 // The frame before each of the first `upto` ops (fh[i] x fw[i], i <= upto; fh[upto] x fw[upto] is the frame after them).
-__device__ __forceinline__ void geo_frames(const GeoProgram& pr, const float* __restrict__ prm, int H, int W, int upto,
+__device__ __forceinline__ void aug_frames(const AugProgram& pr, const float* __restrict__ prm, int H, int W, int upto,
                                            int* fh, int* fw) {
   int h = H, w = W;
   for (int i = 0; i < upto; ++i) {
     fh[i] = h; fw[i] = w;
-    const int code = pr.code[i];
+    const int code = pr.code(i);
     if (code == kAugCrop || code == kAugPad) {
-      h = (int)prm[pr.koff[i] + 2];
-      w = (int)prm[pr.koff[i] + 3];
+      h = (int)prm[pr.koff(i) + 2];
+      w = (int)prm[pr.koff(i) + 3];
     }
   }
   fh[upto] = h; fw[upto] = w;
 }
-// The 3 channels of pixel (y, x) of the frame after the first `n_ops` ops. fh / fw: geo_frames of this image; means:
+// The 3 channels of pixel (y, x) of the frame after the first `n_ops` ops. fh / fw: aug_frames of this image; means:
 // the image's mean slots [slot][3], filled for every slot before op n_ops.
-__device__ __forceinline__ void geo_pixel(const uint8_t* __restrict__ src, int H, int W, bool src_flip, int y, int x,
-                                          const GeoProgram& pr, int n_ops, const float* __restrict__ prm,
+__device__ __forceinline__ void aug_pixel(const uint8_t* __restrict__ src, int H, int W, bool src_flip, int y, int x,
+                                          const AugProgram& pr, int n_ops, const float* __restrict__ prm,
                                           const float* __restrict__ means, const int* fh, const int* fw, float v[3]) {
   int start = 0;
   bool padding = false;
   for (int i = n_ops - 1; i >= 0; --i) {
-    const int code = pr.code[i];
-    const float* p = prm + pr.koff[i];
+    const int code = pr.code(i);
+    const float* p = prm + pr.koff(i);
     if (code == kAugFlip) {
       if (p[0] != 0.f) x = fw[i] - 1 - x;
     } else if (code == kAugCrop) {
@@ -958,7 +858,7 @@ __device__ __forceinline__ void geo_pixel(const uint8_t* __restrict__ src, int H
     } else if (code == kAugPad) {
       const int yy = y - (int)p[0], xx = x - (int)p[1];
       if (yy < 0 || yy >= fh[i] || xx < 0 || xx >= fw[i]) {          // in the padding of op i: (y, x) stays in ITS frame
-        const float* c = p[4] != 0.f ? means + pr.slot[i] * 3 : p + 5;
+        const float* c = p[4] != 0.f ? means + pr.slot(i) * 3 : p + 5;
         v[0] = c[0]; v[1] = c[1]; v[2] = c[2];
         start = i + 1;
         padding = true;
@@ -973,9 +873,10 @@ __device__ __forceinline__ void geo_pixel(const uint8_t* __restrict__ src, int H
     const uint8_t* s = src + ((int64_t)sy * W + (src_flip ? W - 1 - cx : cx)) * 3;
     v[0] = (float)s[0]; v[1] = (float)s[1]; v[2] = (float)s[2];
   }
-  for (int i = start; i < n_ops; ++i) {
-    const int code = pr.code[i];
-    const float* p = prm + pr.koff[i];
+  for (int i = 0; i < n_ops; ++i) {
+    if (i < start) continue;       // `start` differs between lanes; counting from 0 keeps i and the op's loads wave-uniform
+    const int code = pr.code(i);
+    const float* p = prm + pr.koff(i);
     if (code == kAugFlip) {
       if (p[0] != 0.f) x = fw[i] - 1 - x;
     } else if (code == kAugCrop) {
@@ -983,27 +884,29 @@ __device__ __forceinline__ void geo_pixel(const uint8_t* __restrict__ src, int H
     } else if (code == kAugPad) {
       y += (int)p[0]; x += (int)p[1];
     } else {
-      aug_apply(code, p, means + pr.slot[i] * 3, y, x, fw[i], v);
+      aug_apply(code, p, means + pr.slot(i) * 3, y, x, fw[i], v);
     }
   }
 }
-// Pre-pass of one mean slot (op `stage`: a contrast op, or a pad whose colour is the mean of its input frame), as
-// k_aug_rowsum / k_aug_mean but over the frame of that stage, which may hold padding of an earlier slot. A pad with a
-// given colour skips the work.
-__device__ __forceinline__ bool geo_slot_unused(const GeoProgram& pr, int stage, const float* __restrict__ prm) {
-  return pr.code[stage] == kAugPad && prm[pr.koff[stage] + 4] == 0.f;
+// Pre-pass of one mean slot (op `stage`: a contrast op, or a pad whose colour is the mean of its input frame), one
+// launch pair per slot: k_aug_rowsum sums each row of the frame of that stage (the image after the ops before it, which
+// may hold padding of an earlier slot) in float64, x ascending (one thread per row); k_aug_mean adds the row sums
+// ascending and writes float32(sum / (H * W)) per channel: preprocessor.contrast_mean's order. A pad with a given
+// colour skips the work.
+__device__ __forceinline__ bool aug_slot_unused(const AugProgram& pr, int stage, const float* __restrict__ prm) {
+  return pr.code(stage) == kAugPad && prm[pr.koff(stage) + 4] == 0.f;
 }
-__global__ void k_geo_rowsum(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
-                             GeoProgram pr, int stage, const float* __restrict__ params, int P,
+__global__ void k_aug_rowsum(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
+                             AugProgram pr, int stage, const float* __restrict__ params, int P,
                              const float* __restrict__ means, int max_H, double* __restrict__ rows) {
   __shared__ int fh[kAugMaxOps + 1], fw[kAugMaxOps + 1];
   const int n = blockIdx.y;
   const int y = blockIdx.x * blockDim.x + threadIdx.x;
   const mtlssl_image_desc d = desc[n];
   const float* prm = params + (int64_t)n * P;
-  if (threadIdx.x == 0) geo_frames(pr, prm, d.H, d.W, stage, fh, fw);
+  if (threadIdx.x == 0) aug_frames(pr, prm, d.H, d.W, stage, fh, fw);
   __syncthreads();
-  if (geo_slot_unused(pr, stage, prm)) return;
+  if (aug_slot_unused(pr, stage, prm)) return;
   const int FH = fh[stage], FW = fw[stage];
   if (y >= FH || y >= max_H) return;
   const uint8_t* src = pixels + d.offset;
@@ -1011,26 +914,23 @@ __global__ void k_geo_rowsum(const uint8_t* __restrict__ pixels, const mtlssl_im
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
   for (int x = 0; x < FW; ++x) {
     float v[3];
-    geo_pixel(src, d.H, d.W, d.flip != 0, y, x, pr, stage, prm, mn, fh, fw, v);
+    aug_pixel(src, d.H, d.W, d.flip != 0, y, x, pr, stage, prm, mn, fh, fw, v);
     s0 += (double)v[0]; s1 += (double)v[1]; s2 += (double)v[2];
   }
   double* o = rows + ((int64_t)n * max_H + y) * 3;
   o[0] = s0; o[1] = s1; o[2] = s2;
 }
-__global__ void k_geo_mean(const mtlssl_image_desc* __restrict__ desc, GeoProgram pr, int stage,
+__global__ void k_aug_mean(const mtlssl_image_desc* __restrict__ desc, AugProgram pr, int stage,
                            const float* __restrict__ params, int P, int max_H, const double* __restrict__ rows,
                            float* __restrict__ means) {
+  __shared__ int fh[kAugMaxOps + 1], fw[kAugMaxOps + 1];
   const int n = blockIdx.x, c = threadIdx.x;
-  if (c >= 3) return;
   const mtlssl_image_desc d = desc[n];
   const float* prm = params + (int64_t)n * P;
-  if (geo_slot_unused(pr, stage, prm)) return;
-  int FH = d.H, FW = d.W;
-  for (int i = 0; i < stage; ++i)
-    if (pr.code[i] == kAugCrop || pr.code[i] == kAugPad) {
-      FH = (int)prm[pr.koff[i] + 2];
-      FW = (int)prm[pr.koff[i] + 3];
-    }
+  if (c == 0) aug_frames(pr, prm, d.H, d.W, stage, fh, fw);
+  __syncthreads();
+  if (c >= 3 || aug_slot_unused(pr, stage, prm)) return;
+  const int FH = fh[stage], FW = fw[stage];
   float m = __builtin_nanf("");                          // a frame taller than max_H: visibly wrong, never a stray read
   if (FH <= max_H) {
     const double* r = rows + (int64_t)n * max_H * 3 + c;
@@ -1038,18 +938,20 @@ __global__ void k_geo_mean(const mtlssl_image_desc* __restrict__ desc, GeoProgra
     for (int y = 0; y < FH; ++y) t += r[(int64_t)y * 3];
     m = (float)(t / (double)((int64_t)FH * FW));
   }
-  means[((int64_t)n * pr.n_slots + pr.slot[stage]) * 3 + c] = m;
+  means[((int64_t)n * pr.n_slots + pr.slot(stage)) * 3 + c] = m;
 }
-// k_prepare_images_aug over the final frame of the program: desc.sy / sx are float32(final H / OH), float32(final W /
-// OW), and the no-resize branch is taken when the FINAL frame equals OH x OW.
-__global__ void k_prepare_images_geo(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
-                                     int OH, int OW, GeoProgram pr, const float* __restrict__ params, int P,
+// k_prepare_images with the program applied to each of the four taps before the blend (and to the single tap of the
+// no-resize case), over the final frame of the program: desc.sy / sx are float32(final H / OH), float32(final W / OW),
+// and the no-resize branch is taken when the FINAL frame equals OH x OW. desc.flip mirrors the source before the
+// program, as in k_prepare_images.
+__global__ void k_prepare_images_aug(const uint8_t* __restrict__ pixels, const mtlssl_image_desc* __restrict__ desc,
+                                     int OH, int OW, AugProgram pr, const float* __restrict__ params, int P,
                                      const float* __restrict__ means, float* __restrict__ out) {
   __shared__ int fh[kAugMaxOps + 1], fw[kAugMaxOps + 1];
   const int n = blockIdx.y;
   const mtlssl_image_desc d = desc[n];
   const float* prm = params + (int64_t)n * P;
-  if (threadIdx.x == 0) geo_frames(pr, prm, d.H, d.W, pr.n, fh, fw);
+  if (threadIdx.x == 0) aug_frames(pr, prm, d.H, d.W, pr.n, fh, fw);
   __syncthreads();
   const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (p >= (int64_t)OH * OW) return;
@@ -1061,7 +963,7 @@ __global__ void k_prepare_images_geo(const uint8_t* __restrict__ pixels, const m
   float* o = out + ((int64_t)n * OH * OW + p) * 3;
   if (FH == OH && FW == OW) {
     float v[3];
-    geo_pixel(src, H, W, fl, oy, ox, pr, pr.n, prm, mn, fh, fw, v);
+    aug_pixel(src, H, W, fl, oy, ox, pr, pr.n, prm, mn, fh, fw, v);
     o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
     return;
   }
@@ -1071,10 +973,10 @@ __global__ void k_prepare_images_geo(const uint8_t* __restrict__ pixels, const m
   resize_taps(ox, d.sx, FW, x0, x1, xl);
   y0 = min(y0, FH - 1); x0 = min(x0, FW - 1);
   float tl[3], tr[3], bl[3], br[3];
-  geo_pixel(src, H, W, fl, y0, x0, pr, pr.n, prm, mn, fh, fw, tl);
-  geo_pixel(src, H, W, fl, y0, x1, pr, pr.n, prm, mn, fh, fw, tr);
-  geo_pixel(src, H, W, fl, y1, x0, pr, pr.n, prm, mn, fh, fw, bl);
-  geo_pixel(src, H, W, fl, y1, x1, pr, pr.n, prm, mn, fh, fw, br);
+  aug_pixel(src, H, W, fl, y0, x0, pr, pr.n, prm, mn, fh, fw, tl);
+  aug_pixel(src, H, W, fl, y0, x1, pr, pr.n, prm, mn, fh, fw, tr);
+  aug_pixel(src, H, W, fl, y1, x0, pr, pr.n, prm, mn, fh, fw, bl);
+  aug_pixel(src, H, W, fl, y1, x1, pr, pr.n, prm, mn, fh, fw, br);
 #pragma unroll
   for (int c = 0; c < 3; ++c) o[c] = resize_blend(tl[c], tr[c], bl[c], br[c], yl, xl);
 }
@@ -1740,9 +1642,9 @@ int mtlssl_prepare_images(const uint8_t* pixels, const mtlssl_image_desc* desc, 
                      desc, OH, OW, out);
   return check_launch("prepare_images");
 }
-int64_t mtlssl_prepare_images_aug_workspace(int B, int n_contrast, int max_H) {
-  if (B <= 0 || n_contrast <= 0) return 0;
-  const int64_t means = ((int64_t)B * n_contrast * 3 * 4 + 255) / 256 * 256;
+int64_t mtlssl_prepare_images_aug_workspace(int B, int n_slots, int max_H) {
+  if (B <= 0 || n_slots <= 0) return 0;
+  const int64_t means = ((int64_t)B * n_slots * 3 * 4 + 255) / 256 * 256;
   return means + (int64_t)B * max_H * 3 * 8;
 }
 int mtlssl_prepare_images_aug(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
@@ -1752,80 +1654,37 @@ int mtlssl_prepare_images_aug(const uint8_t* pixels, const mtlssl_image_desc* de
   MTLSSL_REQUIRE(n_ops >= 0 && n_ops <= kAugMaxOps, "prepare_images_aug: %d ops, at most %d", n_ops, kAugMaxOps);
   MTLSSL_REQUIRE(n_ops == 0 || prog, "prepare_images_aug: null program");
   AugProgram pr;
-  pr.n = n_ops;
-  int need = 0, n_contrast = 0;
-  for (int i = 0; i < n_ops; ++i) {
-    MTLSSL_REQUIRE(prog[i] >= 0 && prog[i] < kAugNumOps, "prepare_images_aug: bad op code %d at op %d", prog[i], i);
-    pr.code[i] = (int8_t)prog[i];
-    need += aug_nparams(prog[i]);
-    n_contrast += prog[i] == kAugContrast;
-  }
-  MTLSSL_REQUIRE(P == need, "prepare_images_aug: the program takes %d parameters per image, P = %d", need, P);
-  MTLSSL_REQUIRE(P == 0 || B == 0 || params, "prepare_images_aug: null parameters");
-  const int64_t ws = mtlssl_prepare_images_aug_workspace(B, n_contrast, max_H);
-  MTLSSL_REQUIRE(n_contrast == 0 || (max_H >= 1 && workspace && workspace_bytes >= ws),
-                 "prepare_images_aug: %d contrast ops need max_H >= 1 and %lld workspace bytes, got max_H = %d and %lld",
-                 n_contrast, (long long)ws, max_H, (long long)workspace_bytes);
-  if (!B) return MTLSSL_OK;
-  float* means = static_cast<float*>(workspace);
-  double* rows = n_contrast ? reinterpret_cast<double*>(static_cast<char*>(workspace) + (ws - (int64_t)B * max_H * 24))
-                            : nullptr;
-  for (int i = 0, slot = 0; i < n_ops; ++i) {
-    if (pr.code[i] != kAugContrast) continue;
-    hipLaunchKernelGGL(k_aug_rowsum, dim3((unsigned)cdiv(max_H, 64), (unsigned)B), dim3(64), 0, S(stream), pixels,
-                       desc, pr, i, params, P, means, n_contrast, max_H, rows);
-    hipLaunchKernelGGL(k_aug_mean, dim3((unsigned)B), dim3(64), 0, S(stream), desc, slot, n_contrast, max_H, rows,
-                       means);
-    ++slot;
-  }
-  const int64_t pix = (int64_t)OH * OW;
-  hipLaunchKernelGGL(k_prepare_images_aug, dim3((unsigned)cdiv(pix, 256), (unsigned)B), dim3(256), 0, S(stream),
-                     pixels, desc, OH, OW, pr, params, P, means, n_contrast, out);
-  return check_launch("prepare_images_aug");
-}
-int64_t mtlssl_prepare_images_geo_workspace(int B, int n_slots, int max_H) {
-  return mtlssl_prepare_images_aug_workspace(B, n_slots, max_H);
-}
-int mtlssl_prepare_images_geo(const uint8_t* pixels, const mtlssl_image_desc* desc, int B, int OH, int OW,
-                              const int32_t* prog, int n_ops, const float* params, int P, int max_H, void* workspace,
-                              int64_t workspace_bytes, float* out, mtlssl_stream_t stream) {
-  MTLSSL_REQUIRE(B >= 0 && B <= 65535 && OH > 0 && OW > 0, "prepare_images_geo: bad geometry");
-  MTLSSL_REQUIRE(n_ops >= 0 && n_ops <= kAugMaxOps, "prepare_images_geo: %d ops, at most %d", n_ops, kAugMaxOps);
-  MTLSSL_REQUIRE(n_ops == 0 || prog, "prepare_images_geo: null program");
-  GeoProgram pr;
   memset(&pr, 0, sizeof(pr));
   pr.n = n_ops;
   int need = 0, n_slots = 0;
   for (int i = 0; i < n_ops; ++i) {
-    MTLSSL_REQUIRE(prog[i] >= 0 && prog[i] < kAugNumGeoOps, "prepare_images_geo: bad op code %d at op %d", prog[i], i);
-    pr.code[i] = (int8_t)prog[i];
-    pr.koff[i] = (uint16_t)need;
+    MTLSSL_REQUIRE(prog[i] >= 0 && prog[i] < kAugNumOps, "prepare_images_aug: bad op code %d at op %d", prog[i], i);
+    pr.op[i] = (uint32_t)prog[i] | (uint32_t)need << 16;
     need += aug_nparams(prog[i]);
-    if (prog[i] == kAugContrast || prog[i] == kAugPad) pr.slot[i] = (uint8_t)n_slots++;
+    if (prog[i] == kAugContrast || prog[i] == kAugPad) pr.op[i] |= (uint32_t)n_slots++ << 8;
   }
-  pr.koff[n_ops] = (uint16_t)need;
   pr.n_slots = n_slots;
-  MTLSSL_REQUIRE(P == need, "prepare_images_geo: the program takes %d parameters per image, P = %d", need, P);
-  MTLSSL_REQUIRE(P == 0 || B == 0 || params, "prepare_images_geo: null parameters");
-  const int64_t ws = mtlssl_prepare_images_geo_workspace(B, n_slots, max_H);
+  MTLSSL_REQUIRE(P == need, "prepare_images_aug: the program takes %d parameters per image, P = %d", need, P);
+  MTLSSL_REQUIRE(P == 0 || B == 0 || params, "prepare_images_aug: null parameters");
+  const int64_t ws = mtlssl_prepare_images_aug_workspace(B, n_slots, max_H);
   MTLSSL_REQUIRE(n_slots == 0 || (max_H >= 1 && workspace && workspace_bytes >= ws),
-                 "prepare_images_geo: %d mean slots need max_H >= 1 and %lld workspace bytes, got max_H = %d and %lld",
+                 "prepare_images_aug: %d mean slots need max_H >= 1 and %lld workspace bytes, got max_H = %d and %lld",
                  n_slots, (long long)ws, max_H, (long long)workspace_bytes);
   if (!B) return MTLSSL_OK;
   float* means = static_cast<float*>(workspace);
   double* rows = n_slots ? reinterpret_cast<double*>(static_cast<char*>(workspace) + (ws - (int64_t)B * max_H * 24))
                          : nullptr;
   for (int i = 0; i < n_ops; ++i) {                      // slots in program order: a later one may read an earlier one
-    if (pr.code[i] != kAugContrast && pr.code[i] != kAugPad) continue;
-    hipLaunchKernelGGL(k_geo_rowsum, dim3((unsigned)cdiv(max_H, 64), (unsigned)B), dim3(64), 0, S(stream), pixels,
+    if (prog[i] != kAugContrast && prog[i] != kAugPad) continue;
+    hipLaunchKernelGGL(k_aug_rowsum, dim3((unsigned)cdiv(max_H, 64), (unsigned)B), dim3(64), 0, S(stream), pixels,
                        desc, pr, i, params, P, means, max_H, rows);
-    hipLaunchKernelGGL(k_geo_mean, dim3((unsigned)B), dim3(64), 0, S(stream), desc, pr, i, params, P, max_H, rows,
+    hipLaunchKernelGGL(k_aug_mean, dim3((unsigned)B), dim3(64), 0, S(stream), desc, pr, i, params, P, max_H, rows,
                        means);
   }
   const int64_t pix = (int64_t)OH * OW;
-  hipLaunchKernelGGL(k_prepare_images_geo, dim3((unsigned)cdiv(pix, 256), (unsigned)B), dim3(256), 0, S(stream),
+  hipLaunchKernelGGL(k_prepare_images_aug, dim3((unsigned)cdiv(pix, 256), (unsigned)B), dim3(256), 0, S(stream),
                      pixels, desc, OH, OW, pr, params, P, means, out);
-  return check_launch("prepare_images_geo");
+  return check_launch("prepare_images_aug");
 }
 int mtlssl_resize_bilinear_bwd(const float* dy, float* dx, int N, int H, int W, int C, int OH,
                                int OW, mtlssl_stream_t stream) {

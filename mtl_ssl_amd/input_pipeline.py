@@ -17,11 +17,10 @@ The reference overlaps its input with the step through parallel readers and pref
   flushes, same remainder).
 * On a GPU, a batch is packed into a pinned staging slot (descriptors + op parameters + uint8 pixels), copied in one
   H2D copy and turned into the float32 [B,OH,OW,3] batch on a stream of its own: `ops.prepare_images` when the
-  options are flips only, `ops.prepare_images_aug` (the op program before the resize) otherwise, or
-  `ops.prepare_images_geo` when the program crops or pads. The consumer's
-  stream waits on the batch's event at hand-out. Copies and kernels are launched from the consumer's thread, so no
-  second Python thread competes with the step's launch thread. On the CPU, the host preparer runs the numpy path
-  (`preprocessor.apply_program`, then `resize_bilinear_legacy`).
+  options are flips only, `ops.prepare_images_aug` (the op program before the resize, crops and pads included)
+  otherwise. The consumer's stream waits on the batch's event at hand-out. Copies and kernels are launched from the
+  consumer's thread, so no second Python thread competes with the step's launch thread. On the CPU, the host preparer
+  runs the numpy path (`preprocessor.apply_program`, then `resize_bilinear_legacy`).
 """
 import collections
 import multiprocessing
@@ -135,9 +134,9 @@ class _HostPreparer:
 class _DevicePreparer:
     """Pinned staging ring -> one H2D copy + one mtlssl_prepare_images launch per batch on a dedicated stream (a
     program of flips only: the net flip goes into the descriptor), or mtlssl_prepare_images_aug with the batch's
-    [B, P] op parameters staged between the descriptors and the pixels; a program with a crop or a pad goes to
-    mtlssl_prepare_images_geo, with the scales of each image's final frame in its descriptor. The whole decoded image
-    is copied even when a crop keeps a part of it."""
+    [B, P] op parameters staged between the descriptors and the pixels and the scales of each image's final frame (the
+    source size unless the program crops or pads) in its descriptor. The whole decoded image is copied even when a crop
+    keeps a part of it."""
 
     _ALIGN = 256
 
@@ -147,7 +146,6 @@ class _DevicePreparer:
         self.codes = list(codes)
         self.P = preprocessor.num_params(self.codes)
         self.flips_only = all(c == preprocessor.OP_FLIP for c in self.codes)
-        self.geo = preprocessor.has_geometric(self.codes)
         self.device = device
         self.stream = torch.cuda.Stream(device)
         self.slots = [None] * slots          # pinned uint8 staging buffers
@@ -164,7 +162,7 @@ class _DevicePreparer:
         else:
             flips, P = [False] * len(items), self.P
         desc, nbytes = ops.image_descs([ex["image"].shape[:2] for ex, _ in items], flips, OH, OW,
-                                       [frame for _, (_, frame) in items] if self.geo else None)
+                                       [frame for _, (_, frame) in items])
         align = lambda n: -(-n // self._ALIGN) * self._ALIGN
         poff = align(desc.nbytes)
         head = poff + align(len(items) * P * 4)
@@ -195,14 +193,11 @@ class _DevicePreparer:
                 ev[1].record(self.stream)
             if self.flips_only:
                 out = ops.prepare_images(dev[head:], dev[:desc.nbytes], len(items), OH, OW)
-            elif self.geo:
+            else:
                 max_H = max(h for ex, (p, _) in items
                             for h, _ in preprocessor.stage_frames(self.codes, p, *ex["image"].shape[:2]))
-                out = ops.prepare_images_geo(dev[head:], dev[:desc.nbytes], len(items), OH, OW, self.codes,
-                                             dev[poff:head], P, max_H)
-            else:
                 out = ops.prepare_images_aug(dev[head:], dev[:desc.nbytes], len(items), OH, OW, self.codes,
-                                             dev[poff:head], P, max(ex["image"].shape[0] for ex, _ in items))
+                                             dev[poff:head], P, max_H)
             done = torch.cuda.Event(enable_timing=self.profile)
             done.record(self.stream)
         self.events[s] = done

@@ -1339,8 +1339,9 @@ IMAGE_DESC = np.dtype({"names": ["offset", "H", "W", "flip", "sy", "sx", "pad"],
 def image_descs(shapes, flips, OH, OW, frames=None):
     """Descriptors of uint8 [H,W,3] images packed back to back -> (IMAGE_DESC array, total pixel bytes). The scales
     are float32(H / OH), float32(W / OW): the rounding of preprocessor.resize_bilinear_legacy. `frames`: the final
-    (height, width) of each image's augmentation program when it moves the frame (prepare_images_geo); the scales are
-    then those of the final frame, H and W stay the source size."""
+    (height, width) of each image's augmentation program (prepare_images_aug); the scales are then those of the final
+    frame, H and W stay the source size. A program that does not move the frame ends in the source size, so passing its
+    frames changes nothing."""
     d = np.zeros(len(shapes), IMAGE_DESC)
     off = 0
     for i, ((H, W), f) in enumerate(zip(shapes, flips)):
@@ -1368,30 +1369,11 @@ def prepare_images(pixels, desc, B, OH, OW, out=None):
 def prepare_images_aug(pixels, desc, B, OH, OW, prog, params, P, max_H, out=None):
     """prepare_images with an augmentation program applied at the source resolution before the resize
     (mtlssl_prepare_images_aug) = resize_bilinear_legacy(preprocessor.apply_program(image)) per image. prog: the op
-    codes of preprocessor.program (a host sequence, checked by the library); params: a device tensor holding the
-    B x P float32 parameters of preprocessor.plan, 4-byte aligned; max_H >= the H of every image (it sizes the
-    contrast-mean workspace)."""
-    assert pixels.is_cuda and pixels.dtype == torch.uint8 and desc.is_cuda and desc.dtype == torch.uint8
-    assert desc.numel() >= B * IMAGE_DESC.itemsize and desc.data_ptr() % 8 == 0
-    assert params.is_cuda and params.data_ptr() % 4 == 0
-    assert params.numel() * params.element_size() >= B * P * 4, "params hold fewer than B x P floats"
-    from .preprocessor import OP_CONTRAST
-    codes = np.ascontiguousarray(prog, np.int32).reshape(-1)
-    if out is None:
-        out = torch.empty((B, OH, OW, 3), dtype=f32, device=pixels.device)
-    assert tuple(out.shape) == (B, OH, OW, 3)
-    nbytes = int(lib().prepare_images_aug_workspace(B, int((codes == OP_CONTRAST).sum()), int(max_H)))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=pixels.device) if nbytes else None
-    lib().prepare_images_aug(ptr(pixels), ptr(desc), B, OH, OW, codes.ctypes.data, len(codes), ptr(params), P,
-                             int(max_H), ptr(ws), nbytes, ptr(_chk(out)), _stream())
-    return out
-
-
-def prepare_images_geo(pixels, desc, B, OH, OW, prog, params, P, max_H, out=None):
-    """prepare_images_aug for programs with OP_CROP / OP_PAD (mtlssl_prepare_images_geo) =
-    resize_bilinear_legacy(preprocessor.apply_program(image)) per image. desc: image_descs(..., frames=the final
-    frames); max_H >= the height of every stage's frame of every image (max over preprocessor.stage_frames): it sizes
-    the workspace of the mean slots (contrast ops and pads)."""
+    codes of preprocessor.program (a host sequence, checked by the library), OP_CROP / OP_PAD included; params: a device
+    tensor holding the B x P float32 parameters of preprocessor.plan, 4-byte aligned; desc: image_descs(...,
+    frames=the final frames) when the program moves the frame; max_H >= the height of every stage's frame of every
+    image (max over preprocessor.stage_frames; the H of every image when no op moves the frame): it sizes the
+    workspace of the mean slots (contrast ops and pads)."""
     assert pixels.is_cuda and pixels.dtype == torch.uint8 and desc.is_cuda and desc.dtype == torch.uint8
     assert desc.numel() >= B * IMAGE_DESC.itemsize and desc.data_ptr() % 8 == 0
     assert params.is_cuda and params.data_ptr() % 4 == 0
@@ -1402,9 +1384,9 @@ def prepare_images_geo(pixels, desc, B, OH, OW, prog, params, P, max_H, out=None
         out = torch.empty((B, OH, OW, 3), dtype=f32, device=pixels.device)
     assert tuple(out.shape) == (B, OH, OW, 3)
     slots = int(((codes == OP_CONTRAST) | (codes == OP_PAD)).sum())
-    nbytes = int(lib().prepare_images_geo_workspace(B, slots, int(max_H)))
+    nbytes = int(lib().prepare_images_aug_workspace(B, slots, int(max_H)))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pixels.device) if nbytes else None
-    lib().prepare_images_geo(ptr(pixels), ptr(desc), B, OH, OW, codes.ctypes.data, len(codes), ptr(params), P,
+    lib().prepare_images_aug(ptr(pixels), ptr(desc), B, OH, OW, codes.ctypes.data, len(codes), ptr(params), P,
                              int(max_H), ptr(ws), nbytes, ptr(_chk(out)), _stream())
     return out
 

@@ -305,10 +305,6 @@ def program(steps):
     return codes
 
 
-def has_geometric(codes):
-    return any(c in GEOMETRIC_OPS for c in codes)
-
-
 def num_params(codes):
     return sum(OP_PARAMS[c] for c in codes)
 
@@ -624,9 +620,10 @@ def jitter_boxes(boxes, seed, ratio):
 
 
 def contrast_mean(x):
-    """Per-channel mean of a float32 [H,W,3] image for adjust_contrast: float64 sums, x ascending within a row, then
-    the row sums ascending, divided by H*W and rounded once to float32 (the device pre-pass k_aug_rowsum /
-    k_aug_mean adds in the same order). np.cumsum adds sequentially; np.sum would add pairwise."""
+    """Per-channel mean of a float32 [H,W,3] frame for adjust_contrast and the mean-coloured pad: float64 sums, x
+    ascending within a row, then the row sums ascending, divided by H*W and rounded once to float32 (the device pre-pass
+    of a mean slot, k_aug_rowsum / k_aug_mean, adds in the same order). np.cumsum adds sequentially; np.sum would add
+    pairwise."""
     H, W = x.shape[:2]
     rows = np.cumsum(np.asarray(x, np.float64), axis=1)[:, -1, :]
     return (np.cumsum(rows, axis=0)[-1] / float(H * W)).astype(np.float32)

@@ -1,4 +1,4 @@
-"""Photometric augmentation on the GPU: mtlssl_prepare_images_aug against the host restatement
+"""Photometric programs on the GPU: mtlssl_prepare_images_aug, the one program evaluator, against the host restatement
 resize_bilinear_legacy(preprocessor.apply_program(float32(img))) bit for bit (each op alone, chains with flips around
 the position-dependent ops, two contrast ops, both random_distort_color orderings, odd sizes, the no-resize case,
 up to 8 images per launch), the empty program against mtlssl_prepare_images, the pipeline's device batches against
@@ -135,6 +135,8 @@ def test_bad_programs_are_refused(ops):
     img = np.zeros((4, 5, 3), np.uint8)
     with pytest.raises(MtlsslError, match="bad op code 99"):
         _device(ops, [img], [0, 99], [np.zeros(2, np.float32)], 4, 5)
+    with pytest.raises(MtlsslError, match="bad op code 13"):          # the first code past OP_PAD
+        _device(ops, [img], [13], [np.zeros(1, np.float32)], 4, 5)
     with pytest.raises(MtlsslError, match="takes 3 parameters per image, P = 2"):
         _device(ops, [img], [1], [np.zeros(2, np.float32)], 4, 5)
 

@@ -1,7 +1,7 @@
-"""mtlssl_prepare_images_geo (crop / pad ops inside the device image preparation) against the host restatement
+"""mtlssl_prepare_images_aug with crop / pad ops inside the device image preparation against the host restatement
 resize_bilinear_legacy(apply_program(...)), bit for bit: B = 3 sources of 37x53, 64x40 and 33x33 with parameters from
 plan() on fixed draws, every program once with a resize to 24 x 40 and once with the output equal to the final frame
-(the no-resize branch); a program without geometric ops must equal mtlssl_prepare_images_aug."""
+(the no-resize branch); a program without geometric ops must give the same output with and without its frames."""
 import numpy as np
 import pytest
 import torch
@@ -59,14 +59,14 @@ def _planned(name, seed=11):
     return codes, imgs, params, frames, tallest
 
 
-def _device(ops, fn, imgs, codes, params, OH, OW, frames, max_H):
+def _device(ops, imgs, codes, params, OH, OW, frames, max_H):
     desc, _ = ops.image_descs([a.shape[:2] for a in imgs], [False] * len(imgs), OH, OW, frames)
     dev = torch.device("cuda")
     d = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
     px = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(dev)
     n = len(params[0])
     prm = torch.from_numpy(np.stack(params).astype(np.float32) if n else np.zeros((1,), np.float32)).to(dev)
-    return fn(px, d, len(imgs), OH, OW, codes, prm, n, max_H).cpu().numpy()
+    return ops.prepare_images_aug(px, d, len(imgs), OH, OW, codes, prm, n, max_H).cpu().numpy()
 
 
 @pytest.mark.parametrize("name", list(PROGRAMS))
@@ -89,13 +89,13 @@ def test_geo_matches_the_host_restatement(ops, name):
         assert any(p[4] != 0 for p in params) and any(p[13] != 0 for p in params)
     # one launch for the three images, resized
     OH, OW = 24, 40
-    got = _device(ops, ops.prepare_images_geo, imgs, codes, params, OH, OW, frames, max(tallest))
+    got = _device(ops, imgs, codes, params, OH, OW, frames, max(tallest))
     for i, h in enumerate(host):
         np.testing.assert_array_equal(got[i], P.resize_bilinear_legacy(h, OH, OW), err_msg="%s image %d" % (name, i))
     # the no-resize branch: the output is the final frame
     for i, h in enumerate(host):
-        got = _device(ops, ops.prepare_images_geo, imgs[i:i + 1], codes, params[i:i + 1], frames[i][0], frames[i][1],
-                      frames[i:i + 1], tallest[i])
+        got = _device(ops, imgs[i:i + 1], codes, params[i:i + 1], frames[i][0], frames[i][1], frames[i:i + 1],
+                      tallest[i])
         np.testing.assert_array_equal(got[0], h, err_msg="%s image %d unresized" % (name, i))
 
 
@@ -110,10 +110,9 @@ def test_a_program_without_geometric_ops_equals_prepare_images_aug(ops):
     params = [P.plan(steps, rng.uniform(size=P.draw_count(steps)), h, w, BOXES)[0] for h, w in SHAPES]
     assert any(p[3] != 0 for p in params)
     max_H = max(h for h, _ in SHAPES)
-    for OH, OW in ((24, 40), (37, 53)):
-        a = _device(ops, ops.prepare_images_aug, imgs, codes, params, OH, OW, None, max_H)
-        b = _device(ops, ops.prepare_images_geo, imgs, codes, params, OH, OW, None, max_H)
-        np.testing.assert_array_equal(a, b)
-    with pytest.raises(Exception, match="bad op code"):          # the photometric entry point still refuses a crop
-        _device(ops, ops.prepare_images_aug, imgs, [P.OP_CROP], [np.float32([0, 0, h, w]) for h, w in SHAPES], 24, 40,
-                None, max_H)
+    host = [P.apply_program(np.float32(a), codes, p) for a, p in zip(imgs, params)]
+    for OH, OW in ((24, 40), (37, 53)):          # at 37 x 53 image 0 takes the no-resize branch, the other two are resized
+        got = _device(ops, imgs, codes, params, OH, OW, None, max_H)
+        for i, h in enumerate(host):
+            np.testing.assert_array_equal(got[i], P.resize_bilinear_legacy(h, OH, OW), err_msg="image %d -> %d" % (i, OH))
+        np.testing.assert_array_equal(_device(ops, imgs, codes, params, OH, OW, SHAPES, max_H), got)

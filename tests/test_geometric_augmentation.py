@@ -293,6 +293,17 @@ def test_train_time_rule():
     assert train.geometric_augmentation(flip, model("closeness: true"), "record") is False    # and nothing is refused
 
 
+def test_descriptors_with_the_source_sizes_as_frames_are_those_without_frames():
+    """What lets the pipeline pass every program's final frames: a program that moves no frame ends in the source size."""
+    from mtl_ssl_amd import ops
+    shapes, flips = [(37, 53), (64, 40), (33, 33)], [True, False, True]
+    for OH, OW in ((24, 40), (37, 53)):
+        plain, n = ops.image_descs(shapes, flips, OH, OW)
+        framed, m = ops.image_descs(shapes, flips, OH, OW, frames=shapes)
+        assert n == m == sum(h * w * 3 for h, w in shapes)
+        assert plain.tobytes() == framed.tobytes()
+
+
 # ------------------------------------------------------------------------------ the two feeds
 K = 3
 SHAPES = [(40, 56), (56, 40), (33, 33), (40, 56), (56, 40), (33, 33)]
