@@ -10,6 +10,7 @@ mtl_ssl_amd/tf_checkpoint.py (`open_checkpoint` picks by what is on disk). Momen
 `<variable>/Momentum` like TF's MomentumOptimizer names them, moving averages as
 `<variable>/ExponentialMovingAverage` (tf.contrib.opt.MovingAverageOptimizer).
 """
+import json
 import os
 
 import numpy as np
@@ -143,9 +144,14 @@ def _slot_names(trainer):
     return {"momentum": ("/Momentum", None), "rms_prop": ("/RMSProp", "/RMSProp_1"), "adam": ("/Adam", "/Adam_1")}[kind]
 
 
-def save(path, ps, global_step=0, trainer=None):
+INPUT_STATE = "input_state/"
+
+
+def save(path, ps, global_step=0, trainer=None, input_states=None):
     """Full training state: every variable under its reference name, momentum slots, moving averages
-    (when the trainer keeps them), step."""
+    (when the trainer keeps them), step. input_states: one InputPipeline.state() dict per data-parallel rank, taken at
+    the same step; each is stored as the bytes of its JSON text (`input_state/rank<r>`, uint8) beside
+    `input_state/world`, so the whole file still loads without pickle and stream and weights share one file."""
     out = {s.name: ps.value(s.name).detach().cpu().numpy() for s in ps.specs}
     slot0, slot1 = _slot_names(trainer)
     for s in ps.trainable_specs:
@@ -155,6 +161,10 @@ def save(path, ps, global_step=0, trainer=None):
         if trainer is not None and trainer.ema is not None:
             out[s.name + "/ExponentialMovingAverage"] = ps._view(trainer.ema, s).detach().cpu().numpy()
     out["global_step"] = np.asarray(global_step, np.int64)
+    if input_states is not None:
+        out[INPUT_STATE + "world"] = np.asarray(len(input_states), np.int64)
+        for r, st in enumerate(input_states):
+            out["%srank%d" % (INPUT_STATE, r)] = np.frombuffer(json.dumps(st, sort_keys=True).encode("utf-8"), np.uint8)
     np.savez(path, **out)
 
 
@@ -173,6 +183,15 @@ def load(path, ps, trainer=None):
         if trainer is not None and trainer.ema is not None and s.name + "/ExponentialMovingAverage" in ck.files:
             ps._view(trainer.ema, s).copy_(torch.as_tensor(ck[s.name + "/ExponentialMovingAverage"]).to(ps.device))
     return int(ck["global_step"]) if "global_step" in ck.files else 0
+
+
+def load_input_states(path):
+    """The input states save() stored, one dict per rank; None for a state file without any."""
+    ck = np.load(path, allow_pickle=False)
+    if INPUT_STATE + "world" not in ck.files:
+        return None
+    return [json.loads(ck["%srank%d" % (INPUT_STATE, r)].tobytes().decode("utf-8"))
+            for r in range(int(ck[INPUT_STATE + "world"]))]
 
 
 def load_moving_averages(path, ps):

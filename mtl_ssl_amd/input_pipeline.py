@@ -7,7 +7,8 @@ The reference overlaps its input with the step through parallel readers and pref
 * The consuming process replays the record stream of `input_reader.examples` exactly (rank sharding, the shuffle
   buffer, the fixed number of uniform draws of every listed augmentation option (`preprocessor.Step.draws`), the
   same RandomState in the same order). Only the framing of a TFRecord is read here; the draws do not depend on
-  pixels or boxes.
+  pixels or boxes. That stream is small references and numbers, so `InputPipeline.state()` can describe it as of the
+  last batch handed out in a few kilobytes of JSON, and `restore()` continues it in another process.
 * Worker processes (the `spawn` context: a process that has initialised HIP is never forked, and a worker never
   imports torch) read the record, parse the tf.Example, decode the image to uint8, turn the consumer's draws into
   the image's float32 op parameters (`preprocessor.plan`: flip flags, jitter, colour deltas, patch corners, seeds)
@@ -23,6 +24,7 @@ The reference overlaps its input with the step through parallel readers and pref
   runs the numpy path (`preprocessor.apply_program`, then `resize_bilinear_legacy`).
 """
 import collections
+import itertools
 import multiprocessing
 import os
 import queue
@@ -113,6 +115,135 @@ class InputPipelineError(RuntimeError):
     pass
 
 
+class InputStateMismatch(ValueError):
+    """A stream state was taken by a pipeline defined differently from the one asked to continue it; `field` names the
+    first entry of the definition that differs."""
+
+    def __init__(self, field, was, now):
+        ValueError.__init__(self, "the input state was taken with another %s (%r, this pipeline has %r)" % (field, was, now))
+        self.field = field
+
+
+STATE_VERSION = 1
+
+
+def _plain(v):
+    """Parsed option arguments as JSON would give them back: lists for tuples, Python scalars for numpy's."""
+    if hasattr(v, "keys"):
+        return {str(k): _plain(v[k]) for k in v.keys()}
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    return v.item() if isinstance(v, np.generic) else v
+
+
+def _rng_to_json(st):
+    name, key, pos, has_gauss, cached = st
+    return [str(name), [int(x) for x in key], int(pos), int(has_gauss), float(cached)]
+
+
+def _rng_from_json(st):
+    return (str(st[0]), np.asarray(st[1], np.uint32), int(st[2]), int(st[3]), float(st[4]))
+
+
+class _RecordStream:
+    """The record stream of `input_reader.examples` as an object whose whole state is plain data: rank sharding over
+    the files, the shuffle buffer, then the fixed number of uniform draws per record, from the same RandomState in the
+    same order. An item is (path, index, offset, length) and its draws. `cursor()` is the state outside the shuffle
+    buffer and the RandomState; every item also comes with the numbers that undo its step on the buffer and repeat its
+    calls of the RandomState (`undo`), so a consumer that lets the stream run ahead can still name the state after any
+    recent item without copying the buffer or the RandomState's 624 words per item."""
+
+    def __init__(self, paths, rng, loop, rank, world, shuffle_buffer, n_draws):
+        self.paths, self.rng, self.loop, self.rank, self.world = paths, rng, loop, rank, world
+        self.shuffle_buffer, self.n_draws = shuffle_buffer, n_draws
+        self.epoch, self.file, self.record, self.i = 0, 0, 0, 0     # pass over the files; the next record; stream counter
+        self.buf, self.draining = [], False
+        self._spans = None                                          # open iterator over paths[file], at `record`
+
+    def _next_record(self):
+        """records() of input_reader.examples: the next record of this rank, None at the end of a non-looping stream."""
+        while True:
+            if self._spans is None:
+                if self.file >= len(self.paths):
+                    if not self.loop:
+                        return None
+                    self.epoch, self.file, self.record = self.epoch + 1, 0, 0
+                    if not self.paths:
+                        return None
+                self._spans = itertools.islice(record_spans(self.paths[self.file]), self.record, None)
+            span = next(self._spans, None)
+            if span is None:
+                self._spans, self.file, self.record = None, self.file + 1, 0
+                continue
+            k, mine = self.record, (self.i % self.world) == self.rank
+            self.record += 1
+            self.i += 1
+            if mine:
+                return (self.paths[self.file], k) + span
+
+    def next(self):
+        """-> (record, draws, undo) or None. undo = (records appended to the buffer, index drawn, the buffer's length
+        then), None without a buffer."""
+        undo = None
+        if self.shuffle_buffer <= 0:
+            rec = self._next_record()
+        else:
+            buf, grown, rec = self.buf, 0, None
+            while not self.draining and rec is None:
+                new = self._next_record()
+                if new is None:
+                    self.draining = True
+                    break
+                buf.append(new)
+                grown += 1
+                if len(buf) > self.shuffle_buffer:
+                    rec = self._draw()
+            if rec is None and buf:
+                rec = self._draw()
+            if rec is not None:
+                undo = (grown,) + rec[1:]
+                rec = rec[0]
+        if rec is None:
+            return None
+        # preprocessor.preprocess: a fixed number of rng.uniform() per listed option, whatever the pixels or boxes
+        return rec, [float(self.rng.uniform()) for _ in range(self.n_draws)], undo
+
+    def _draw(self):
+        buf = self.buf
+        n = len(buf)
+        j = int(self.rng.randint(n))
+        buf[j], buf[-1] = buf[-1], buf[j]
+        return buf.pop(), j, n
+
+    def cursor(self):
+        return (self.epoch, self.file, self.record, self.i, self.draining)
+
+    def repeat_calls(self, rng, undo):
+        """Advance `rng` (a copy of the RandomState as it was before an item) by the calls that item made."""
+        if undo is not None:
+            rng.randint(undo[2])
+        for _ in range(self.n_draws):
+            rng.uniform()
+
+    def rewound(self, items):
+        """A copy of the shuffle buffer as it was before `items` (the latest (record, undo) pairs, oldest first)."""
+        buf = list(self.buf)
+        for rec, undo in reversed(items):
+            if undo is None:
+                continue
+            grown, j, _ = undo
+            buf.append(rec)
+            buf[j], buf[-1] = buf[-1], buf[j]
+            if grown:
+                del buf[-grown:]
+        return buf
+
+    def restore(self, cursor, rng_state, buf):
+        self.epoch, self.file, self.record, self.i, self.draining = cursor
+        self.rng.set_state(rng_state)
+        self.buf, self._spans = list(buf), None
+
+
 class _HostPreparer:
     """The host path on the decoded uint8 images: float32 cast, the op program (flips, colour ops, patches),
     resize_bilinear_legacy, collate."""
@@ -129,6 +260,17 @@ class _HostPreparer:
 
     def hand_out(self, batch):
         return batch
+
+
+class _NoPreparer:
+    """device=None: the pipeline only follows the stream and hands out each batch's size. The training launcher runs
+    one beside the serial host generator, batch for batch, to know that generator's stream state."""
+
+    def prepare(self, items, OH, OW):
+        return len(items)
+
+    def hand_out(self, size):
+        return size
 
 
 class _DevicePreparer:
@@ -225,16 +367,20 @@ class _DevicePreparer:
 class InputPipeline:
     """Iterator (and context manager) over the batches `input_reader.batches(...)` yields for the same arguments, with
     `images` already on `device` (ready on the consumer's current stream at hand-out); on a CPU device, the host
-    preparer yields exactly batches()'s dicts.
+    preparer yields exactly batches()'s dicts; with device=None no batch is built and the batch's size is yielded.
 
     num_workers: decode processes (default: `default_num_workers()` of 8 readers); local_ranks: ranks on this node
     sharing its CPUs; prefetch: batches decoded / staged ahead of the consumer (train.proto prefetch_queue_capacity);
     geometric: as in input_reader.batches (random crop / pad options run, no frozen auxiliary labels).
+
+    `state()` describes the stream as of the last batch handed out, as plain JSON data; a pipeline built with the same
+    arguments and given that dict (`state=`, or `restore()` before the first batch) continues with exactly the
+    batches this one would have handed out next. The description does not depend on num_workers, prefetch or timing.
     """
 
     def __init__(self, paths, num_classes, batch_size, augmentation_options=(), rng=None, loop=False, rank=0,
                  world=1, shuffle_buffer=0, resized_shape=None, max_pending=64, drop_remainder=False, device="cpu",
-                 num_workers=None, prefetch=10, local_ranks=1, profile=False, geometric=False):
+                 num_workers=None, prefetch=10, local_ranks=1, profile=False, geometric=False, state=None):
         self.paths = list(paths)
         self.num_classes = int(num_classes)
         self.batch_size = int(batch_size)
@@ -249,23 +395,44 @@ class InputPipeline:
         self.prefetch = max(1, int(prefetch))
         self.num_workers = int(num_workers) if num_workers else default_num_workers(8, local_ranks)
         self.timings = collections.Counter()          # worker seconds per stage, consumer seconds of packing
-        self._records = self._record_stream()
+        self._records = _RecordStream(self.paths, self.rng, self.loop, self.rank, self.world, self.shuffle_buffer,
+                                      self.n_draws)
         self._exhausted = False
-        self._seq_next = 0                            # next task sequence number
+        self._seq_next = 0                            # next task sequence number = stream items drawn so far
         self._seq_want = 0                            # next result to bucket
         self._done = {}                               # out-of-order results
-        self._buckets, self._pending = {}, 0
-        self._ready = collections.deque()             # assembled batches: (items, OH, OW)
-        self._staged = collections.deque()            # prepared batches awaiting hand-out
+        self._buckets, self._pending = {}, 0          # key -> [(example, worker's parameters, item's log entry)]
+        self._ready = collections.deque()             # assembled batches: (items, key, stream mark)
+        self._staged = collections.deque()            # prepared batches awaiting hand-out, each with its mark
+        # what state() needs, as references to small tuples: the stream items from `_log_base` on, each (record, draws,
+        # undo, the stream's cursor after it); the cursor before the first of them and a RandomState that has made the
+        # calls of every item before it; a pipeline continued from a state re-decodes that state's bucket contents
+        # first, under the sequence numbers below `_refill[0]` (log entries without a cursor: they move nothing)
+        self._log, self._log_base = collections.deque(), 0
+        self._cursor_base = self._records.cursor()
+        self._rng_base = np.random.RandomState(0)
+        self._rng_base.set_state(self.rng.get_state())
+        self._refill = (0, {})
+        self._resend = collections.deque()            # the log entries of those, until they are sent to the workers
+        self._started = False
+        # the mark of the last batch handed out: (items bucketed, ((key, log entries in the bucket), ...), exhausted)
+        self._mark = (0, (), False)
+        self._handed = 0
+        self._definition = None
         self._procs = []
         self._closed = False
-        import torch
-        dev = torch.device(device)
-        self._preparer = (_HostPreparer(self.codes) if dev.type == "cpu"
-                          else _DevicePreparer(dev, self.prefetch + 1, self.codes, profile))
+        if device is None:
+            self._preparer = _NoPreparer()
+        else:
+            import torch
+            dev = torch.device(device)
+            self._preparer = (_HostPreparer(self.codes) if dev.type == "cpu"
+                              else _DevicePreparer(dev, self.prefetch + 1, self.codes, profile))
         ctx = multiprocessing.get_context("spawn")
         self._tasks, self._results = ctx.Queue(), ctx.Queue()
         try:
+            if state is not None:
+                self.restore(state)
             for _ in range(self.num_workers):
                 p = ctx.Process(target=_worker_main, args=(self._tasks, self._results, self.num_classes, self.steps, self.geometric),
                                 daemon=True)
@@ -275,67 +442,59 @@ class InputPipeline:
             self.close()
             raise
 
-    # ---------------------------------------------------------------- the record stream of input_reader.examples
-    def _record_stream(self):
-        rng, world, rank, paths = self.rng, self.world, self.rank, self.paths
-
-        def records():
-            i = 0
-            while True:
-                for p in paths:
-                    for k, span in enumerate(record_spans(p)):
-                        mine = (i % world) == rank
-                        i += 1
-                        if mine:
-                            yield (p, k) + span
-                if not self.loop:
-                    return
-
-        def shuffled():
-            if self.shuffle_buffer <= 0:
-                yield from records()
-                return
-            buf = []
-            for rec in records():
-                buf.append(rec)
-                if len(buf) > self.shuffle_buffer:
-                    j = int(rng.randint(len(buf)))
-                    buf[j], buf[-1] = buf[-1], buf[j]
-                    yield buf.pop()
-            while buf:
-                j = int(rng.randint(len(buf)))
-                buf[j], buf[-1] = buf[-1], buf[j]
-                yield buf.pop()
-
-        for rec in shuffled():
-            # preprocessor.preprocess: a fixed number of rng.uniform() per listed option, whatever the pixels or boxes
-            yield rec, [float(rng.uniform()) for _ in range(self.n_draws)]
-
     def _submit(self):
         depth = self.prefetch * self.batch_size + self.num_workers
-        while not self._exhausted and self._seq_next - self._seq_want < depth:     # decoded or in flight
-            try:
-                (path, index, offset, length), draws = next(self._records)
-            except StopIteration:
-                self._exhausted = True
-                break
-            self._tasks.put((self._seq_next, path, index, offset, length, draws))
+        while (self._resend or not self._exhausted) and self._seq_next - self._seq_want < depth:   # decoded or in flight
+            if self._resend:
+                entry = self._resend.popleft()
+            else:
+                item = self._records.next()
+                if item is None:
+                    self._exhausted = True
+                    break
+                entry = item + (self._records.cursor(),)
+            self._log.append(entry)
+            self._tasks.put((self._seq_next,) + entry[0] + (entry[1],))
             self._seq_next += 1
 
     # ---------------------------------------------------------------- bucketing of input_reader.batches
-    def _bucket(self, ex, params):
+    def _key(self, frame):
+        H, W = frame
+        return tuple(self.resized_shape(H, W)) if self.resized_shape is not None else (H, W)
+
+    def _passed(self, entry, cursor, rng):
+        """The stream's cursor after a log entry, `rng` advanced by the entry's calls."""
+        if entry[3] is None:
+            return cursor
+        self._records.repeat_calls(rng, entry[2])
+        return entry[3]
+
+    def _marked(self, exhausted=False):
+        """The stream mark of a batch assembled now: where bucketing stands and who waits in which bucket."""
+        return (self._seq_want, self._waiting(self._buckets, self._buckets), exhausted)
+
+    @staticmethod
+    def _waiting(buckets, keys):
+        """((key, ((log entry, final frame) of every example in that bucket, in order)), ...): references, no copies."""
+        return tuple((k, tuple((e, p[1]) for _, p, e in buckets[k])) for k in keys)
+
+    def _bucket(self, seq, ex, params):
         """`params`: the worker's (op parameters, final frame); the frame is the source size unless a crop / pad moved it."""
-        H, W = params[1]
-        key = tuple(self.resized_shape(H, W)) if self.resized_shape is not None else (H, W)
-        self._buckets.setdefault(key, []).append((ex, params))
+        entry = self._log[seq - self._log_base]
+        if seq < self._refill[0]:                    # a restored state's bucket content goes back where it waited
+            self._buckets[self._refill[1][seq]].append((ex, params, entry))
+            self._pending += 1
+            return
+        key = self._key(params[1])
+        self._buckets.setdefault(key, []).append((ex, params, entry))
         self._pending += 1
         if len(self._buckets[key]) == self.batch_size:
             self._pending -= self.batch_size
-            self._ready.append((self._buckets.pop(key), key))
+            self._ready.append((self._buckets.pop(key), key, self._marked()))
         elif self._pending > self.max_pending:
             key = max(self._buckets, key=lambda k: len(self._buckets[k]))
             self._pending -= len(self._buckets[key])
-            self._ready.append((self._buckets.pop(key), key))
+            self._ready.append((self._buckets.pop(key), key, self._marked()))
 
     def _next_ready(self, block):
         """The next assembled batch: None at the end of the stream, or (block=False) when none is assembled yet."""
@@ -343,15 +502,16 @@ class InputPipeline:
             while self._seq_want in self._done:              # bucket what has arrived, in stream order
                 ex, params = self._done.pop(self._seq_want)
                 self._seq_want += 1
-                self._bucket(ex, params)
+                self._bucket(self._seq_want - 1, ex, params)
             if self._ready:
                 break
             self._submit()
-            if self._exhausted and self._seq_want == self._seq_next:
-                if not self.drop_remainder:
-                    for key in sorted(self._buckets):
-                        self._ready.append((self._buckets[key], key))
+            if self._exhausted and not self._resend and self._seq_want == self._seq_next:
+                left = self._buckets if not self.drop_remainder else {}
                 self._buckets, self._pending = {}, 0
+                keys = sorted(left)
+                for n, key in enumerate(keys):       # the mark of a remainder batch: the remainder batches after it
+                    self._ready.append((left[key], key, (self._seq_want, self._waiting(left, keys[n + 1:]), True)))
                 break
             try:
                 seq, ex, params, timings, err = self._results.get(timeout=0.5) if block else self._results.get_nowait()
@@ -369,17 +529,18 @@ class InputPipeline:
         return self._ready.popleft() if self._ready else None
 
     def _stage(self, ready):
-        items, (OH, OW) = ready
+        items, (OH, OW), mark = ready
         t0 = time.perf_counter()
-        staged = self._preparer.prepare(items, OH, OW)
+        staged = self._preparer.prepare([it[:2] for it in items], OH, OW)
         self.timings["stage"] += time.perf_counter() - t0
-        self._staged.append(staged)
+        self._staged.append((staged, mark))
 
     # ---------------------------------------------------------------- iterator
     def __iter__(self):
         return self
 
     def __next__(self):
+        self._started = True
         if self._closed:
             raise StopIteration
         try:
@@ -389,7 +550,12 @@ class InputPipeline:
                     self.close()
                     raise StopIteration
                 self._stage(ready)
-            batch = self._preparer.hand_out(self._staged.popleft())
+            staged, self._mark = self._staged.popleft()
+            self._handed += 1
+            while self._log_base < self._mark[0]:    # state() starts from the mark: forget the items before it
+                self._cursor_base = self._passed(self._log.popleft(), self._cursor_base, self._rng_base)
+                self._log_base += 1
+            batch = self._preparer.hand_out(staged)
             # stage what has already been decoded, so that its copy and kernel overlap the step about to run
             while len(self._staged) < self.prefetch:
                 ready = self._next_ready(block=False)
@@ -402,6 +568,94 @@ class InputPipeline:
         except BaseException:
             self.close()
             raise
+
+    # ---------------------------------------------------------------- stopping and continuing
+    DEFINITION = ("paths", "file_sizes", "num_classes", "batch_size", "options", "geometric", "loop", "rank", "world",
+                  "shuffle_buffer", "max_pending", "drop_remainder")
+
+    def definition(self):
+        """What two pipelines must share for one to continue the other's stream, as JSON data. The resize rule is a
+        function and cannot be listed: it is checked through the bucket keys a state records."""
+        if self._definition is None:
+            self._definition = {
+                "paths": list(self.paths), "file_sizes": [os.path.getsize(p) for p in self.paths],
+                "num_classes": self.num_classes, "batch_size": self.batch_size,
+                "options": [[s.kind, _plain(s.args)] for s in self.steps], "geometric": self.geometric,
+                "loop": bool(self.loop), "rank": int(self.rank), "world": int(self.world),
+                "shuffle_buffer": self.shuffle_buffer, "max_pending": self.max_pending,
+                "drop_remainder": bool(self.drop_remainder)}
+        return self._definition
+
+    def state(self):
+        """The stream as of the last batch handed out (the start of the stream if none was), as a JSON-serialisable
+        dict: where the record cursor, the RandomState and the shuffle buffer stood when that batch was assembled, and
+        which records waited in which bucket with which draws. Nothing decoded, staged or in flight is part of it: the
+        record stream runs ahead of bucketing, so the cursor is the one logged with the last item bucketed, the
+        RandomState is a second one that repeats each item's calls as batches are handed out, and the shuffle buffer
+        is wound back over the items drawn since. `replay` (items drawn but not bucketed) is therefore always empty."""
+        m, waiting, exhausted = self._mark
+        log = list(self._log)
+        cursor, rng = self._cursor_base, np.random.RandomState(0)
+        rng.set_state(self._rng_base.get_state())
+        for entry in log[:max(0, m - self._log_base)]:         # none once a batch was handed out: the log starts at its mark
+            cursor = self._passed(entry, cursor, rng)
+        epoch, file, record, i, draining = cursor
+        index = {}
+        for n, p in enumerate(self.paths):
+            index.setdefault(p, n)
+        ref = lambda rec: [index[rec[0]], int(rec[1]), int(rec[2]), int(rec[3])]
+        buf = self._records.rewound([(e[0], e[2]) for e in log[max(0, m - self._log_base):]])
+        return {
+            "version": STATE_VERSION, "definition": dict(self.definition()), "batches": self._handed, "items": m,
+            "cursor": {"pass": epoch, "file": file, "record": record, "i": i},
+            "rng": _rng_to_json(rng.get_state()), "shuffle": [ref(r) for r in buf], "draining": bool(draining),
+            "buckets": [{"key": [int(v) for v in key],
+                         "items": [{"record": ref(e[0]), "draws": list(e[1]), "frame": [int(v) for v in frame]}
+                                   for e, frame in items]} for key, items in waiting],
+            "replay": [], "pending": sum(len(items) for _, items in waiting), "exhausted": bool(exhausted)}
+
+    def restore(self, state):
+        """Continue the stream a `state()` dict describes. Only before the first batch is asked for. Raises
+        InputStateMismatch (naming the field) when the state was taken by a differently defined pipeline, and leaves
+        this one untouched then."""
+        if self._started or self._closed:
+            raise RuntimeError("InputPipeline.restore() must be called before the first batch is asked for")
+        if state.get("version") != STATE_VERSION:
+            raise InputStateMismatch("version", state.get("version"), STATE_VERSION)
+        mine, theirs = self.definition(), state["definition"]
+        for field in self.DEFINITION:
+            if theirs.get(field) != mine[field]:
+                raise InputStateMismatch(field, theirs.get(field), mine[field])
+        if state["replay"]:
+            raise ValueError("the input state lists replay items, which this version never writes")
+        for b in state["buckets"]:
+            for it in b["items"]:
+                if list(self._key(it["frame"])) != list(b["key"]):
+                    raise InputStateMismatch("resized_shape", b["key"], list(self._key(it["frame"])))
+        ref = lambda r: (self.paths[r[0]], int(r[1]), int(r[2]), int(r[3]))
+        c = state["cursor"]
+        cursor = (int(c["pass"]), int(c["file"]), int(c["record"]), int(c["i"]), bool(state["draining"]))
+        self._records.restore(cursor, _rng_from_json(state["rng"]), [ref(r) for r in state["shuffle"]])
+        self._rng_base.set_state(self.rng.get_state())
+        m = int(state["items"])
+        first = m - sum(len(b["items"]) for b in state["buckets"])
+        self._log.clear()
+        self._log_base = self._seq_want = self._seq_next = first
+        self._cursor_base = cursor
+        self._buckets, self._pending, where, waiting = {}, 0, {}, []
+        self._resend.clear()
+        for b in state["buckets"]:
+            key = tuple(int(v) for v in b["key"])
+            self._buckets[key] = []
+            entries = [(ref(it["record"]), [float(u) for u in it["draws"]], None, None) for it in b["items"]]
+            for e in entries:
+                where[first + len(self._resend)] = key
+                self._resend.append(e)
+            waiting.append((key, tuple((e, tuple(it["frame"])) for e, it in zip(entries, b["items"]))))
+        self._refill = (m, where)
+        self._exhausted = bool(state["exhausted"])
+        self._mark = (m, tuple(waiting), self._exhausted)
+        self._handed = int(state["batches"])
 
     def queue_fill(self):
         """(batches staged ahead of the consumer, capacity): the prefetch queue's fill for the training summaries

@@ -42,6 +42,11 @@ def _flags(argv):
     ap.add_argument("--save_summaries_secs", type=float, default=None,
                     help="overrides train_config.save_summaries_secs (default 120): seconds between two summaries in "
                          "train_dir's TensorBoard event file; 0 writes none")
+    ap.add_argument("--input_state", choices=("resume", "restart"), default="resume",
+                    help="resume: a run that continues from train_dir's state file also continues its input stream where "
+                         "that file left it (shuffle buffer, draws, waiting images; --input_pipeline=async only); restart: "
+                         "the stream starts at the first record again")
+    ap.add_argument("--log_every", type=int, default=10, help="steps between two printed loss lines")
     return ap.parse_args(argv)
 
 
@@ -94,11 +99,51 @@ def geometric_augmentation(augmentation_options, model_config, aux_labels):
     return ok
 
 
+class HostBatches:
+    """The serial generator input_reader.batches with `images` copied to `device` at hand-out. With follow_state, a
+    pipeline that builds no batches (InputPipeline(device=None), one decode worker) follows the same stream from a
+    copy of the RandomState, batch for batch, so that state() is the state the asynchronous pipeline would report
+    after as many batches: a state file written by a host-fed run can be continued with --input_pipeline=async. The
+    generator itself cannot be continued (there is no restore())."""
+
+    def __init__(self, paths, num_classes, batch_size, augmentation_options, rng, device, follow_state=False,
+                 geometric=False, **kw):
+        from . import input_pipeline, input_reader
+        self.device = device
+        self._shadow = None
+        if follow_state:
+            twin = np.random.RandomState(0)
+            twin.set_state((rng if rng is not None else twin).get_state())
+            self._shadow = input_pipeline.InputPipeline(paths, num_classes, batch_size, augmentation_options, twin,
+                                                        device=None, num_workers=1, prefetch=2, geometric=geometric, **kw)
+        self._batches = input_reader.batches(paths, num_classes, batch_size, augmentation_options, rng,
+                                             geometric=geometric, **kw)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        b = next(self._batches)
+        if self._shadow is not None and next(self._shadow) != int(b["images"].shape[0]):
+            raise RuntimeError("the pipeline following the host generator's stream has left it")
+        b["images"] = b["images"].to(self.device, non_blocking=True)
+        return b
+
+    def state(self):
+        """InputPipeline.state() of the stream as of the last batch handed out; None without follow_state."""
+        return None if self._shadow is None else self._shadow.state()
+
+    def close(self):
+        if self._shadow is not None:
+            self._shadow.close()
+
+
 def record_batches(kind, paths, num_classes, batch_size, augmentation_options, rng, device, input_config,
-                   prefetch=10, geometric=False, **kw):
+                   prefetch=10, geometric=False, follow_state=False, **kw):
     """The batches of input_reader.batches with `images` on `device`: 'async' = mtl_ssl_amd.input_pipeline
     (input_reader.proto num_readers decode workers, train.proto prefetch_queue_capacity batches ahead), 'host' = the
-    serial generator, images copied at hand-out. geometric: see geometric_augmentation."""
+    serial generator, images copied at hand-out (follow_state: see HostBatches). geometric: see
+    geometric_augmentation."""
     from . import input_pipeline, input_reader
     if kind == "async":
         local = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
@@ -108,12 +153,7 @@ def record_batches(kind, paths, num_classes, batch_size, augmentation_options, r
     if kind != "host":
         raise ValueError("input pipeline %r: async or host" % kind)
 
-    def gen():
-        for b in input_reader.batches(paths, num_classes, batch_size, augmentation_options, rng, geometric=geometric,
-                                      **kw):
-            b["images"] = b["images"].to(device, non_blocking=True)
-            yield b
-    return gen()
+    return HostBatches(paths, num_classes, batch_size, augmentation_options, rng, device, follow_state, geometric, **kw)
 
 
 def main(argv=None):
@@ -165,11 +205,16 @@ def main(argv=None):
                             if input_config.get("shuffle", True) else 0,
                             resized_shape=lambda h, w: probe.resized_shape(h, w, rz),
                             max_pending=64 if world == 1 else 256,
-                            prefetch=int(train_config.prefetch_queue_capacity), geometric=geometric)
+                            prefetch=int(train_config.prefetch_queue_capacity), geometric=geometric,
+                            follow_state=True)
 
     def next_batch():
         return next(stream)
     os.makedirs(f.train_dir, exist_ok=True)
+    if (rank == 0 and f.input_pipeline == "host" and f.input_state == "resume"
+            and os.path.exists(os.path.join(f.train_dir, "model.ckpt.npz"))):
+        print("warning: --input_pipeline=host cannot continue its input stream: weights and step are resumed, the "
+              "records restart at the first one (--input_pipeline=async continues it)")
     if rank == 0 and f.pipeline_config_path:          # train.py:235-247 keeps the configuration beside the checkpoints
         with open(os.path.join(f.train_dir, "pipeline.config"), "w") as out:
             out.write(open(f.pipeline_config_path).read())
@@ -177,7 +222,8 @@ def main(argv=None):
         trainer.train(next_batch, lambda: probe, train_config, master=f.master, task=rank, num_clones=1,
                       worker_replicas=world, is_chief=rank == 0, train_dir=f.train_dir, model_config=model_config,
                       num_steps=f.num_steps, aux_labels=f.aux_labels, save_summaries_secs=f.save_summaries_secs,
-                      total_configs=total_configs, input_queue=stream)
+                      total_configs=total_configs, input_queue=stream, input_state=f.input_state,
+                      log_every=max(1, f.log_every))
     finally:
         if hasattr(stream, "close"):
             stream.close()

@@ -542,18 +542,57 @@ class Trainer:
 def collective_verdict(comm, code, device):
     """max over the data-parallel ranks of a small non-negative failure code (0 = fine). Every rank must call it at
     the same point of the step loop; with one rank (or no communicator) it is the identity."""
+    return collective_step_verdict(comm, code, False, device)[0]
+
+
+def collective_step_verdict(comm, code, save, device):
+    """collective_verdict plus, in the same all-reduce, whether any rank wants the state written after this step
+    (only the chief ever asks): every rank must take its input state at the step the chief saves at, and the chief's
+    clock alone knows when that is. -> (worst code, save)."""
     if comm is None or comm.world <= 1:
-        return int(code)
-    flag = torch.tensor([int(code)], dtype=torch.int32, device=device)
+        return int(code), bool(save)
+    flag = torch.tensor([int(code), int(bool(save))], dtype=torch.int32, device=device)
     comm.allreduce(flag, op="max")
-    return int(flag.item())
+    code, save = flag.tolist()
+    return int(code), bool(save)
+
+
+def gather_input_states(local):
+    """One input state per data-parallel rank, in rank order, on rank 0 (None on the others) over the process group
+    the launcher initialised; [local] where there is none. None when some rank has no state to give."""
+    import torch.distributed as dist
+    if not (dist.is_initialized() and dist.get_world_size() > 1):
+        return None if local is None else [local]
+    states = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+    dist.gather_object(local, states, dst=0)
+    return None if states is None or any(s is None for s in states) else states
+
+
+def restore_input_state(input_queue, path, rank, world, say=print):
+    """Continue `input_queue` from the state rank `rank` stored in the state file. Where that cannot be done the stream
+    starts at its first record and one line says why. -> whether it was restored."""
+    from . import checkpoint, input_pipeline
+    states = checkpoint.load_input_states(path)
+    why = None
+    if states is None:
+        why = "%s holds no input state" % path
+    elif len(states) != world:
+        why = "the input state was saved by %d rank(s), this run has %d" % (len(states), world)
+    else:
+        try:
+            input_queue.restore(states[rank])
+        except input_pipeline.InputStateMismatch as e:
+            why = str(e)
+    if why is not None:
+        say("input stream of rank %d restarts at its first record: %s" % (rank, why))
+    return why is None
 
 
 def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=0, num_clones=1,
           worker_replicas=1, clone_on_cpu=False, ps_tasks=0, worker_job_name="lonely_worker",
           is_chief=True, train_dir=None, num_examples=0, total_configs=None, model_config=None,
           is_first_training=True, num_steps=None, log_every=10, save_interval_secs=600, aux_labels="record",
-          save_summaries_secs=None, input_queue=None):
+          save_summaries_secs=None, input_queue=None, input_state="resume"):
     """object_detection/trainer.py:217-219 signature. `create_tensor_dict_fn()` yields one batch
     dict per call (see mtl_ssl_amd.synthetic.make_batch for the field contract);
     `create_model_fn()` returns a built FasterRCNNMetaArch. Parameter-server arguments
@@ -565,12 +604,19 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
     0 = none) after the previous one. total_configs (the reference's tuple of model / train / train input / eval /
     eval input configs) adds the five config texts once; input_queue: an object with queue_fill() -> (batches staged,
     capacity) for the queue/fraction_of_<capacity>_full tag (input_pipeline.InputPipeline).
+    An input_queue with state() has its state stored in every state file, taken at the step of the weights; one with
+    restore() continues from the state a resumed file holds for this rank (restore_input_state) unless input_state is
+    "restart". Streams without these methods (synthetic batches) behave as before; the launcher's host generator has
+    state() only, so its files carry the state and the generator itself starts afresh.
     train_config.show_image_summary is accepted and ignored: the reference hands the images to
     DetectionModel.provide_image_infos (trainer.py:175-176, core/model.py:288-290), which nothing ever reads."""
     import os
     import torch.distributed as dist
     from . import checkpoint
     world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    if input_state not in ("resume", "restart"):
+        raise ValueError("input_state %r: resume or restart" % input_state)
     model = create_model_fn()
     trainer = Trainer(model, train_config, world, aux_labels=aux_labels)
     if is_chief:
@@ -584,6 +630,11 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
     if state and os.path.exists(state):
         trainer.global_step = checkpoint.load(state, model.ps, trainer)
         model.prepare()
+        if hasattr(input_queue, "restore"):
+            if input_state == "restart":
+                print("input stream of rank %d restarts at its first record: --input_state=restart" % rank)
+            else:
+                restore_input_state(input_queue, state, rank, world)
     elif train_config.fine_tune_checkpoint:
         mtl = model_config.mtl if model_config is not None else model._mtl
         ckpt = checkpoint.open_checkpoint(str(train_config.fine_tune_checkpoint))
@@ -600,11 +651,16 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
     save_secs = float(save_interval_secs) if save_interval_secs else 0.0
 
     def save_state():
-        if state and is_chief:
+        """Every rank calls this at the same step: the chief's one file holds every rank's input state."""
+        if not state:
+            return
+        inputs = gather_input_states(input_queue.state() if hasattr(input_queue, "state") else None)
+        if is_chief:
             os.makedirs(train_dir, exist_ok=True)
             tmp = state + ".tmp.npz"
-            checkpoint.save(tmp, model.ps, trainer.global_step, trainer)
-            os.replace(tmp, state)             # a crash mid-write never clobbers the previous state
+            checkpoint.save(tmp, model.ps, trainer.global_step, trainer, input_states=inputs)
+            os.replace(tmp, state)             # a crash mid-write never clobbers the previous state; one file, so
+                                               # weights and stream cannot disagree
 
     secs = train_config.save_summaries_secs if save_summaries_secs is None else save_summaries_secs
     writer = None
@@ -675,8 +731,10 @@ class _TrainSummaries:
 def _train_loop(trainer, model, create_tensor_dict_fn, steps, log_every, is_chief, save_secs, save_state, writer):
     last_save = time.time()
     log = []
+    shared_save = trainer.comm is not None and trainer.comm.world > 1
     while steps is None or trainer.global_step < steps:
         t0 = time.time()
+        save_now = False
         losses = trainer.step(create_tensor_dict_fn())
         is_log_step = trainer.global_step % log_every == 0 or trainer.global_step == steps
         if is_log_step:
@@ -694,7 +752,10 @@ def _train_loop(trainer, model, create_tensor_dict_fn, steps, log_every, is_chie
                     model.check_device_flags()
                 except RuntimeError as e:
                     bad, why = 2, e
-            worst = collective_verdict(trainer.comm, bad, model.ps.device)
+            # the same all-reduce carries the chief's wish to save: with several ranks the state is written on log steps
+            # only, so that every rank snapshots its input stream at the step of the chief's weights
+            save_now = bool(shared_save and is_chief and save_secs and time.time() - last_save >= save_secs)
+            worst, save_now = collective_step_verdict(trainer.comm, bad, save_now, model.ps.device)
             if worst and not bad:
                 why = RuntimeError("another data-parallel rank reported %s; stopping with it"
                                    % ("a non-finite loss" if worst == 1 else "a device-side invariant violation"))
@@ -714,7 +775,7 @@ def _train_loop(trainer, model, create_tensor_dict_fn, steps, log_every, is_chie
                 if trainer.comm is not None:
                     trainer.comm.close()
                 raise
-        if save_secs and time.time() - last_save >= save_secs:          # trainer.py:464-466 save_interval_secs
+        if save_now if shared_save else (save_secs and time.time() - last_save >= save_secs):   # trainer.py:464-466
             save_state()
             last_save = time.time()
     save_state()
