@@ -721,8 +721,9 @@ int mtlssl_dedup_windows(const float* windows, int batch, int n_expand, int n2, 
  * by their per-proposal loss keeps at most num_hard_examples proposals; the loss terms are the sums over the kept
  * ones and only they are back-propagated.
  *   _scores: scores[B,n2] = cls + loc row losses (loss_type 0 BOTH — the row losses carry weight / normaliser),
- *            cls only (1) or loc only (2); rows >= num_proposals[b] get -inf (not candidates). Feed each image's
- *            row to mtlssl_nms.
+ *            cls only (1) or loc only (2); rows >= num_proposals[b] get -FLT_MAX, whatever their losses hold: still
+ *            candidates, sorted behind every real proposal (mtlssl_nms leaves the sorted slots of -inf scores
+ *            unwritten but scans them). Feed each image's row to mtlssl_nms.
  *   _apply:  selected[B,max_selected] / num_selected[B] = the NMS output per image; selected indices >=
  *            num_proposals[b] (padding rows the NMS appended after every real candidate; nullable = none) are
  *            dropped — the reference unpads BEFORE mining (:1921-1929); zeroes the rows of d_box [B*n2, box_ld]

@@ -2,6 +2,8 @@
 // normalisers computed on the device so the step never syncs with the host), class-selected box
 // loss, edgemask targets, refine-input assembly, expanded windows. Tiny tensors; one block per
 // image where a per-image reduction is needed.
+#include <cfloat>
+
 #include "common.h"
 
 namespace mtlssl {
@@ -119,8 +121,13 @@ __global__ void __launch_bounds__(256)
 // core/losses.py:418-631 HardExampleMiner as the second stage uses it (faster_rcnn_meta_arch.py:1758-1762,
 // 1902-1946): per image, greedy NMS over the first num_proposals proposal boxes with the per-proposal LOSS as score
 // keeps at most num_hard_examples mutually non-overlapping "hard" proposals; the two loss terms become the sums over
-// the kept ones and only those rows receive a gradient. Stage 1: the NMS scores (padding rows = -inf, not
-// candidates). The row losses already carry weight / normaliser, so 'both' (cls * w_cls + loc * w_loc) is their sum.
+// the kept ones and only those rows receive a gradient. Stage 1: the NMS scores. The row losses already carry
+// weight / normaliser, so 'both' (cls * w_cls + loc * w_loc) is their sum. Padding rows get the lowest FINITE score,
+// whatever their loss holds: they stay candidates that sort behind every real proposal (losses are >= 0), so the NMS
+// writes every one of its n2 sorted slots. With -inf they were no candidates: mtlssl_nms's sort skips those, its scan
+// still walks all n2 slots, and the slots behind the last candidate held what the PREVIOUS image's sort had left in
+// the shared workspace — boxes and row indices of that image, some below this image's num_proposals, which _apply
+// then kept as mined.
 __global__ void __launch_bounds__(256)
     k_hard_mining_scores(const float* loc_rl, const float* cls_rl, const int32_t* num_prop, int n2, int loss_type,
                          float* scores) {
@@ -128,7 +135,7 @@ __global__ void __launch_bounds__(256)
   if (i >= n2) return;
   int64_t o = (int64_t)b * n2 + i;
   float v = loss_type == 1 ? cls_rl[o] : loss_type == 2 ? loc_rl[o] : cls_rl[o] + loc_rl[o];
-  scores[o] = i < num_prop[b] ? v : -INFINITY;
+  scores[o] = i < num_prop[b] ? v : -FLT_MAX;
 }
 // Stage 2 (one block per image): rows the NMS kept stay, every other row's gradient is zeroed; the mined losses are
 // the sums of the kept rows, accumulated in row order (fixed order: reproducible).
@@ -144,7 +151,7 @@ __global__ void __launch_bounds__(256)
   if (threadIdx.x == 0) s_kept = 0;
   __syncthreads();
   int ns = min(num_sel[b], max_sel);
-  // padding rows (index >= num_proposals, score -inf) come last in the NMS order: selected ones are not mined
+  // padding rows (index >= num_proposals, the lowest finite score) come last in the NMS order: selected ones are not mined
   int nvalid = num_prop ? min(num_prop[b], n2) : n2;
   for (int j = threadIdx.x; j < ns; j += 256) {
     int r = sel[(int64_t)b * max_sel + j];

@@ -1165,8 +1165,9 @@ def hard_example_mining(loc_rl, cls_rl, boxes, num_proposals, d_box, d_cls, num_
     """core/losses.py:418-631 on the second stage (see mtlssl_hard_mining_*): loc_rl / cls_rl [B,n2] per-proposal
     losses, boxes [B,n2,4] the proposal boxes. Zeroes the gradient rows of proposals that were not mined (in place)
     and returns (mined loc loss [B], mined cls loss [B], selected [B,max_sel], number kept [B]). The NMS sees padding
-    rows (score -inf) LAST, so they never suppress a proposal; the ones it may append are dropped by _apply, which also
-    returns the count without them (= NMS over the first num_proposals rows, the reference's unpad step)."""
+    rows (the lowest finite score) LAST, so they never suppress a proposal; the ones it may append are dropped by
+    _apply, which also returns the count without them (= NMS over the first num_proposals rows, the reference's unpad
+    step)."""
     B, n2 = loc_rl.shape
     dev = loc_rl.device
     scores = torch.empty((B, n2), dtype=f32, device=dev)

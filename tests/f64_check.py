@@ -1,5 +1,6 @@
-"""Helpers shared by the float64 kernel tests (test_gpu_head_kernels.py, test_gpu_spatial_kernels.py): elementwise
-comparison against a float64 reference with a per-element bound, bitwise comparison, host <-> device copies.
+"""Helpers shared by the float64 kernel tests (test_gpu_head_kernels.py, test_gpu_spatial_kernels.py,
+test_gpu_option_kernels.py): elementwise comparison against a float64 reference with a per-element bound, bitwise
+comparison, host <-> device copies.
 A plain module: no fixtures, not a conftest."""
 import numpy as np
 import torch
