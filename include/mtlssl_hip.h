@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 17
+#define MTLSSL_ABI_VERSION 18
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -410,6 +410,27 @@ int mtlssl_eval_nms(const float* boxes, const float* scores, const int32_t* segm
  * to fp32, label = ch0 < ch1; count_out (one int32, device) = pixels whose label equals gt_mask [h,w]. */
 int mtlssl_edgemask_agreement(const float* logits, int Hf, int Wf, const float* gt_mask, int h, int w,
                               int32_t* count_out, mtlssl_stream_t stream);
+/* The MS-COCO evaluator's greedy match (pycocotools COCOeval.evaluateImg as restated by CocoDetectionEvaluator._iou /
+ * _evaluate_image in mtl_ssl_amd/evaluation.py, which define the semantics; the reference reaches it through
+ * utils/object_detection_evaluation.py:294-425). A segment is one (image, category) pair with at least one detection
+ * or groundtruth box: detections [dt_off[s], dt_off[s+1]) of dt_boxes [ND,4] and groundtruth [gt_off[s], gt_off[s+1])
+ * of gt_boxes [NG,4] / gt_area [NG] / gt_crowd [NG] (offsets int32[num_segments+1]; boxes ymin,xmin,ymax,xmax in
+ * pixels, double; everything in device memory). The caller has sorted each segment's detections by descending score,
+ * stably, and cut them to the image's best max_detections_per_image. iou_thrs [T] and area_rng [A,2] are the
+ * evaluator's own doubles; T*A <= 64. One wavefront per segment, lane t*A + a walks the detections in order for
+ * threshold t in area range a: the unclaimed box of highest IoU >= min(thr, 1 - 1e-10) (an equal IoU replaces),
+ * regular boxes before ignored ones (crowd, or area outside [lo, hi]), crowd boxes claimable again with IoU =
+ * intersection / detection area, union floored at 1e-300. Outputs: bit t*A + a of dt_match[i] / dt_ignore[i] =
+ * detection i matched / is ignored (matched to an ignored box, or unmatched with its own area outside the range);
+ * npig[s*A + a] = the segment's groundtruth boxes not ignored in range a. The first m detections of a segment are the
+ * result for maxDets = m. max_gt = the largest groundtruth count of a segment (host int), at most
+ * MTLSSL_COCO_MATCH_MAX_GT; beyond it MTLSSL_EINVAL (the evaluator keeps such a segment on the host). All arithmetic
+ * in double, plain stores, no atomics: the same bits run to run. */
+#define MTLSSL_COCO_MATCH_MAX_GT 256
+int mtlssl_coco_match(const int32_t* dt_off, const int32_t* gt_off, int num_segments, int max_gt,
+                      const double* dt_boxes, const double* gt_boxes, const double* gt_area, const uint8_t* gt_crowd,
+                      const double* iou_thrs, int num_iou_thrs, const double* area_rng, int num_area_rng,
+                      uint64_t* dt_match, uint64_t* dt_ignore, int32_t* npig, mtlssl_stream_t stream);
 
 /* Auxiliary-task labels from the groundtruth alone (Trainer(aux_labels="generate")): what the reference computes once,
  * offline, when it writes a record (create_records/create_pascal_tf_record.py:120-421), made per step on the device

@@ -59,7 +59,7 @@ FIELD_KIND = {
     "learning_rate": "LearningRate", "manual_step_learning_rate": "ManualStepLearningRate",
     "constant_learning_rate": "ConstantLearningRate",
     "exponential_decay_learning_rate": "ExponentialDecayLearningRate", "schedule": "LearningRateSchedule",
-    "hard_example_miner": "HardExampleMiner",
+    "hard_example_miner": "HardExampleMiner", "coco_eval_options": "CocoEvalOptions",
     # protos/preprocessor.proto: the PreprocessingStep options mtl_ssl_amd.preprocessor runs
     "random_horizontal_flip": "RandomHorizontalFlip", "normalize_image": "NormalizeImage",
     "subtract_channel_mean": "SubtractChannelMean", "random_adjust_brightness": "RandomAdjustBrightness",
@@ -141,6 +141,9 @@ DEFAULTS = {
                     # train.proto:84-86: summaries (trainer.train writes them; show_image_summary feeds nothing in the
                     # reference and is accepted and ignored)
                     "show_image_summary": False, "save_summaries_secs": 120},
+    # protos/eval.proto:71-80 (eval_config.coco_eval_options; mtl_ssl_amd/eval.py coco_eval_options)
+    "CocoEvalOptions": {"eval_metric_index": [], "eval_class_type": 0,
+                        "eval_ann_filename": "../data/mscoco/annotations/instances_val2017.json"},
     # protos/optimizer.proto
     "Optimizer": {"use_moving_average": True, "moving_average_decay": 0.9999},
     "MomentumOptimizer": {"momentum_optimizer_value": 0.9, "learning_rate": "@LearningRate"},

@@ -20,6 +20,18 @@ import numpy as np
 from .create_pascal_tf_record import aux_label_features, read_label_map
 
 
+def read_instances(path):
+    """An instances JSON indexed the way the converter and the evaluator need it: (the parsed file, {category id:
+    name}, {image id: its annotations in file order})."""
+    with open(path) as fh:
+        ann = json.load(fh)
+    cats = {int(c["id"]): c["name"] for c in ann.get("categories", [])}
+    per_image = {}
+    for a in ann.get("annotations", []):
+        per_image.setdefault(a["image_id"], []).append(a)
+    return ann, cats, per_image
+
+
 def clip_box(bbox, width, height):
     """[x, y, w, h] clipped to the image — boundary_check :73-84."""
     l, t, w, h = bbox
@@ -70,12 +82,8 @@ def convert(data_dir, year, set_name, output_name="coco", annotations_dir="annot
     rng = labels.PyRandom(seed)
     done = {}
     for s in (["train", "val"] if set_name == "trainval" else [set_name]):
-        ann = json.load(open(os.path.join(data_dir, annotations_dir, "instances_%s%s.json" % (s, year))))
-        cats = {int(c["id"]): c["name"] for c in ann.get("categories", [])}
+        ann, cats, per_image = read_instances(os.path.join(data_dir, annotations_dir, "instances_%s%s.json" % (s, year)))
         K = max(list((label_map or {}).values()) + list(cats) + [1])
-        per_image = {}
-        for a in ann.get("annotations", []):
-            per_image.setdefault(a["image_id"], []).append(a)
         records, empty = [], 0
         for i, info in enumerate(ann["images"]):
             if log_every and i % log_every == 0:

@@ -6,6 +6,9 @@ With mtl.window / closeness / edgemask the model also gets the record's groundtr
 mtl/window_map, mtl/closeness_diff and mtl/edgemask_ap (mtl_metrics.py); eval_config.nms_type / nms_threshold /
 soft_nms_sigma re-suppress each class's detections on the device before the evaluator sees them
 (utils/per_image_evaluation.py:35-68, 258).
+With 'coco_metrics' the evaluator's greedy match runs on the device (ops.coco_match), and eval_config.coco_eval_options
+adds the COCO_Eval/<class>/<metric> keys it selects and may name an annotation file as the groundtruth
+(eval_util.py:489-549).
 eval_config.calc_loss adds the model's losses (Loss/<name>, FasterRCNNMetaArch.eval_loss on the device);
 submission_format_output writes the test servers' files instead of metrics; a metrics run with --eval_dir keeps the
 best state under <eval_dir>/best/ (main_subset); --run_once=false evaluates every new state of --checkpoint_dir
@@ -46,6 +49,97 @@ def eval_nms_options(ec):
     f32 = lambda v: float(np.float32(v))
     return (nms_type, f32(ec.get("nms_threshold", 1.0)), f32(ec.get("soft_nms_sigma", 0.5)),
             f32(ec.get("iou_threshold", 0.5)))
+
+
+# eval_util.py:489-492: the reference's names of the twelve COCO numbers, in pycocotools' order
+COCO_METRIC_NAMES = ("AP", "AP_IoU50", "AP_IoU75", "AP_small", "AP_medium", "AP_large",
+                     "AR_max1", "AR_max10", "AR_max100", "AR_small", "AR_medium", "AR_large")
+
+
+def coco_eval_options(ec):
+    """eval_config.coco_eval_options (eval_util.py:495-522) -> None without the message, else dict(metric_index = the
+    chosen rows of the twelve, in ascending order; class_type 0 = the row 'All', 1 = 'All' and every category;
+    ann_filename = the annotation file when the config names one, else None). The two ValueErrors are the
+    reference's."""
+    from . import config
+    opts = ec.get("coco_eval_options")
+    if opts is None:
+        return None
+    if not isinstance(opts, config.Msg):
+        raise ValueError("eval_config.coco_eval_options: a message expected, got %r" % (opts,))
+    opts.kind = "CocoEvalOptions"
+    index = [int(v) for v in opts.eval_metric_index] or [0]
+    if min(index) < 0 or max(index) > len(COCO_METRIC_NAMES) - 1:
+        raise ValueError("eval_metric_index")
+    class_type = int(opts.eval_class_type)
+    if class_type < 0 or class_type > 1:
+        raise ValueError("eval_class_type")
+    ann = str(opts.eval_ann_filename) if opts.has("eval_ann_filename") else ""
+    return dict(metric_index=sorted(set(index)), class_type=class_type, ann_filename=ann or None)
+
+
+def coco_class_names(num_classes, label_map_path=""):
+    """{category id 1..K: name} of the COCO_Eval rows: the names of label_map_path — a category the map does not name
+    has no row (eval_util.py:534-537) — or 'category_<id>' for every category without a map."""
+    if not label_map_path:
+        return {i: "category_%d" % i for i in range(1, int(num_classes) + 1)}
+    from .create_pascal_tf_record import read_label_map
+    names = {int(i): n for n, i in read_label_map(label_map_path).items()}
+    return {i: names[i] for i in range(1, int(num_classes) + 1) if i in names}
+
+
+def coco_eval_keys(res, options, class_names):
+    """eval_util.py:519-547: {'COCO_Eval/<class name>/<metric name>': value} from CocoDetectionEvaluator.evaluate()'s
+    stats (the row 'All', always first) and per_class_stats (one row per named category with class_type 1)."""
+    rows = [("All", res["stats"])]
+    if options["class_type"] == 1:
+        rows += [(class_names[k + 1], res["per_class_stats"][k]) for k in range(len(res["per_class_stats"]))
+                 if k + 1 in class_names]
+    return {"COCO_Eval/%s/%s" % (name, COCO_METRIC_NAMES[i]): float(row[i])
+            for name, row in rows for i in options["metric_index"]}
+
+
+class CocoAnnotations:
+    """Groundtruth of the COCO evaluator from an instances JSON (coco_eval_options.eval_ann_filename), which holds what
+    the records do not: crowd flags and segmentation areas. Only the images that are evaluated count (the reference
+    evaluates against every image of the file)."""
+
+    def __init__(self, path):
+        from .create_mscoco_tf_record import read_instances
+        ann, _, self.per_image = read_instances(path)
+        self.path = path
+        self.images = {int(i["id"]): i for i in ann.get("images", [])}
+
+    def image(self, source_id):
+        """image/source_id of a record -> (integer image id, (height, width) in pixels of the original image, boxes
+        [G,4] (ymin, xmin, ymax, xmax) in those pixels, classes 0-based = category_id - 1, iscrowd, area)."""
+        try:
+            image_id = int(source_id)
+        except (TypeError, ValueError):
+            image_id = None
+        if image_id not in self.images:
+            raise ValueError("evaluated image %r (image/source_id) is not among the images of %s"
+                             % (source_id, self.path))
+        info, anns = self.images[image_id], self.per_image.get(image_id, [])
+        xywh = np.asarray([a["bbox"] for a in anns], np.float64).reshape(-1, 4)
+        boxes = np.stack([xywh[:, 1], xywh[:, 0], xywh[:, 1] + xywh[:, 3], xywh[:, 0] + xywh[:, 2]], 1)
+        return (image_id, (int(info["height"]), int(info["width"])), boxes,
+                np.asarray([int(a["category_id"]) - 1 for a in anns], np.int64),
+                np.asarray([bool(a.get("iscrowd", 0)) for a in anns], bool),
+                np.asarray([float(a["area"]) if "area" in a else float(a["bbox"][2]) * float(a["bbox"][3])
+                            for a in anns], np.float64))
+
+
+def coco_annotations(options, log=None):
+    """The CocoAnnotations of options['ann_filename'] when the config names a file that exists; otherwise None —
+    groundtruth comes from the records — and one line says so (the reference returns no metrics without the file)."""
+    log = log or (lambda msg: print(msg, file=sys.stderr, flush=True))
+    path = options["ann_filename"]
+    if path and os.path.exists(path):
+        return CocoAnnotations(path)
+    log("coco_eval_options.eval_ann_filename %s: COCO groundtruth comes from the records (no crowd flags, box areas)"
+        % ("is not set" if not path else "%r does not exist" % path))
+    return None
 
 
 def suppress_per_class(boxes, scores, classes, scale, num_classes, nms_type, nms_threshold, sigma, max_per_class,
@@ -162,6 +256,10 @@ def main(argv=None):
     cats = eval_workflow.categories(K, str(reader.get("label_map_path", "") or "")) if (submission or n_vis) else None
     if submission and not f.eval_dir:
         raise ValueError("eval_config.submission_format_output writes <eval_dir>/detection_results/: give --eval_dir")
+    # eval_util.py:489-549: which COCO_Eval/<class>/<metric> keys to report, and the annotation file as groundtruth
+    coco_opts = coco_eval_options(ec) if (coco and not submission) else None
+    coco_names = coco_class_names(K, str(reader.get("label_map_path", "") or "")) if coco_opts else None
+    coco_ann = coco_annotations(coco_opts) if coco_opts else None
 
     def evaluate_state(fh):
         """One evaluation of the state in the open file fh (eval_util.run_checkpoint_once)."""
@@ -175,7 +273,8 @@ def main(argv=None):
                 raise ValueError(checkpoint.NO_MOVING_AVERAGES % fh.name)
         model.prepare()
         # evaluator.py:318-322: iou_threshold is PASCAL's matching threshold; COCO keeps its .50:.05:.95
-        ev = evaluation.CocoDetectionEvaluator(K) if coco else evaluation.PascalDetectionEvaluator(K, iou_thr)
+        # the COCO evaluator matches on the device (ops.coco_match): the same numbers as its host loops, bit for bit
+        ev = evaluation.CocoDetectionEvaluator(K, device=dev) if coco else evaluation.PascalDetectionEvaluator(K, iou_thr)
         mm = mtl_metrics.MtlMetrics()
         missing = {}
         em_counts = []
@@ -282,19 +381,28 @@ def main(argv=None):
                     closeness_error = str(e)
             # evaluator.py:137-150 hands the COCO evaluator absolute boxes, the PASCAL one either (IoU is scale-free)
             scale = np.asarray([H, W, H, W], np.float64) if coco else 1.0
-            gt_boxes = np.asarray(b["groundtruth_boxes"][0], np.float64).reshape(-1, 4) * scale
-            gt_cls = np.asarray(b["groundtruth_classes"][0]).argmax(1)
-            if coco:
-                ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls)
-            else:     # evaluator.py:196-201 -> eval_util.py:332-334: PASCAL's difficult boxes are ignored, not missed
-                diff = b.get("groundtruth_difficult")
-                ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls,
-                                                      is_difficult=None if diff is None else np.asarray(diff[0], bool))
+            image_key = n_img
+            if coco_ann is not None:
+                # groundtruth from the annotation file, keyed by the integer source id, in the pixels of the ORIGINAL
+                # image (the file's height / width): the detections are scaled to that frame as well
+                sid = None if b.get("source_id") is None else b["source_id"][0]
+                image_key, (oh, ow), gt_boxes, gt_cls, gt_crowd, gt_area = coco_ann.image(sid)
+                scale = np.asarray([oh, ow, oh, ow], np.float64)
+                ev.add_single_ground_truth_image_info(image_key, gt_boxes, gt_cls, is_crowd=gt_crowd, areas=gt_area)
+            else:
+                gt_boxes = np.asarray(b["groundtruth_boxes"][0], np.float64).reshape(-1, 4) * scale
+                gt_cls = np.asarray(b["groundtruth_classes"][0]).argmax(1)
+                if coco:
+                    ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls)
+                else:     # evaluator.py:196-201 -> eval_util.py:332-334: PASCAL's difficult boxes are ignored, not missed
+                    diff = b.get("groundtruth_difficult")
+                    ev.add_single_ground_truth_image_info(
+                        n_img, gt_boxes, gt_cls, is_difficult=None if diff is None else np.asarray(diff[0], bool))
             if eval_nms is None:
-                ev.add_single_detected_image_info(n_img, np.asarray(d["detection_boxes"][0][:n], np.float64) * scale,
+                ev.add_single_detected_image_info(image_key, np.asarray(d["detection_boxes"][0][:n], np.float64) * scale,
                                                   d["detection_scores"][0][:n], d["detection_classes"][0][:n])
             else:
-                ev.add_single_detected_image_info(n_img, *suppress_per_class(
+                ev.add_single_detected_image_info(image_key, *suppress_per_class(
                     d["detection_boxes"][0][:n], d["detection_scores"][0][:n], d["detection_classes"][0][:n], scale, K,
                     nms_type, nms_thr, sigma, eval_nms, dev))
             n_img += 1
@@ -315,8 +423,12 @@ def main(argv=None):
         res = ev.evaluate()
         out = {"global_step": int(step), "num_images": n_img}
         for k, v in res.items():
-            if k not in ("precisions", "recalls"):           # the per-class curves stay in the evaluator
+            # the per-class curves stay in the evaluator; the per-category COCO table is reported through the
+            # COCO_Eval/ keys that coco_eval_options asks for
+            if k not in ("precisions", "recalls", "per_class_stats"):
                 out[k] = _plain(v)
+        if coco_opts is not None:
+            out.update(coco_eval_keys(res, coco_opts, coco_names))
         mres = mm.evaluate()
         if closeness_error is not None:
             mres.pop("mtl/closeness_diff", None)

@@ -190,6 +190,10 @@ class CocoDetectionEvaluator:
       "ignored" instead of true/false positive; regular boxes are preferred over ignored ones;
     * precision is made monotonically non-increasing and sampled at the recall thresholds; AP / AR are the
       means over the entries that exist (-1 where a category has no groundtruth).
+
+    `_iou` and `_evaluate_image` define the match. With a CUDA `device` evaluate() runs it there instead
+    (ops.coco_match, one launch for all images and categories, pinned bit for bit against these two
+    functions); the accumulation after it is the same host code on both paths.
     """
     IOU_THRS = np.linspace(0.5, 0.95, 10)
     REC_THRS = np.linspace(0.0, 1.0, 101)
@@ -198,8 +202,17 @@ class CocoDetectionEvaluator:
     NAMES = ("AP", "AP50", "AP75", "AP_small", "AP_medium", "AP_large",
              "AR_1", "AR_10", "AR_100", "AR_small", "AR_medium", "AR_large")
 
-    def __init__(self, num_classes, max_detections_per_image=100):
+    def __init__(self, num_classes, max_detections_per_image=100, device=None):
+        """device: a CUDA device runs the greedy match of evaluate() there (ops.coco_match: every (image, category)
+        pair in one launch, bit for bit what _evaluate_image gives); None keeps the numpy loops."""
         self.K, self.cap = int(num_classes), int(max_detections_per_image)
+        if device is not None:
+            import torch
+            device = torch.device(device)
+            if device.type != "cuda":
+                raise ValueError("CocoDetectionEvaluator: device %s is no CUDA device (None = the host path)" % device)
+        self.device = device
+        self.timings = {}
         self.clear()
 
     def clear(self):
@@ -273,55 +286,171 @@ class CocoDetectionEvaluator:
         dig |= (~dtm) & ((darea < rng[0]) | (darea > rng[1]))[None, :]
         return ds, dtm, dig, int(np.sum(~gig))
 
-    def evaluate(self):
-        """-> dict(stats = the 12 COCO numbers in pycocotools' order, by name too, per_class_ap [K])."""
-        T, R, A, M = len(self.IOU_THRS), len(self.REC_THRS), len(self.AREA_RNG), len(self.MAX_DETS)
-        precision = -np.ones((T, R, self.K, A, M))
-        recall = -np.ones((T, self.K, A, M))
-        keys = sorted(set(self.gt) | set(self.dt), key=str)
+    def _accumulate(self, scores, dtm, dig, npig):
+        """One (category, area range, maxDets) cell: the detections of every image in image order with their dtm / dig
+        [T,n] -> (recall [T], precision [T,R]) (COCOeval.accumulate)."""
+        T, R = len(self.IOU_THRS), len(self.REC_THRS)
+        rec, prec = np.zeros(T), np.zeros((T, R))
+        order = np.argsort(-scores, kind="mergesort")
+        dtm, dig = dtm[:, order], dig[:, order]
+        tps = np.cumsum(dtm & ~dig, 1).astype(float)
+        fps = np.cumsum(~dtm & ~dig, 1).astype(float)
+        for t in range(T):
+            tp, fp = tps[t], fps[t]
+            rc = tp / npig
+            pr = tp / (fp + tp + np.spacing(1))
+            rec[t] = rc[-1] if len(tp) else 0
+            pr = np.maximum.accumulate(pr[::-1])[::-1]
+            inds = np.searchsorted(rc, self.REC_THRS, side="left")
+            q = np.zeros(R)
+            ok = inds < len(pr)
+            q[ok] = pr[inds[ok]]
+            prec[t] = q
+        return rec, prec
+
+    def _cells_host(self, keys):
+        """(k, a, m, scores, dtm, dig, npig) of every cell that has an image, through _evaluate_image."""
         for k in range(self.K):
             for a, rng in enumerate(self.AREA_RNG):
                 for m, md in enumerate(self.MAX_DETS):
                     res = [r for r in (self._evaluate_image(key, k, rng, md) for key in keys) if r is not None]
                     if not res:
                         continue
-                    npig = sum(r[3] for r in res)
-                    if npig == 0:
-                        continue
-                    scores = np.concatenate([r[0] for r in res])
-                    order = np.argsort(-scores, kind="mergesort")
-                    dtm = np.concatenate([r[1] for r in res], 1)[:, order]
-                    dig = np.concatenate([r[2] for r in res], 1)[:, order]
-                    tps = np.cumsum(dtm & ~dig, 1).astype(float)
-                    fps = np.cumsum(~dtm & ~dig, 1).astype(float)
-                    for t in range(T):
-                        tp, fp = tps[t], fps[t]
-                        rc = tp / npig
-                        pr = tp / (fp + tp + np.spacing(1))
-                        recall[t, k, a, m] = rc[-1] if len(tp) else 0
-                        pr = np.maximum.accumulate(pr[::-1])[::-1]
-                        inds = np.searchsorted(rc, self.REC_THRS, side="left")
-                        q = np.zeros(R)
-                        ok = inds < len(pr)
-                        q[ok] = pr[inds[ok]]
-                        precision[t, :, k, a, m] = q
+                    yield (k, a, m, np.concatenate([r[0] for r in res]), np.concatenate([r[1] for r in res], 1),
+                           np.concatenate([r[2] for r in res], 1), sum(r[3] for r in res))
+
+    def _segment_tables(self, keys):
+        """The (image, category) pairs that hold a detection or a groundtruth box, ordered by (category, image): their
+        detections (in the image's descending-score order) and groundtruth boxes (input order) as flat arrays with
+        offsets — what ops.coco_match reads. Classes outside [0, K) belong to no category, as on the host path."""
+        none_g = (np.zeros((0, 4)), np.zeros(0, int), np.zeros(0, bool), np.zeros(0))
+        none_d = (np.zeros((0, 4)), np.zeros(0), np.zeros(0, int))
+        gts, dts = [self.gt.get(key, none_g) for key in keys], [self.dt.get(key, none_d) for key in keys]
+        N = max(len(keys), 1)
+        cat = lambda parts, j, dtype: (np.concatenate([p[j] for p in parts]) if parts else np.zeros(0)).astype(dtype)
+        img = lambda parts: np.repeat(np.arange(len(parts)), [len(p[1]) for p in parts]).astype(np.int64)
+        gb, gc, gcrowd, garea = (np.concatenate([p[0] for p in gts]).reshape(-1, 4) if gts else np.zeros((0, 4)),
+                                 cat(gts, 1, np.int64), cat(gts, 2, bool), cat(gts, 3, np.float64))
+        db, ds, dc = (np.concatenate([p[0] for p in dts]).reshape(-1, 4) if dts else np.zeros((0, 4)),
+                      cat(dts, 1, np.float64), cat(dts, 2, np.int64))
+        gkey, dkey = gc * N + img(gts), dc * N + img(dts)
+        gsel = np.flatnonzero((gc >= 0) & (gc < self.K))
+        dsel = np.flatnonzero((dc >= 0) & (dc < self.K))
+        gsel = gsel[np.argsort(gkey[gsel], kind="stable")]
+        dsel = dsel[np.argsort(dkey[dsel], kind="stable")]
+        seg_key = np.unique(np.concatenate([gkey[gsel], dkey[dsel]]))
+        S = len(seg_key)
+        off = lambda k: np.concatenate([[0], np.cumsum(np.bincount(np.searchsorted(seg_key, k), minlength=S))])
+        return dict(seg_cat=seg_key // N, seg_img=seg_key % N, dt_off=off(dkey[dsel]), gt_off=off(gkey[gsel]),
+                    dt_boxes=np.ascontiguousarray(db[dsel]), dt_scores=ds[dsel], gt_boxes=np.ascontiguousarray(gb[gsel]),
+                    gt_area=garea[gsel], gt_crowd=gcrowd[gsel])
+
+    def match_on_device(self, keys, timings=None):
+        """dtm / dig [T,A,ND] bool and npig [S,A] of every segment in ONE ops.coco_match launch and one copy back; a
+        segment with more groundtruth boxes than the kernel holds goes through _evaluate_image instead. timings (a
+        dict) receives the seconds of the table build, the kernel and the copy."""
+        import time
+
+        import torch
+        from . import ops
+        T, A = len(self.IOU_THRS), len(self.AREA_RNG)
+        t0 = time.perf_counter()
+        tab = self._segment_tables(keys)
+        S, ND = len(tab["seg_cat"]), len(tab["dt_boxes"])
+        gt_off, n_gt = tab["gt_off"], np.diff(tab["gt_off"])
+        large = np.flatnonzero(n_gt > ops.COCO_MATCH_MAX_GT)
+        gkeep = np.ones(int(gt_off[-1]), bool)
+        for s in large:                                    # the kernel sees such a segment without groundtruth
+            gkeep[gt_off[s]:gt_off[s + 1]] = False
+        dev_gt_off = np.concatenate([[0], np.cumsum(np.where(n_gt > ops.COCO_MATCH_MAX_GT, 0, n_gt))])
+        up = lambda x, dtype: torch.from_numpy(np.ascontiguousarray(x, dtype)).to(self.device)
+        args = (up(tab["dt_boxes"], np.float64), up(tab["gt_boxes"][gkeep], np.float64),
+                up(tab["gt_area"][gkeep], np.float64), up(tab["gt_crowd"][gkeep], np.uint8),
+                up(self.IOU_THRS, np.float64), up(np.asarray(self.AREA_RNG), np.float64))
+        if timings is not None:
+            torch.cuda.synchronize(self.device)
+        t1 = time.perf_counter()
+        with torch.cuda.device(self.device):
+            packed = ops.coco_match(tab["dt_off"], dev_gt_off, *args)[3]
+        if timings is not None:
+            torch.cuda.synchronize(self.device)
+        t2 = time.perf_counter()
+        host = packed.cpu().numpy()
+        t3 = time.perf_counter()
+        bits = np.arange(T * A, dtype=np.uint64).reshape(T, A, 1)
+        one = np.uint64(1)
+        dtm = ((host[:ND].view(np.uint64)[None, None, :] >> bits) & one).astype(bool)
+        dig = ((host[ND:2 * ND].view(np.uint64)[None, None, :] >> bits) & one).astype(bool)
+        npig = host[2 * ND:].view(np.int32)[:S * A].reshape(S, A).astype(np.int64)
+        if S and npig.min() < 0:
+            raise RuntimeError("coco_match left a segment out (npig %d)" % int(npig.min()))
+        for s in large:
+            d0, d1 = tab["dt_off"][s], tab["dt_off"][s + 1]
+            for a, rng in enumerate(self.AREA_RNG):
+                _, m, g, n = self._evaluate_image(keys[tab["seg_img"][s]], int(tab["seg_cat"][s]), rng, d1 - d0)
+                dtm[:, a, d0:d1], dig[:, a, d0:d1], npig[s, a] = m, g, n
+        if timings is not None:
+            timings.update(table_build_s=t1 - t0, kernel_s=t2 - t1, copy_s=t3 - t2)
+        return tab, dtm, dig, npig
+
+    def _cells_device(self, keys):
+        """The cells of _cells_host from one device match: the first m detections of a segment are its maxDets = m
+        result (whether a detection matches depends only on the detections before it)."""
+        tab, dtm, dig, npig = self.match_on_device(keys, self.timings)
+        dt_off, seg_cat = tab["dt_off"], tab["seg_cat"]
+        rank = np.arange(int(dt_off[-1])) - np.repeat(dt_off[:-1], np.diff(dt_off))
+        first = np.searchsorted(seg_cat, np.arange(self.K + 1))          # segments are ordered by category
+        for k in range(self.K):
+            s0, s1 = first[k], first[k + 1]
+            if s0 == s1:
+                continue
+            d0, d1 = dt_off[s0], dt_off[s1]
+            for a in range(len(self.AREA_RNG)):
+                for m, md in enumerate(self.MAX_DETS):
+                    sel = rank[d0:d1] < md
+                    yield (k, a, m, tab["dt_scores"][d0:d1][sel], dtm[:, a, d0:d1][:, sel], dig[:, a, d0:d1][:, sel],
+                           int(npig[s0:s1, a].sum()))
+
+    def evaluate(self):
+        """-> dict(stats = the 12 COCO numbers in pycocotools' order, by name too, per_class_ap [K], per_class_stats
+        [K,12] = the 12 numbers with the category axis restricted to one category)."""
+        import time
+        T, R, A, M = len(self.IOU_THRS), len(self.REC_THRS), len(self.AREA_RNG), len(self.MAX_DETS)
+        precision = -np.ones((T, R, self.K, A, M))
+        recall = -np.ones((T, self.K, A, M))
+        keys = sorted(set(self.gt) | set(self.dt), key=str)
+        self.timings = {}
+        cells = self._cells_host(keys) if self.device is None else self._cells_device(keys)
+        spent = 0.0
+        for k, a, m, scores, dtm, dig, npig in cells:
+            if npig == 0:
+                continue
+            t0 = time.perf_counter()
+            recall[:, k, a, m], precision[:, :, k, a, m] = self._accumulate(scores, dtm, dig, npig)
+            spent += time.perf_counter() - t0
+        self.timings["accumulate_s"] = spent
 
         def mean_valid(x):
             x = x[x > -1]
             return float(x.mean()) if x.size else -1.0
 
-        def ap(iou=None, area=0, md=2):
-            p = precision if iou is None else precision[np.isclose(self.IOU_THRS, iou)]
-            return mean_valid(p[:, :, :, area, md])
+        def twelve(precision, recall):
+            def ap(iou=None, area=0, md=2):
+                p = precision if iou is None else precision[np.isclose(self.IOU_THRS, iou)]
+                return mean_valid(p[:, :, :, area, md])
 
-        def ar(area=0, md=2):
-            return mean_valid(recall[:, :, area, md])
+            def ar(area=0, md=2):
+                return mean_valid(recall[:, :, area, md])
 
-        stats = [ap(), ap(0.5), ap(0.75), ap(area=1), ap(area=2), ap(area=3),
-                 ar(md=0), ar(md=1), ar(md=2), ar(area=1), ar(area=2), ar(area=3)]
+            return [ap(), ap(0.5), ap(0.75), ap(area=1), ap(area=2), ap(area=3),
+                    ar(md=0), ar(md=1), ar(md=2), ar(area=1), ar(area=2), ar(area=3)]
+
+        stats = twelve(precision, recall)
         out = dict(zip(self.NAMES, stats))
         out["stats"] = np.asarray(stats)
         out["per_class_ap"] = np.asarray([mean_valid(precision[:, :, k, 0, 2]) for k in range(self.K)])
+        out["per_class_stats"] = np.asarray([twelve(precision[:, :, k:k + 1], recall[:, k:k + 1])
+                                             for k in range(self.K)]).reshape(self.K, 12)
         return out
 
 

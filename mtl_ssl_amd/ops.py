@@ -1039,6 +1039,44 @@ def edgemask_agreement(logits, gt_mask):
     return out
 
 
+COCO_MATCH_MAX_GT = 256              # MTLSSL_COCO_MATCH_MAX_GT: groundtruth boxes of one segment (a lane's matched set)
+
+
+def coco_match(dt_offsets, gt_offsets, dt_boxes, gt_boxes, gt_area, gt_crowd, iou_thrs, area_rng):
+    """mtlssl_coco_match: the COCO evaluator's greedy match (CocoDetectionEvaluator._evaluate_image) of every segment
+    — one (image, category) pair — in one launch. dt_offsets / gt_offsets: host ints [S+1], the segments' row ranges
+    in dt_boxes [ND,4] (per segment in descending score, already cut to the image's cap) and gt_boxes [NG,4] /
+    gt_area [NG] (float64, device) / gt_crowd [NG] (uint8, device); iou_thrs [T] and area_rng [A,2]: float64 device
+    tensors of the evaluator's own values, T*A <= 64. A segment holds at most COCO_MATCH_MAX_GT groundtruth boxes.
+    -> (dt_match [ND] int64, dt_ignore [ND] int64, npig [S,A] int32, packed): bit t*A + a of dt_match / dt_ignore is
+    dtm / dig of that detection at threshold t in area range a (read the words as uint64); the three are views of
+    `packed`, one int64 device buffer, so that a single copy brings all of them to the host."""
+    dto = np.ascontiguousarray(dt_offsets, np.int64).reshape(-1)
+    gto = np.ascontiguousarray(gt_offsets, np.int64).reshape(-1)
+    S = len(dto) - 1
+    assert S >= 0 and len(gto) == S + 1 and dto[0] == 0 and gto[0] == 0, (dto.shape, gto.shape)
+    assert (np.diff(dto) >= 0).all() and (np.diff(gto) >= 0).all(), "segment offsets must not decrease"
+    ND, NG = int(dto[-1]), int(gto[-1])
+    assert max(ND, NG) < 2 ** 29, "offsets are int32"
+    T, A = int(iou_thrs.numel()), int(area_rng.shape[0])
+    dev = iou_thrs.device
+    assert tuple(dt_boxes.shape) == (ND, 4) and tuple(gt_boxes.shape) == (NG, 4) and tuple(gt_area.shape) == (NG,) \
+        and tuple(gt_crowd.shape) == (NG,) and tuple(area_rng.shape) == (A, 2), \
+        (dt_boxes.shape, gt_boxes.shape, gt_area.shape, gt_crowd.shape, area_rng.shape)
+    f64 = torch.float64
+    packed = torch.empty((2 * ND + (S * A + 1) // 2,), dtype=torch.int64, device=dev)
+    dt_match, dt_ignore = packed[:ND], packed[ND:2 * ND]
+    npig = packed[2 * ND:].view(i32)[:S * A].view(S, A)
+    offs = torch.from_numpy(np.concatenate([dto, gto]).astype(np.int32)).to(dev)
+    lib().coco_match(ptr(offs), ptr(offs) + 4 * (S + 1), S, int(np.diff(gto).max()) if S else 0,
+                     ptr(_chk(dt_boxes, f64)) if ND else None, ptr(_chk(gt_boxes, f64)) if NG else None,
+                     ptr(_chk(gt_area, f64)) if NG else None, ptr(_chk(gt_crowd, torch.uint8)) if NG else None,
+                     ptr(_chk(iou_thrs, f64)), T, ptr(_chk(area_rng, f64)), A,
+                     ptr(dt_match) if ND else None, ptr(dt_ignore) if ND else None, ptr(npig) if S else None,
+                     _stream())
+    return dt_match, dt_ignore, npig, packed
+
+
 def draw_boxes(image, boxes, colors, thickness):
     """mtlssl_draw_boxes: paints the outlines of boxes [n,4] int32 (ymin, xmin, ymax, xmax absolute, half open) in
     colors [n,3] uint8 into image, a uint8 [H,W,3] device tensor whose rows may be strided (a column slice of a wider
