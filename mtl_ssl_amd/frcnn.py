@@ -498,13 +498,19 @@ class FasterRCNNMetaArch:
     def _format_groundtruth_data(self, H, W):
         """faster_rcnn_meta_arch.py:1218-1266: absolute boxes (+ bg-padded classes)."""
         if "boxes_abs" not in self._gt:
-            # constants are created once: a host->device torch.tensor() is a synchronising copy, which
-            # would make the launch thread wait for the whole previous step every iteration
-            key = ("hw_scale", H, W)
-            if key not in self._consts:
-                self._consts[key] = torch.tensor([H, W, H, W], dtype=f32, device=self.ps.device)
-            self._gt["boxes_abs"] = ops.scale_channels(self._gt["boxes_norm"].contiguous(), self._consts[key])
+            self._gt["boxes_abs"] = ops.scale_channels(self._gt["boxes_norm"].contiguous(), self._hw_scales(H, W)[0])
         return self._gt
+
+    def _hw_scales(self, H, W):
+        """([H, W, H, W], [1/H, 1/W, 1/H, 1/W]): the per-coordinate factors between normalised and absolute boxes."""
+        # constants are created once: a host->device torch.tensor() is a synchronising copy, which
+        # would make the launch thread wait for the whole previous step every iteration
+        key = ("hw_scale", H, W)
+        if key not in self._consts:
+            dev = self.ps.device
+            self._consts[key] = (torch.tensor([H, W, H, W], dtype=f32, device=dev),
+                                 torch.tensor([1.0 / H, 1.0 / W, 1.0 / H, 1.0 / W], dtype=f32, device=dev))
+        return self._consts[key]
 
     def _crop(self, F, boxes_norm_flat, box_ind, want_argmax):
         c = self.cfg
@@ -528,27 +534,32 @@ class FasterRCNNMetaArch:
             return ops.sample_proposals(props, nprop, gt["boxes_abs"], gt["num"], gt["classes_bg"],
                                         self.max_num_proposals, c.second_stage_balance_fraction, self.seed,
                                         stream0, 2, H, W)
-        dev = props.device
-        inv = torch.tensor([1.0 / H, 1.0 / W, 1.0 / H, 1.0 / W], dtype=f32, device=dev)
-        fwd = torch.tensor([H, W, H, W], dtype=f32, device=dev)
+        fwd, inv = self._hw_scales(H, W)
         norm = ops.scale_channels(props, inv)
         return ops.scale_channels(norm, fwd), norm, nprop       # normalized_to_image_coordinates :693
 
-    def _predict_second_stage(self, pd):
-        """faster_rcnn_meta_arch.py:611-719."""
-        c, mtl = self.cfg, self._mtl
+    def _proposals_to_crop(self, pd):
+        """_postprocess_rpn (:1055-1132), the head of both meta-architectures' second stage: the proposals as absolute
+        and normalised [B, N2, 4] boxes with their valid count, the normalised ones flattened to [B*N2, 4], and their
+        box_ind."""
+        c = self.cfg
         B, H, W, _ = pd["image_shape"]
-        F = pd["rpn_features_to_crop"]
         gt = self._format_groundtruth_data(H, W) if self._is_training else None
-        # _postprocess_rpn :1055-1132
         props, _scores, nprop = ops.rpn_proposals(
             pd["rpn_box_encodings"], pd["rpn_objectness_predictions_with_background"], pd["anchors"],
             H, W, c.first_stage_nms_score_threshold, c.first_stage_nms_iou_threshold,
             int(c.first_stage_max_proposals))
         N2 = self.max_num_proposals
         boxes_abs, boxes_norm, num = self._second_stage_proposals(props, nprop, gt, H, W)
-        box_ind = self._box_ind(B, N2, F.device)
-        flat = boxes_norm.view(B * N2, 4)
+        box_ind = self._box_ind(B, N2, pd["rpn_features_to_crop"].device)
+        return boxes_abs, boxes_norm, num, boxes_norm.view(B * N2, 4), box_ind
+
+    def _predict_second_stage(self, pd):
+        """faster_rcnn_meta_arch.py:611-719."""
+        mtl = self._mtl
+        F = pd["rpn_features_to_crop"]
+        B, N2 = F.shape[0], self.max_num_proposals
+        boxes_abs, boxes_norm, num, flat, box_ind = self._proposals_to_crop(pd)
         crops, argmax = self._crop(F, flat, box_ind, True)
         early_win = None
         if (self._is_training and mtl.refine and mtl.window and self._shared_classifier is False
@@ -664,27 +675,31 @@ class FasterRCNNMetaArch:
         # stream (measured with a 1-rank communicator: 60.2 ms/step against 55.5)
         return getattr(self._wgrad_exec(), "stream", None)
 
+    def _expand_window_class_predictions(self, pd):
+        """Window-class predictions of every proposal's N_EXPAND windows, [B, N_EXPAND, N2] row order: the step of
+        predict_with_mtl_results that depends on the window head's kind."""
+        if "_refine_win" in pd:                   # issued early on the third stream (_predict_second_stage)
+            ops.wait_on(self._refine_stream(), "refine: early window pass")
+            win = pd.pop("_refine_win")
+            win.record_stream(torch.cuda.current_stream())
+            return win
+        return self._refine_window_predictions(pd["rpn_features_to_crop"], pd["proposal_boxes_normalized"])
+
     def predict_with_mtl_results(self, pd):
         """faster_rcnn_meta_arch.py:764-846, executed per image."""
         mtl = self._mtl
-        F = pd["rpn_features_to_crop"]
-        B = F.shape[0]
+        B = pd["rpn_features_to_crop"].shape[0]
         N2 = self.max_num_proposals
         K1 = self.num_classes + 1
         cls = pd["class_predictions_with_background"]
         win = None
         if mtl.window:
-            if "_refine_win" in pd:               # issued early on the third stream (_predict_second_stage)
-                ops.wait_on(self._refine_stream(), "refine: early window pass")
-                win = pd.pop("_refine_win")
-                win.record_stream(torch.cuda.current_stream())
-            else:
-                win = self._refine_window_predictions(F, pd["proposal_boxes_normalized"])
+            win = self._expand_window_class_predictions(pd)
             pd["expand_window_class_predictions"] = win.view(B, self.N_EXPAND, N2, K1)
         clo = pd["closeness_predictions"] if mtl.closeness else None
         net = ops.refine_concat(cls, win, clo, B, N2, self.N_EXPAND, bool(mtl.global_closeness))
         hidden, sctx = net, None
-        if self.refine_stack is not None:
+        if self.refine_stack is not None:          # :833-840: FC stack + dropout before the refiner
             hidden, sctx = self.refine_stack.forward(net, self._is_training, self.seed, self.step)
         refined = self.refine_fc.forward(hidden)
         pd["_refine_hidden"], pd["_refine_ctx"] = hidden, sctx
@@ -712,10 +727,7 @@ class FasterRCNNMetaArch:
                 gt = self._format_groundtruth_data(H, W)
                 _, norm, num = self._second_stage_proposals(boxes, num, gt, H, W)
                 return {"detection_boxes": norm, "num_detections": num}
-            key = ("inv_hw", H, W)
-            if key not in self._consts:
-                self._consts[key] = torch.tensor([1.0 / H, 1.0 / W, 1.0 / H, 1.0 / W], dtype=f32, device=boxes.device)
-            return {"detection_boxes": ops.scale_channels(boxes, self._consts[key]), "detection_scores": scores,
+            return {"detection_boxes": ops.scale_channels(boxes, self._hw_scales(H, W)[1]), "detection_scores": scores,
                     "num_detections": num}
         key = "mtl_refined_class_predictions_with_background"
         cls = pd[key] if (self._mtl.refine and key in pd) else pd["class_predictions_with_background"]
@@ -741,134 +753,26 @@ class FasterRCNNMetaArch:
         part: "all", or the two halves a trainer may schedule apart — "early" = every term that does not need the
         refiner's output (a chain of small latency-bound kernels that can run on a side stream under the refiner's
         tower forward), then "late" = the refined-classification term (after predict_with_mtl_results)."""
-        c, mtl = self.cfg, self._mtl
-        B, H, W, _ = pd["image_shape"]
-        gt = self._format_groundtruth_data(H, W)
-        dev = self.ps.device
-        g = float(loss_scale)
+        second = not self._first_stage_only
+        new = {}                    # the gradients this call makes, unscaled
         if part == "late":
-            losses, d = pd["_losses_early"], pd["_d"]
-            if self._first_stage_only:
-                return losses
-            dt, cls_s = pd["_det_targets"], pd["_cls_s"]
-            cls_targets = dt["cls_targets"].view(B * self.max_num_proposals, self.num_classes + 1)
-            if mtl.refine:
-                rs = cls_s if c.second_stage_classification_loss_weight == mtl.refined_classification_loss_weight \
-                    else ops.detector_loss_scales(dt["cls_weights"], dt["reg_weights"], pd["num_proposals"], None,
-                                                  mtl.refined_classification_loss_weight, 0.0, 0.0)[0]
-                rl, d_ref = ops.softmax_ce(pd["mtl_refined_class_predictions_with_background"], cls_targets,
-                                           rs.view(-1))
-                losses["refined_classification_loss"] = ops.reduce_sum(rl)
-                if g != 1.0:
-                    ops.axpby(d_ref, d_ref, g, 0.0)
-                d["refined_class_predictions"] = d_ref
-            return losses
-        losses, d = {}, {}
-        # ---- _loss_rpn :1591-1668
-        anchors = pd["anchors"]
-        n = anchors.shape[0]
-        if "um" not in self._consts:
-            K1_ = self.num_classes + 1
-            self._consts["um"] = torch.zeros((1,), dtype=f32, device=dev)
-            self._consts["um2"] = torch.tensor([1.0] + [0.0] * (K1_ - 1), dtype=f32, device=dev)
-        um = self._consts["um"]
-        tg = ops.assign_targets(anchors, gt["boxes_abs"], gt["num"], None, um, 0.7, 0.3, True)
-        cls_t = tg["cls_targets"].view(B, n)
-        sampled = ops.balanced_sample(tg["cls_weights"], cls_t, int(c.first_stage_minibatch_size),
-                                      c.first_stage_positive_balance_fraction, self.seed,
-                                      (2 * self.step * 65536) & 0xFFFFFFFF, 2)
-        loc_s, obj_s = ops.rpn_loss_scales(sampled, tg["reg_weights"],
-                                           c.first_stage_localization_loss_weight / B,
-                                           c.first_stage_objectness_loss_weight / B)
-        rl, d_enc = ops.smooth_l1(pd["rpn_box_encodings"], tg["reg_targets"], loc_s, 3.0)
-        losses["first_stage_localization_loss"] = ops.reduce_sum(rl)
-        rl, d_obj = ops.softmax_ce(pd["rpn_objectness_predictions_with_background"], ops.onehot2(cls_t), obj_s)
-        losses["first_stage_objectness_loss"] = ops.reduce_sum(rl)
-        d["rpn_box_encodings"], d["rpn_objectness"] = d_enc, d_obj
-        pd["_rpn_targets"] = dict(tg, sampled=sampled)
-        if self._first_stage_only:
-            if mtl.edgemask:
-                em = self._edgemask
-                mh, mw = em.shape[2], em.shape[3]
-                tgt, sc = ops.edgemask_targets(em, mtl.edgemask_loss_weight / (B * mh * mw))
-                pr = ops.resize_bilinear_fwd(pd["edgemask_predictions"], mh, mw)
-                rl, d_pr = ops.softmax_ce(pr, tgt, sc.view(-1))
-                losses["edgemask_loss"] = ops.reduce_sum(rl)
-                d["edgemask_resized"] = d_pr
-            if g != 1.0:
-                for k in d:
-                    ops.axpby(d[k], d[k], g, 0.0)
-            pd["_d"], pd["_losses_early"], pd["_cls_s"] = d, losses, None
-            return losses
-        # ---- _loss_box_classifier :1670-1793
-        N2, K, K1 = self.max_num_proposals, self.num_classes, self.num_classes + 1
-        um2 = self._consts["um2"]
-        dt = ops.assign_targets(pd["proposal_boxes"], gt["boxes_abs"], gt["num"], gt["classes_bg"], um2,
-                                0.5, 0.5, False, gt_extra=gt["closeness"] if mtl.closeness else None)
-        cls_s, loc_s2, clo_s = ops.detector_loss_scales(
-            dt["cls_weights"], dt["reg_weights"], pd["num_proposals"],
-            dt.get("extra_targets") if mtl.closeness else None,
-            c.second_stage_classification_loss_weight, c.second_stage_localization_loss_weight,
-            mtl.closeness_loss_weight)
-        cls_targets = dt["cls_targets"].view(B * N2, K1)
-        rl_loc, d_box = ops.box_select_smooth_l1(pd["refined_box_encodings"], cls_targets,
-                                                 dt["reg_targets"].view(B * N2, 4), loc_s2.view(-1), 1.0)
-        rl_cls, d_cls = ops.softmax_ce(pd["class_predictions_with_background"], cls_targets, cls_s.view(-1))
-        if self._hard_miner is not None:
-            # :1758-1762 -> _unpad_proposals_and_apply_hard_mining (:1902-1946) over ALL the NMS survivors of the RPN (no
-            # balanced sample when a miner is configured, :475, :1118): greedy NMS over the first num_proposals boxes
-            # scored by their loss, the terms become sums over the mined proposals, the others get no gradient. Mined
-            # per image and summed; the reference's loop `return`s inside its first iteration (:1930), i.e. a clone
-            # with more than one image would silently drop the others' second-stage loss — not reproduced.
-            hm = self._hard_miner
-            lm, cm, sel, nsel = ops.hard_example_mining(rl_loc.view(B, N2), rl_cls.view(B, N2), pd["proposal_boxes"],
-                                                        pd["num_proposals"], d_box, d_cls, hm["num_hard_examples"],
-                                                        hm["iou_threshold"], hm["loss_type"])
-            rl_loc, rl_cls = lm, cm
-            pd["_mined"] = (sel, nsel)
-        losses["second_stage_localization_loss"] = ops.reduce_sum(rl_loc)
-        losses["second_stage_classification_loss"] = ops.reduce_sum(rl_cls)
-        d["refined_box_encodings"], d["class_predictions"] = d_box, d_cls
-        pd["_det_targets"] = dt
-        if mtl.closeness:
-            rl, d_clo = ops.softmax_ce(pd["closeness_predictions"], dt["extra_targets"].view(B * N2, K1),
-                                       clo_s.view(-1), col0=1)
-            losses["closeness_classification_loss"] = ops.reduce_sum(rl)
-            d["closeness_predictions"] = d_clo
-        # ---- _loss_window_class :1839-1858
-        if mtl.window:
-            wc = self._window["classes"].view(-1, K1)
-            ws = torch.full((wc.shape[0],), mtl.window_class_loss_weight / wc.shape[0], dtype=f32, device=dev)
-            rl, d_win = ops.softmax_ce(pd["window_class_predictions"], wc, ws)
-            losses["window_class_loss"] = ops.reduce_sum(rl)
-            d["window_class_predictions"] = d_win
-        # ---- _loss_edgemask :1860-1881
-        if mtl.edgemask:
-            em = self._edgemask
-            mh, mw = em.shape[2], em.shape[3]
-            tgt, sc = ops.edgemask_targets(em, mtl.edgemask_loss_weight / (B * mh * mw))
-            pr = ops.resize_bilinear_fwd(pd["edgemask_predictions"], mh, mw)
-            rl, d_pr = ops.softmax_ce(pr, tgt, sc.view(-1))
-            losses["edgemask_loss"] = ops.reduce_sum(rl)
-            d["edgemask_resized"] = d_pr
+            losses, d, cls_s = pd["_losses_early"], pd["_d"], pd["_cls_s"]
+        else:
+            losses, d, cls_s = {}, {}, None
+            self._loss_rpn(pd, self.step, losses, new, True)
+            if second:
+                cls_s = self._loss_box_classifier(pd, losses, new, True)
+                self._loss_window_class(pd, losses, new, True)
+            self._loss_edgemask(pd, losses, new, True)
         if part == "early":
-            if g != 1.0:
-                for k in d:
-                    ops.axpby(d[k], d[k], g, 0.0)
-            pd["_d"], pd["_losses_early"], pd["_cls_s"] = d, losses, cls_s
-            return losses
-        # ---- _loss_refined_classifier :1795-1837
-        if mtl.refine:
-            rs = cls_s if c.second_stage_classification_loss_weight == mtl.refined_classification_loss_weight \
-                else ops.detector_loss_scales(dt["cls_weights"], dt["reg_weights"], pd["num_proposals"], None,
-                                              mtl.refined_classification_loss_weight, 0.0, 0.0)[0]
-            rl, d_ref = ops.softmax_ce(pd["mtl_refined_class_predictions_with_background"], cls_targets,
-                                       rs.view(-1))
-            losses["refined_classification_loss"] = ops.reduce_sum(rl)
-            d["refined_class_predictions"] = d_ref
+            pd["_losses_early"], pd["_cls_s"] = losses, cls_s
+        elif second:
+            self._loss_refined_classifier(pd, cls_s, losses, new, True)
+        g = float(loss_scale)
         if g != 1.0:
-            for k in d:
-                ops.axpby(d[k], d[k], g, 0.0)
+            for t in new.values():
+                ops.axpby(t, t, g, 0.0)
+        d.update(new)
         pd["_d"] = d
         return losses
 
@@ -895,82 +799,160 @@ class FasterRCNNMetaArch:
             raise ValueError("eval_loss is the loss of an inference model; a training model calls loss()")
         if self._hard_miner is not None:
             raise ValueError("eval_config.calc_loss with a hard_example_miner is not supported")
-        c, mtl = self.cfg, self._mtl
+        second = not self._first_stage_only
+        losses = {}
+        self._loss_rpn(pd, int(image_index), losses, None, False)
+        if second:
+            cls_s = self._loss_box_classifier(pd, losses, None, False)
+            if self._mtl.window and self._window["classes"].numel() == 0:
+                losses["window_class_loss"] = torch.zeros((1,), dtype=f32, device=self.ps.device)
+            else:
+                self._loss_window_class(pd, losses, None, False)
+        self._loss_edgemask(pd, losses, None, False)
+        if second:
+            self._loss_refined_classifier(pd, cls_s, losses, None, False)
+        return losses
+
+    # ------------------------------------------------------------------ the loss terms, cut as the reference cuts them
+    # Each adds its entries to `losses` and, with want_grad, the gradients w.r.t. its prediction tensors to `d`
+    # (unscaled: loss() applies loss_scale).
+    def _unmatched_class_targets(self):
+        """Class target of an unmatched anchor (the one objectness column: 0) and of an unmatched proposal (one-hot
+        background)."""
+        if "um" not in self._consts:
+            dev = self.ps.device
+            self._consts["um"] = torch.zeros((1,), dtype=f32, device=dev)
+            self._consts["um2"] = torch.tensor([1.0] + [0.0] * self.num_classes, dtype=f32, device=dev)
+        return self._consts["um"], self._consts["um2"]
+
+    def _loss_rpn(self, pd, draw, losses, d, want_grad):
+        """faster_rcnn_meta_arch.py:1591-1668. `draw` seeds the minibatch draw: the step in training, the image's index
+        in evaluation."""
+        c = self.cfg
         B, H, W, _ = pd["image_shape"]
         gt = self._format_groundtruth_data(H, W)
-        dev = self.ps.device
-        losses = {}
-        K, K1 = self.num_classes, self.num_classes + 1
-        if "um" not in self._consts:
-            self._consts["um"] = torch.zeros((1,), dtype=f32, device=dev)
-            self._consts["um2"] = torch.tensor([1.0] + [0.0] * (K1 - 1), dtype=f32, device=dev)
-        # ---- _loss_rpn :1591-1668
         anchors = pd["anchors"]
         n = anchors.shape[0]
-        tg = ops.assign_targets(anchors, gt["boxes_abs"], gt["num"], None, self._consts["um"], 0.7, 0.3, True)
+        um, _ = self._unmatched_class_targets()
+        tg = ops.assign_targets(anchors, gt["boxes_abs"], gt["num"], None, um, 0.7, 0.3, True)
         cls_t = tg["cls_targets"].view(B, n)
         sampled = ops.balanced_sample(tg["cls_weights"], cls_t, int(c.first_stage_minibatch_size),
                                       c.first_stage_positive_balance_fraction, self.seed,
-                                      (2 * int(image_index) * 65536) & 0xFFFFFFFF, 2)
-        loc_s, obj_s = ops.rpn_loss_scales(sampled, tg["reg_weights"], c.first_stage_localization_loss_weight / B,
+                                      (2 * draw * 65536) & 0xFFFFFFFF, 2)
+        loc_s, obj_s = ops.rpn_loss_scales(sampled, tg["reg_weights"],
+                                           c.first_stage_localization_loss_weight / B,
                                            c.first_stage_objectness_loss_weight / B)
-        rl, _ = ops.smooth_l1(pd["rpn_box_encodings"], tg["reg_targets"], loc_s, 3.0, want_grad=False)
+        rl, d_enc = ops.smooth_l1(pd["rpn_box_encodings"], tg["reg_targets"], loc_s, 3.0, want_grad=want_grad)
         losses["first_stage_localization_loss"] = ops.reduce_sum(rl)
-        rl, _ = ops.softmax_ce(pd["rpn_objectness_predictions_with_background"], ops.onehot2(cls_t), obj_s,
-                               want_grad=False)
+        rl, d_obj = ops.softmax_ce(pd["rpn_objectness_predictions_with_background"], ops.onehot2(cls_t), obj_s,
+                                   want_grad=want_grad)
         losses["first_stage_objectness_loss"] = ops.reduce_sum(rl)
+        if want_grad:
+            d["rpn_box_encodings"], d["rpn_objectness"] = d_enc, d_obj
         pd["_rpn_targets"] = dict(tg, sampled=sampled)
-        if not self._first_stage_only:
-            # ---- _loss_box_classifier :1670-1793 over every padded proposal
-            N2 = self.max_num_proposals
-            dt = ops.assign_targets(pd["proposal_boxes"], gt["boxes_abs"], gt["num"], gt["classes_bg"],
-                                    self._consts["um2"], 0.5, 0.5, False,
-                                    gt_extra=gt["closeness"] if mtl.closeness else None)
-            cls_s, loc_s2, clo_s = ops.detector_loss_scales(
-                dt["cls_weights"], dt["reg_weights"], pd["num_proposals"],
-                dt.get("extra_targets") if mtl.closeness else None,
-                c.second_stage_classification_loss_weight, c.second_stage_localization_loss_weight,
-                mtl.closeness_loss_weight)
-            cls_targets = dt["cls_targets"].view(B * N2, K1)
-            rl, _ = ops.box_select_smooth_l1(pd["refined_box_encodings"], cls_targets,
-                                             dt["reg_targets"].view(B * N2, 4), loc_s2.view(-1), 1.0, want_grad=False)
-            losses["second_stage_localization_loss"] = ops.reduce_sum(rl)
-            rl, _ = ops.softmax_ce(pd["class_predictions_with_background"], cls_targets, cls_s.view(-1),
-                                   want_grad=False)
-            losses["second_stage_classification_loss"] = ops.reduce_sum(rl)
-            pd["_det_targets"] = dt
-            if mtl.closeness:
-                rl, _ = ops.softmax_ce(pd["closeness_predictions"], dt["extra_targets"].view(B * N2, K1),
-                                       clo_s.view(-1), col0=1, want_grad=False)
-                losses["closeness_classification_loss"] = ops.reduce_sum(rl)
-            # ---- _loss_window_class :1839-1858
-            if mtl.window:
-                wc = self._window["classes"].view(-1, K1)
-                if wc.shape[0]:
-                    ws = torch.full((wc.shape[0],), mtl.window_class_loss_weight / wc.shape[0], dtype=f32, device=dev)
-                    rl, _ = ops.softmax_ce(pd["window_class_predictions"], wc, ws, want_grad=False)
-                    losses["window_class_loss"] = ops.reduce_sum(rl)
-                else:
-                    losses["window_class_loss"] = torch.zeros((1,), dtype=f32, device=dev)
-        # ---- _loss_edgemask :1860-1881
-        if mtl.edgemask:
-            em = self._edgemask
-            mh, mw = em.shape[2], em.shape[3]
-            tgt, sc = ops.edgemask_targets(em, mtl.edgemask_loss_weight / (B * mh * mw))
-            pr = ops.resize_bilinear_fwd(pd["edgemask_predictions"], mh, mw)
-            rl, _ = ops.softmax_ce(pr, tgt, sc.view(-1), want_grad=False)
-            losses["edgemask_loss"] = ops.reduce_sum(rl)
-        # ---- _loss_refined_classifier :1795-1837
-        if mtl.refine and not self._first_stage_only:
-            rs = cls_s if c.second_stage_classification_loss_weight == mtl.refined_classification_loss_weight \
-                else ops.detector_loss_scales(dt["cls_weights"], dt["reg_weights"], pd["num_proposals"], None,
-                                              mtl.refined_classification_loss_weight, 0.0, 0.0)[0]
-            rl, _ = ops.softmax_ce(pd["mtl_refined_class_predictions_with_background"], cls_targets, rs.view(-1),
-                                   want_grad=False)
-            losses["refined_classification_loss"] = ops.reduce_sum(rl)
-        return losses
+
+    def _loss_box_classifier(self, pd, losses, d, want_grad):
+        """faster_rcnn_meta_arch.py:1670-1793, the closeness term (:1774-1791) and the hard example miner with it.
+        Returns the classification term's per-proposal scales, which the refined term shares when its weight is the
+        same."""
+        c, mtl = self.cfg, self._mtl
+        B, H, W, _ = pd["image_shape"]
+        gt = self._format_groundtruth_data(H, W)
+        N2, K1 = self.max_num_proposals, self.num_classes + 1
+        _, um2 = self._unmatched_class_targets()
+        dt = ops.assign_targets(pd["proposal_boxes"], gt["boxes_abs"], gt["num"], gt["classes_bg"], um2,
+                                0.5, 0.5, False, gt_extra=gt["closeness"] if mtl.closeness else None)
+        cls_s, loc_s2, clo_s = ops.detector_loss_scales(
+            dt["cls_weights"], dt["reg_weights"], pd["num_proposals"],
+            dt.get("extra_targets") if mtl.closeness else None,
+            c.second_stage_classification_loss_weight, c.second_stage_localization_loss_weight,
+            mtl.closeness_loss_weight)
+        cls_targets = dt["cls_targets"].view(B * N2, K1)
+        rl_loc, d_box = ops.box_select_smooth_l1(pd["refined_box_encodings"], cls_targets,
+                                                 dt["reg_targets"].view(B * N2, 4), loc_s2.view(-1), 1.0,
+                                                 want_grad=want_grad)
+        rl_cls, d_cls = ops.softmax_ce(pd["class_predictions_with_background"], cls_targets, cls_s.view(-1),
+                                       want_grad=want_grad)
+        if self._hard_miner is not None:
+            # :1758-1762 -> _unpad_proposals_and_apply_hard_mining (:1902-1946) over ALL the NMS survivors of the RPN (no
+            # balanced sample when a miner is configured, :475, :1118): greedy NMS over the first num_proposals boxes
+            # scored by their loss, the terms become sums over the mined proposals, the others get no gradient. Mined
+            # per image and summed; the reference's loop `return`s inside its first iteration (:1930), i.e. a clone
+            # with more than one image would silently drop the others' second-stage loss — not reproduced.
+            hm = self._hard_miner
+            lm, cm, sel, nsel = ops.hard_example_mining(rl_loc.view(B, N2), rl_cls.view(B, N2), pd["proposal_boxes"],
+                                                        pd["num_proposals"], d_box, d_cls, hm["num_hard_examples"],
+                                                        hm["iou_threshold"], hm["loss_type"])
+            rl_loc, rl_cls = lm, cm
+            pd["_mined"] = (sel, nsel)
+        losses["second_stage_localization_loss"] = ops.reduce_sum(rl_loc)
+        losses["second_stage_classification_loss"] = ops.reduce_sum(rl_cls)
+        if want_grad:
+            d["refined_box_encodings"], d["class_predictions"] = d_box, d_cls
+        pd["_det_targets"] = dt
+        if mtl.closeness:
+            rl, d_clo = ops.softmax_ce(pd["closeness_predictions"], dt["extra_targets"].view(B * N2, K1),
+                                       clo_s.view(-1), col0=1, want_grad=want_grad)
+            losses["closeness_classification_loss"] = ops.reduce_sum(rl)
+            if want_grad:
+                d["closeness_predictions"] = d_clo
+        return cls_s
+
+    def _loss_refined_classifier(self, pd, cls_s, losses, d, want_grad):
+        """faster_rcnn_meta_arch.py:1795-1837, on the targets _loss_box_classifier left in pd['_det_targets']."""
+        c, mtl = self.cfg, self._mtl
+        if not mtl.refine:
+            return
+        dt = pd["_det_targets"]
+        rs = cls_s if c.second_stage_classification_loss_weight == mtl.refined_classification_loss_weight \
+            else ops.detector_loss_scales(dt["cls_weights"], dt["reg_weights"], pd["num_proposals"], None,
+                                          mtl.refined_classification_loss_weight, 0.0, 0.0)[0]
+        cls_targets = dt["cls_targets"].view(-1, self.num_classes + 1)
+        rl, d_ref = ops.softmax_ce(pd["mtl_refined_class_predictions_with_background"], cls_targets, rs.view(-1),
+                                   want_grad=want_grad)
+        losses["refined_classification_loss"] = ops.reduce_sum(rl)
+        if want_grad:
+            d["refined_class_predictions"] = d_ref
+
+    def _loss_window_class(self, pd, losses, d, want_grad):
+        """faster_rcnn_meta_arch.py:1839-1858."""
+        mtl = self._mtl
+        if not mtl.window:
+            return
+        wc = self._window["classes"].view(-1, self.num_classes + 1)
+        ws = torch.full((wc.shape[0],), mtl.window_class_loss_weight / wc.shape[0], dtype=f32, device=self.ps.device)
+        rl, d_win = ops.softmax_ce(pd["window_class_predictions"], wc, ws, want_grad=want_grad)
+        losses["window_class_loss"] = ops.reduce_sum(rl)
+        if want_grad:
+            d["window_class_predictions"] = d_win
+
+    def _loss_edgemask(self, pd, losses, d, want_grad):
+        """faster_rcnn_meta_arch.py:1860-1881."""
+        mtl = self._mtl
+        if not mtl.edgemask:
+            return
+        B = pd["image_shape"][0]
+        em = self._edgemask
+        mh, mw = em.shape[2], em.shape[3]
+        tgt, sc = ops.edgemask_targets(em, mtl.edgemask_loss_weight / (B * mh * mw))
+        pr = ops.resize_bilinear_fwd(pd["edgemask_predictions"], mh, mw)
+        rl, d_pr = ops.softmax_ce(pr, tgt, sc.view(-1), want_grad=want_grad)
+        losses["edgemask_loss"] = ops.reduce_sum(rl)
+        if want_grad:
+            d["edgemask_resized"] = d_pr
 
     # ------------------------------------------------------------------ backward
+    def _backward_refiner(self, pd, d):
+        """The refiner's filter gradients; through the residual its output gradient also reaches the class logits."""
+        mtl = self._mtl
+        d_ref = d["refined_class_predictions"]
+        self.refine_fc.wgrad(pd["_refine_hidden"], d_ref)    # refiner input is stop_gradient (:834)
+        if self.refine_stack is not None:
+            g_h = self.refine_fc.dgrad(pd["_refine_hidden"].shape, d_ref)
+            self.refine_stack.backward(pd["_refine_ctx"], g_h, need_input_grad=False)
+        if mtl.refine_residue and not mtl.stop_gradient_for_prediction_org:
+            ops.axpby(d_ref, d["class_predictions"], 1.0, 1.0)
+
     def backward(self, pd):
         """Accumulates dLoss/dW into the flat gradient buffer (ParamStore.grads)."""
         mtl = self._mtl
@@ -981,16 +963,9 @@ class FasterRCNNMetaArch:
             dF = torch.zeros_like(F)
             return self._backward_first_stage(pd, d, F, dF, B)
         dF = torch.empty_like(F)         # first written IN FULL by the main head's RoI-crop backward below (no memset)
-        d_cls = d["class_predictions"]
-        # refine: gradient reaches the refiner weights and, through the residual, the class logits
         if mtl.refine:
-            d_ref = d["refined_class_predictions"]
-            self.refine_fc.wgrad(pd["_refine_hidden"], d_ref)    # refiner input is stop_gradient (:834)
-            if self.refine_stack is not None:
-                g_h = self.refine_fc.dgrad(pd["_refine_hidden"].shape, d_ref)
-                self.refine_stack.backward(pd["_refine_ctx"], g_h, need_input_grad=False)
-            if mtl.refine_residue and not mtl.stop_gradient_for_prediction_org:
-                ops.axpby(d_ref, d_cls, 1.0, 1.0)
+            self._backward_refiner(pd, d)
+        d_cls = d["class_predictions"]
         c = self.cfg
         # main head -> tower -> crops -> dF
         feat = pd["_feat"]

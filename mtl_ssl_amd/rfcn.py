@@ -99,21 +99,13 @@ class RFCNMetaArch(FasterRCNNMetaArch):
     # ------------------------------------------------------------------ forward
     def _predict_second_stage(self, pd):
         """rfcn_meta_arch.py:208-310."""
-        c, mtl = self.cfg, self._mtl
-        B, H, W, _ = pd["image_shape"]
+        mtl = self._mtl
         F = pd["rpn_features_to_crop"]
-        gt = self._format_groundtruth_data(H, W) if self._is_training else None
-        N2 = self.max_num_proposals
+        B, N2 = F.shape[0], self.max_num_proposals
         # block4 runs on the WHOLE map here: the main tower and its score maps do not depend on the proposals, only the
         # position-sensitive pooling does. The decode -> NMS -> sampling chain nevertheless stays on this stream: the
         # window tower's forward on the aux stream already fills the chip under it (DESIGN.md §3.4, retired switches)
-        props, _scores, nprop = ops.rpn_proposals(
-            pd["rpn_box_encodings"], pd["rpn_objectness_predictions_with_background"], pd["anchors"],
-            H, W, c.first_stage_nms_score_threshold, c.first_stage_nms_iou_threshold,
-            int(c.first_stage_max_proposals))
-        boxes_abs, boxes_norm, num = self._second_stage_proposals(props, nprop, gt, H, W)
-        flat = boxes_norm.view(B * N2, 4)
-        box_ind = self._box_ind(B, N2, F.device)
+        boxes_abs, boxes_norm, num, flat, box_ind = self._proposals_to_crop(pd)
         cside = None
         if (mtl.closeness and self._is_training and not self._shared_classifier
                 and os.environ.get("MTLSSL_CLOSENESS_FWD_SIDE", "0") == "1"):
@@ -167,34 +159,15 @@ class RFCNMetaArch(FasterRCNNMetaArch):
         pd.update({"window_class_predictions": wp["class"], "_wp": wp})
         return pd
 
-    def predict_with_mtl_results(self, pd):
-        """faster_rcnn_meta_arch.py:764-846 with the R-FCN window head, per image."""
-        mtl = self._mtl
-        F = pd["rpn_features_to_crop"]
-        B = F.shape[0]
-        N2 = self.max_num_proposals
-        K1 = self.num_classes + 1
-        cls = pd["class_predictions_with_background"]
-        win = None
-        if mtl.window:
-            ew = ops.expand_windows(pd["proposal_boxes_normalized"], self.N_EXPAND)
-            flat = ew.view(B * self.N_EXPAND * N2, 4)
-            box_ind = self._box_ind(B, self.N_EXPAND * N2, F.device)
-            feat = self._window_features(pd, self._is_training)
-            win = self.window_predictor.predict(feat, flat, box_ind)["class"]
-            pd["expand_window_class_predictions"] = win.view(B, self.N_EXPAND, N2, K1)
-        clo = pd["closeness_predictions"] if mtl.closeness else None
-        net = ops.refine_concat(cls, win, clo, B, N2, self.N_EXPAND, bool(mtl.global_closeness))
-        hidden, sctx = net, None
-        if self.refine_stack is not None:          # faster_rcnn_meta_arch.py:833-840: FC stack + dropout before the refiner
-            hidden, sctx = self.refine_stack.forward(net, self._is_training, self.seed, self.step)
-        refined = self.refine_fc.forward(hidden)
-        pd["_refine_hidden"], pd["_refine_ctx"] = hidden, sctx
-        if mtl.refine_residue:
-            ops.axpby(cls, refined, 1.0, 1.0)
-        pd["mtl_refined_class_predictions_with_background"] = refined
-        pd["_refine_in"] = net
-        return pd
+    def _expand_window_class_predictions(self, pd):
+        """The refiner's windows (faster_rcnn_meta_arch.py:774-812) through the R-FCN window head: pooled from the
+        whole-map window tower's score maps, no crops."""
+        B, N2 = pd["rpn_features_to_crop"].shape[0], self.max_num_proposals
+        ew = ops.expand_windows(pd["proposal_boxes_normalized"], self.N_EXPAND)
+        flat = ew.view(B * self.N_EXPAND * N2, 4)
+        box_ind = self._box_ind(B, self.N_EXPAND * N2, ew.device)
+        feat = self._window_features(pd, self._is_training)
+        return self.window_predictor.predict(feat, flat, box_ind)["class"]
 
     # ------------------------------------------------------------------ backward
     def backward(self, pd):
@@ -205,15 +178,9 @@ class RFCNMetaArch(FasterRCNNMetaArch):
         dF = torch.zeros_like(F)
         if self._first_stage_only:             # faster_rcnn_meta_arch.py:603: the RPN (+ edge-mask head) is the model
             return self._backward_first_stage(pd, d, F, dF, B)
-        d_cls = d["class_predictions"]
         if mtl.refine:
-            d_ref = d["refined_class_predictions"]
-            self.refine_fc.wgrad(pd["_refine_hidden"], d_ref)
-            if self.refine_stack is not None:
-                g_h = self.refine_fc.dgrad(pd["_refine_hidden"].shape, d_ref)
-                self.refine_stack.backward(pd["_refine_ctx"], g_h, need_input_grad=False)
-            if mtl.refine_residue and not mtl.stop_gradient_for_prediction_org:
-                ops.axpby(d_ref, d_cls, 1.0, 1.0)
+            self._backward_refiner(pd, d)
+        d_cls = d["class_predictions"]
         stop = bool(mtl.stop_gradient_for_aux_tasks)
         held = []          # the aux towers' input gradients (only without stop_gradient_for_aux_tasks)
 

@@ -111,3 +111,38 @@ def test_forward_overlap_switches_do_not_change_a_bit(cfg_name, monkeypatch):
         del tr, model
     assert res["0"][0] == res["1"][0]
     assert torch.equal(res["0"][1], res["1"][1])
+
+
+@pytest.mark.parametrize("cfg_name,refined_weight", [("smoke_resnet50_mtl.config", None),
+                                                     ("smoke_rfcn_resnet50_mtl.config", None),
+                                                     ("smoke_resnet50_mtl.config", 0.5)])
+def test_split_loss_equals_whole_loss_bit_for_bit(cfg_name, refined_weight, monkeypatch):
+    """MTLSSL_SPLIT_LOSS=1 (loss(part="early") on the side stream, the refiner, then loss(part="late")) against
+    MTLSSL_SPLIT_LOSS=0 (the refiner, then loss(part="all")): the same terms, the same loss_scale on every gradient,
+    so the losses and gradients of a step are bit-identical. With refined_classification_loss_weight 0.5 the refined
+    term no longer shares the classification term's scales and computes its own."""
+    import __graft_entry__ as g
+    g.build()
+    from mtl_ssl_amd import config, model_builder, synthetic, trainer
+    text = open(os.path.join(ROOT, "configs", cfg_name)).read()
+    if refined_weight is not None:
+        assert "refined_classification_loss_weight: 1.0" in text
+        text = text.replace("refined_classification_loss_weight: 1.0",
+                            "refined_classification_loss_weight: %s" % refined_weight)
+    cfg = config.parse_pipeline_config(text)
+    K = int(cfg.model.faster_rcnn.num_classes)
+    res = {}
+    for mode in ("1", "0"):
+        monkeypatch.setenv("MTLSSL_SPLIT_LOSS", mode)
+        model = model_builder.build(cfg.model, True, "cuda", seed=5)
+        tr = trainer.Trainer(model, cfg.train_config, 1)
+        assert tr.split_loss == (mode == "1")
+        batch = tr.stage_batch(synthetic.make_batch(2, 160, 224, K, seed=21, device="cuda", max_gt=4, num_windows=6))
+        tr.forward_backward(batch)
+        losses = {k: float(v.item()) for k, v in tr.forward_backward(batch).items()}
+        torch.cuda.synchronize()
+        assert "refined_classification_loss" in losses
+        res[mode] = (losses, model.ps.grads.clone())
+        del tr, model
+    assert res["1"][0] == res["0"][0]
+    assert torch.equal(res["1"][1], res["0"][1])
