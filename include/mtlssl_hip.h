@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 18
+#define MTLSSL_ABI_VERSION 19
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -431,6 +431,28 @@ int mtlssl_coco_match(const int32_t* dt_off, const int32_t* gt_off, int num_segm
                       const double* dt_boxes, const double* gt_boxes, const double* gt_area, const uint8_t* gt_crowd,
                       const double* iou_thrs, int num_iou_thrs, const double* area_rng, int num_area_rng,
                       uint64_t* dt_match, uint64_t* dt_ignore, int32_t* npig, mtlssl_stream_t stream);
+/* The PASCAL evaluator's tp/fp labelling for every groundtruth subset at once (utils/per_image_evaluation.py:233-281,
+ * which utils/object_detection_evaluation.py:199-211 runs once per subset with groundtruth_is_difficult = ~member;
+ * restated by PascalDetectionEvaluator._tp_fp in mtl_ssl_amd/evaluation.py, which defines the semantics). A segment is
+ * one (image, class) pair that holds a detection: detections [dt_off[s], dt_off[s+1]) of dt_boxes [ND,4] and
+ * groundtruth [gt_off[s], gt_off[s+1]) of gt_boxes [NG,4] / gt_member [NG] (offsets int32[num_segments+1]; boxes
+ * ymin,xmin,ymax,xmax, double; bit j of gt_member = the box belongs to subset j; everything in device memory). The
+ * caller has filtered, sorted and capped each segment's detections exactly as _tp_fp does. One wavefront per segment:
+ * per detection the IoUs against every groundtruth box in utils/np_box_ops.py's double arithmetic (np.maximum /
+ * np.minimum with NaN propagation, inter / ((area_a + area_b) - inter), no floor: 0/0 is NaN), np.argmax's box g (the
+ * first NaN if there is one, otherwise the first maximum), then lane j < num_subsets with its own claimed set: IoU >=
+ * iou_threshold and g outside subset j -> bit j of drop[i] (the detection is removed from subset j); IoU >= threshold,
+ * g a member and unclaimed -> bit j of tp[i], g claimed; otherwise a false positive (no bit). hit[i] = 1 when the best
+ * IoU >= threshold whatever the membership (CorLoc reads it), else 0. Every element of tp / drop / hit [ND] is written.
+ * max_gt = the largest groundtruth count of a segment (host int), at most MTLSSL_PASCAL_MATCH_MAX_GT, and num_subsets at
+ * most 64; beyond either MTLSSL_EINVAL (the evaluator keeps such work on the host). A segment that breaks the bound
+ * all the same gets hit = MTLSSL_PASCAL_MATCH_LEFT_OUT. Plain stores, no atomics: the same bits run to run. */
+#define MTLSSL_PASCAL_MATCH_MAX_GT 256
+#define MTLSSL_PASCAL_MATCH_LEFT_OUT 2
+int mtlssl_pascal_match(const int32_t* dt_off, const int32_t* gt_off, int num_segments, int max_gt,
+                        const double* dt_boxes, const double* gt_boxes, const uint64_t* gt_member,
+                        double iou_threshold, int num_subsets, uint64_t* tp, uint64_t* drop, uint8_t* hit,
+                        mtlssl_stream_t stream);
 
 /* Auxiliary-task labels from the groundtruth alone (Trainer(aux_labels="generate")): what the reference computes once,
  * offline, when it writes a record (create_records/create_pascal_tf_record.py:120-421), made per step on the device

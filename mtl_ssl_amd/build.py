@@ -25,6 +25,7 @@ SOURCES = {
     "depthwise.hip": [], "pool_concat.hip": [], "winograd.hip": [],
     "eval_metrics.hip": ["-ffp-contract=off"],   # evaluator NMS / edge-mask metric: numpy's double arithmetic
     "coco_eval.hip": ["-ffp-contract=off"],      # COCO match: the host evaluator's double IoU arithmetic
+    "pascal_eval.hip": ["-ffp-contract=off"],    # PASCAL subset labelling: the host evaluator's double IoU arithmetic
     "aux_labels.hip": ["-ffp-contract=off"],     # labels from boxes: the host definitions' double arithmetic
     "summaries.hip": ["-ffp-contract=off"],      # variable histograms: the bucket rule and moments are double arithmetic
     "visualize.hip": [],               # box overlay of the evaluator's visualisations (integer work only)

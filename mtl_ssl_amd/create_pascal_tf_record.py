@@ -8,7 +8,9 @@ names data_decoders/tf_example_decoder.py:34-124 reads.
         --output_path=voc07_trainval.record [--label_map_path=pascal_label_map.pbtxt]
 
 No TensorFlow, lxml or protoc: xml.etree for the annotations, this package's tf.Example codec and TFRecord framing
-for the output. `--seed` fixes the random windows (the reference draws them from Python's global `random`)."""
+for the output. `--seed` fixes the random windows (the reference draws them from Python's global `random`).
+`--subsets=NAME:LO:HI[,NAME:LO:HI...]` tags every box with the named area ranges that hold it (image/object/subset, the
+reference's :67-69, 444-457, 487, whose table is `--subsets=all:0:inf`); eval then reports one mAP per subset."""
 import argparse
 import hashlib
 import io
@@ -66,6 +68,34 @@ def parse_annotation(path):
                 height=int(txt(size, "height", "0")) if size is not None else 0, objects=objs)
 
 
+def parse_subsets(text):
+    """--subsets: 'NAME:LO:HI[,NAME:LO:HI...]' -> [(name, lo, hi)] in the flag's order; 'inf' is a bound. A malformed
+    entry, an empty name, a name holding '|' (the record's separator) or LO > HI is a ValueError naming the entry."""
+    out = []
+    for entry in str(text).split(","):
+        parts = entry.split(":")
+        if len(parts) != 3:
+            raise ValueError("--subsets entry %r: NAME:LO:HI expected" % entry)
+        name = parts[0].strip()
+        if not name or "|" in name:
+            raise ValueError("--subsets entry %r: the name must be non-empty and hold no '|'" % entry)
+        try:
+            lo, hi = float(parts[1]), float(parts[2])
+        except ValueError:
+            raise ValueError("--subsets entry %r: LO and HI must be numbers (or inf)" % entry)
+        if not lo <= hi:
+            raise ValueError("--subsets entry %r: LO > HI" % entry)
+        out.append((name, lo, hi))
+    return out
+
+
+def box_subsets(obj, subsets):
+    """image/object/subset of one object (create_pascal_tf_record.py:444-457): the names whose range holds the box's
+    area in the annotation's pixels, LO <= area < HI, joined with '|' in the table's order; '' = no subset."""
+    area = (obj["ymax"] - obj["ymin"]) * (obj["xmax"] - obj["xmin"])
+    return "|".join(name for name, lo, hi in subsets if lo <= area < hi).encode("utf-8")
+
+
 def aux_label_features(boxes, classes, W, H, num_classes, rng, random_windows=True, num_windows=64, keep=None):
     """The recycled-annotation fields of a record from absolute [ymin, xmin, ymax, xmax] boxes and 1-based classes:
     window boxes + soft labels, per-object closeness (rows `keep`), the 2 x 64 x 64 foreground mask."""
@@ -88,9 +118,10 @@ def aux_label_features(boxes, classes, W, H, num_classes, rng, random_windows=Tr
 
 
 def example_from_annotation(ann, image_bytes, label_map, num_classes, rng, ignore_difficult=False, random_windows=True,
-                            num_windows=64):
+                            num_windows=64, subsets=None):
     """-> serialized tf.Example (create_pascal_tf_record.py:66-497: boxes normalised by the image size, 1-based class
-    ids, difficult / truncated / pose, the window, closeness and edge-mask labels)."""
+    ids, difficult / truncated / pose, the window, closeness and edge-mask labels; with `subsets` (parse_subsets) also
+    image/object/subset)."""
     from PIL import Image
     from . import input_reader
     image = Image.open(io.BytesIO(image_bytes))
@@ -117,12 +148,13 @@ def example_from_annotation(ann, image_bytes, label_map, num_classes, rng, ignor
         "image/object/difficult": np.array([o["difficult"] for o in objs], np.int64),
         "image/object/truncated": np.array([o["truncated"] for o in objs], np.int64),
         "image/object/view": [o["pose"].encode("utf-8") for o in objs],
+        **({} if subsets is None else {"image/object/subset": [box_subsets(o, subsets) for o in objs]}),
         **aux,
     })
 
 
 def convert(data_dir, year, image_set, output_path, label_map=None, annotations_dir="Annotations", exclude=(),
-            ignore_difficult=False, random_windows=True, seed=0, log_every=100):
+            ignore_difficult=False, random_windows=True, seed=0, log_every=100, subsets=None):
     """Walks <data_dir>/<year>/ImageSets/Main/aeroplane_<set>.txt like the reference (:531-538) and writes one record
     per listed image. Returns the number of records."""
     from . import input_reader, labels
@@ -144,7 +176,8 @@ def convert(data_dir, year, image_set, output_path, label_map=None, annotations_
                 ann = parse_annotation(os.path.join(data_dir, y, annotations_dir, ex + ".xml"))
                 folder = ann["folder"] or y
                 img = open(os.path.join(data_dir, folder, "JPEGImages", ann["filename"] or ex + ".jpg"), "rb").read()
-                records.append(example_from_annotation(ann, img, label_map, K, rng, ignore_difficult, random_windows))
+                records.append(example_from_annotation(ann, img, label_map, K, rng, ignore_difficult, random_windows,
+                                                       subsets=subsets))
     input_reader.write_tfrecord(output_path, records)
     return len(records)
 
@@ -161,11 +194,18 @@ def main(argv=None):
     ap.add_argument("--ignore_difficult_instances", default="false")
     ap.add_argument("--random_multi_object", default="true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--subsets", default="",
+                    help="NAME:LO:HI[,NAME:LO:HI...]: tag each box with the names whose LO <= pixel area < HI "
+                         "(image/object/subset); inf is a bound; all:0:inf is the reference's table")
     f = ap.parse_args(sys.argv[1:] if argv is None else argv)
     truth = lambda s: str(s).lower() in ("1", "true", "yes")
+    try:
+        subsets = parse_subsets(f.subsets) if f.subsets else None
+    except ValueError as e:
+        ap.error(str(e))
     n = convert(f.data_dir, f.year, f.set, f.output_path, read_label_map(f.label_map_path) if f.label_map_path else None,
                 f.annotations_dir, [e.strip() for e in f.exclude.split(",") if e.strip()],
-                truth(f.ignore_difficult_instances), truth(f.random_multi_object), f.seed)
+                truth(f.ignore_difficult_instances), truth(f.random_multi_object), f.seed, subsets=subsets)
     print("wrote %d records to %s" % (n, f.output_path))
     return n
 

@@ -9,6 +9,9 @@ soft_nms_sigma re-suppress each class's detections on the device before the eval
 With 'coco_metrics' the evaluator's greedy match runs on the device (ops.coco_match), and eval_config.coco_eval_options
 adds the COCO_Eval/<class>/<metric> keys it selects and may name an annotation file as the groundtruth
 (eval_util.py:489-549).
+Records that carry image/object/subset (create_pascal_tf_record --subsets) add one PASCAL result per groundtruth subset,
+'Subset <name> mAP@<thr>IOU[/<category>]', labelled on the device (ops.pascal_match), and with --eval_dir the
+pr_curve_<subset>_<nms>.txt files (eval_util.py:186-203, 300-380).
 eval_config.calc_loss adds the model's losses (Loss/<name>, FasterRCNNMetaArch.eval_loss on the device);
 submission_format_output writes the test servers' files instead of metrics; a metrics run with --eval_dir keeps the
 best state under <eval_dir>/best/ (main_subset); --run_once=false evaluates every new state of --checkpoint_dir
@@ -99,6 +102,19 @@ def coco_eval_keys(res, options, class_names):
             for name, row in rows for i in options["metric_index"]}
 
 
+def pascal_subset_keys(res, iou_threshold, class_names):
+    """eval_util.py:372-380: {'Subset <name> mAP@<thr>IOU': mAP, '.../<category>': AP} from
+    PascalSubsetEvaluator.evaluate(), the name padded to ten columns as the reference formats it; a category that
+    class_names (coco_class_names) does not hold has no key. The mAP keys come first, subsets in sorted order."""
+    head = {name: "Subset {:10} mAP@{}IOU".format(name, iou_threshold) for name in res["subset_names"]}
+    out = {head[name]: float(res["mean_ap"][name]) for name in res["subset_names"]}
+    for name in res["subset_names"]:
+        for k, v in enumerate(res["ap_per_class"][name]):
+            if k + 1 in class_names:
+                out["%s/%s" % (head[name], class_names[k + 1])] = float(v)
+    return out
+
+
 class CocoAnnotations:
     """Groundtruth of the COCO evaluator from an instances JSON (coco_eval_options.eval_ann_filename), which holds what
     the records do not: crowd flags and segmentation areas. Only the images that are evaluated count (the reference
@@ -184,6 +200,18 @@ def _raw_records(paths):
             sid = (f.get("image/source_id") or [b""])[0].decode("utf-8")
             name = (f.get("image/filename") or [b""])[0].decode("utf-8")
             yield sid, name, f.get("image/encoded", [b""])[0]
+
+
+def _record_subsets(paths):
+    """(source id, groundtruth_subset of the record or None when it lacks image/object/subset) of every record, in the
+    order the input pipeline delivers them (shuffle off, one image per batch). The field is evaluation-only: no batch
+    of the input pipeline carries it, so eval reads it beside the stream, as it reads the original images."""
+    from . import input_reader
+    for p in paths:
+        for rec in input_reader.read_tfrecord(p):
+            f = input_reader.parse_example(rec)
+            sid = (f.get("image/source_id") or [b""])[0].decode("utf-8")
+            yield sid, input_reader.groundtruth_subset(f)
 
 
 def _download(post, losses):
@@ -275,6 +303,11 @@ def main(argv=None):
         # evaluator.py:318-322: iou_threshold is PASCAL's matching threshold; COCO keeps its .50:.05:.95
         # the COCO evaluator matches on the device (ops.coco_match): the same numbers as its host loops, bit for bit
         ev = evaluation.CocoDetectionEvaluator(K, device=dev) if coco else evaluation.PascalDetectionEvaluator(K, iou_thr)
+        # eval_util.py:300-380: beside it, one PASCAL result per groundtruth subset of the records' image/object/subset,
+        # labelled on the device (ops.pascal_match); the legacy keys above stay the host evaluator's
+        sub_ev = None if (coco or submission) else evaluation.PascalSubsetEvaluator(K, iou_thr, device=dev)
+        subsets = _record_subsets(record_paths(reader)) if sub_ev is not None else None
+        any_subsets = False
         mm = mtl_metrics.MtlMetrics()
         missing = {}
         em_counts = []
@@ -396,20 +429,31 @@ def main(argv=None):
                     ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls)
                 else:     # evaluator.py:196-201 -> eval_util.py:332-334: PASCAL's difficult boxes are ignored, not missed
                     diff = b.get("groundtruth_difficult")
-                    ev.add_single_ground_truth_image_info(
-                        n_img, gt_boxes, gt_cls, is_difficult=None if diff is None else np.asarray(diff[0], bool))
+                    diff = None if diff is None else np.asarray(diff[0], bool)
+                    ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls, is_difficult=diff)
+                    sid, names = next(subsets)
+                    if b.get("source_id") is not None and b["source_id"][0] != sid:
+                        raise RuntimeError("record %d: the input pipeline delivered %r, the record file holds %r"
+                                           % (n_img, b["source_id"][0], sid))
+                    any_subsets |= names is not None
+                    sub_ev.add_single_ground_truth_image_info(n_img, gt_boxes, gt_cls, is_difficult=diff, subsets=names)
             if eval_nms is None:
-                ev.add_single_detected_image_info(image_key, np.asarray(d["detection_boxes"][0][:n], np.float64) * scale,
-                                                  d["detection_scores"][0][:n], d["detection_classes"][0][:n])
+                dets = (np.asarray(d["detection_boxes"][0][:n], np.float64) * scale, d["detection_scores"][0][:n],
+                        d["detection_classes"][0][:n])
             else:
-                ev.add_single_detected_image_info(image_key, *suppress_per_class(
+                dets = suppress_per_class(
                     d["detection_boxes"][0][:n], d["detection_scores"][0][:n], d["detection_classes"][0][:n], scale, K,
-                    nms_type, nms_thr, sigma, eval_nms, dev))
+                    nms_type, nms_thr, sigma, eval_nms, dev)
+            ev.add_single_detected_image_info(image_key, *dets)
+            if sub_ev is not None:
+                sub_ev.add_single_detected_image_info(image_key, *dets)
             n_img += 1
         if hasattr(stream, "close"):
             stream.close()
         if raw is not None:
             raw.close()
+        if subsets is not None:
+            subsets.close()
         if submission:
             # eval_util.py:783-786, 838-841: no metrics, only the files of the test servers
             paths = eval_workflow.save_detection_results_for_submission(results, cats, f.eval_dir, metrics_set)
@@ -429,6 +473,10 @@ def main(argv=None):
                 out[k] = _plain(v)
         if coco_opts is not None:
             out.update(coco_eval_keys(res, coco_opts, coco_names))
+        sres = None
+        if any_subsets:
+            sres = sub_ev.evaluate()
+            out.update(pascal_subset_keys(sres, iou_thr, coco_class_names(K, str(reader.get("label_map_path", "") or ""))))
         mres = mm.evaluate()
         if closeness_error is not None:
             mres.pop("mtl/closeness_diff", None)
@@ -445,6 +493,8 @@ def main(argv=None):
             with open(os.path.join(f.eval_dir, "metrics-%d.json" % step), "w") as fh_out:
                 json.dump(out, fh_out)
             eval_workflow.write_eval_summaries(f.eval_dir, out, images, step)
+            if sres is not None:        # eval_util.py:186-203: the macro-averaged PR curve of every subset, as text
+                evaluation.write_pr_curves(f.eval_dir, sres["precisions"], sres["recalls"], nms_type, nms_thr, sigma)
             # eval_util.py:869-870, 934-997
             eval_workflow.save_best_ckpt(out, fh.name, step, f.eval_dir, metrics_set, str(ec.get("main_subset", "") or ""),
                                          source=fh)

@@ -103,9 +103,10 @@ COCO_AP_KEY = "AP"                     # this build's name of COCO_Eval/All/AP
 
 def main_metric(metrics, metrics_set, main_subset=""):
     """eval_util.py:940-961: (key, value) of the metric that decides the best checkpoint. PASCAL: the first key without
-    '/' that holds main_subset; with an empty main_subset the 'Subset all' value, which is this build's only mAP
-    (mean_ap — there are no subsets here). COCO: COCO_Eval/All/AP, here 'AP'. A main_subset that matches no scalar key
-    is an error (the reference stops on its assert)."""
+    '/' that holds main_subset — a 'Subset <name> mAP@<thr>IOU' key when the records carry groundtruth subsets; with
+    an empty main_subset mean_ap, the mAP over every box that is not difficult (the reference's 'Subset all'). COCO:
+    COCO_Eval/All/AP, here 'AP'. A main_subset that matches no scalar key is an error (the reference stops on its
+    assert)."""
     if "coco" in metrics_set:
         if COCO_AP_KEY not in metrics:
             raise ValueError("coco metrics without %r: %s" % (COCO_AP_KEY, sorted(metrics)))

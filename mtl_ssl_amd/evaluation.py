@@ -170,6 +170,342 @@ def evaluate_detections(detections, groundtruth, num_classes, image_hw=None, mat
     return ev.evaluate()
 
 
+# ------------------------------------------------------------------------------ PASCAL groundtruth subsets
+class PascalSubsetEvaluator:
+    """ObjectDetectionEvaluation(subset_names=...) (utils/object_detection_evaluation.py:52-276, fed by
+    eval_util.py:300-380): every groundtruth box carries a '|'-joined string of subset names and each subset gets its
+    own PASCAL result — by definition what PascalDetectionEvaluator gives for the same images with is_difficult =
+    ~member(subset). A box flagged difficult belongs to no subset (eval_util.py:343-350). CorLoc does not depend on the
+    subset. The add_* methods only store; evaluate() does the work, in the order the detections were added.
+
+    The subset only decides what a detection's best-IoU box means, not which box that is, so with a CUDA `device` the
+    labelling of all subsets of all (image, class) pairs runs there in one launch (ops.pascal_match, pinned bit for bit
+    against _tp_fp); device=None loops _tp_fp per subset. The accumulation after it is PascalDetectionEvaluator's own
+    evaluate() on both paths.
+
+    Unlike the reference, an image whose `subsets` disagree in length with its boxes, or that has none while other
+    images have them, is an error naming the image (the reference falls back to a subset 'default' and then raises
+    unless some box names it), and strings that are all empty give no subsets and a warning (the reference invents
+    an empty 'default' whose mAP is NaN)."""
+    MAX_DEVICE_SUBSETS = 64              # ops.PASCAL_MATCH_MAX_SUBSETS: one lane per subset; more stay on the host
+
+    def __init__(self, num_classes, matching_iou_threshold=0.5, max_detections_per_class=10000, device=None):
+        self._pascal = PascalDetectionEvaluator(num_classes, matching_iou_threshold, max_detections_per_class)
+        self.K, self.thr, self.cap = self._pascal.K, self._pascal.thr, self._pascal.cap
+        if device is not None:
+            import torch
+            device = torch.device(device)
+            if device.type != "cuda":
+                raise ValueError("PascalSubsetEvaluator: device %s is no CUDA device (None = the host path)" % device)
+        self.device = device
+        self.timings = {}
+        self.clear()
+
+    def clear(self):
+        self.gt, self.dt = {}, {}
+
+    def add_single_ground_truth_image_info(self, image_key, boxes, class_labels, is_difficult=None, subsets=None):
+        if image_key in self.gt:
+            return
+        boxes = np.asarray(boxes, float).reshape(-1, 4)
+        cls = np.asarray(class_labels, int).reshape(-1)
+        diff = np.zeros(len(cls), bool) if is_difficult is None else np.asarray(is_difficult, bool).reshape(-1)
+        if subsets is not None:
+            subsets = [s.decode("utf-8") if isinstance(s, bytes) else str(s) for s in subsets]
+            if len(subsets) != len(boxes):
+                raise ValueError("image %r: %d subset strings for %d groundtruth boxes" % (image_key, len(subsets), len(boxes)))
+        self.gt[image_key] = (boxes, cls, diff, subsets)
+
+    def add_single_detected_image_info(self, image_key, boxes, scores, class_labels):
+        boxes = np.asarray(boxes, float).reshape(-1, 4)
+        scores = np.asarray(scores, float).reshape(-1)
+        cls = np.asarray(class_labels, int).reshape(-1)
+        if not (len(boxes) == len(scores) == len(cls)):
+            raise ValueError("one image's detections disagree in length: %d boxes, %d scores, %d class labels"
+                             % (len(boxes), len(scores), len(cls)))
+        if image_key in self.dt:
+            return
+        valid = (boxes[:, 0] < boxes[:, 2]) & (boxes[:, 1] < boxes[:, 3])       # _remove_invalid_boxes
+        self.dt[image_key] = (boxes[valid], scores[valid], cls[valid])
+
+    def subset_names(self):
+        """The union of the stored images' subset names, '' dropped, sorted. Raises when images with and without
+        subset strings are mixed."""
+        have = [k for k, g in self.gt.items() if g[3] is not None]
+        if have and len(have) != len(self.gt):
+            lacking = next(k for k, g in self.gt.items() if g[3] is None)
+            raise ValueError("image %r has no groundtruth subsets, image %r has them: all images or none" % (lacking, have[0]))
+        return sorted({n for k in have for s in self.gt[k][3] for n in s.split("|")} - {""})
+
+    def _members(self, names):
+        """{image key: bool [G, S]}: box g belongs to subset s; a difficult box belongs to none."""
+        col = {n: j for j, n in enumerate(names)}
+        out = {}
+        for key, (boxes, cls, diff, subsets) in self.gt.items():
+            m = np.zeros((len(boxes), len(names)), bool)
+            for g, s in enumerate(subsets or ()):
+                for n in s.split("|"):
+                    if n:
+                        m[g, col[n]] = True
+            m[diff] = False
+            out[key] = m
+        return out
+
+    def _segments(self, members):
+        """(image key, class, detections of the class, their scores, the class's groundtruth boxes, their membership
+        [G, S]) for every image with detections, in the order they were added, and every class."""
+        S = next(iter(members.values())).shape[1] if members else 0
+        none = (np.zeros((0, 4)), np.zeros(0, int))
+        for key, (boxes, scores, cls) in self.dt.items():
+            gb, gc = self.gt[key][:2] if key in self.gt else none
+            mem = members.get(key, np.zeros((0, S), bool))
+            for c in range(self.K):
+                yield key, c, boxes[cls == c], scores[cls == c], gb[gc == c], mem[gc == c]
+
+    def _labels_host(self, members, S):
+        """scores / labels [S][K] lists of per-image arrays and the CorLoc hits [K], through _tp_fp once per subset."""
+        scores = [[[] for _ in range(self.K)] for _ in range(S)]
+        labels = [[[] for _ in range(self.K)] for _ in range(S)]
+        correct = np.zeros(self.K)
+        for key, c, db, ds, gb, mem in self._segments(members):
+            for s in range(S):
+                sc, lab = self._pascal._tp_fp(db, ds, gb, ~mem[:, s])
+                scores[s][c].append(sc)
+                labels[s][c].append(lab)
+            if len(db) and len(gb):
+                top = int(np.argmax(ds))
+                correct[c] += float(iou_matrix(db[top:top + 1], gb).max() >= self.thr)
+        return scores, labels, correct
+
+    def _segment_tables(self, members, S):
+        """What ops.pascal_match reads: every (image, class) pair with a detection, ordered by (class, image) so that a
+        class's detections are one run of the flat arrays. Detections are sorted and capped by _tp_fp's own numpy calls
+        (score ties fall as they fall there); top_pos = where the segment's np.argmax(ds) detection landed (-1: the cap
+        cut it off); membership as one uint64 word per groundtruth box."""
+        per_class = [[] for _ in range(self.K)]
+        for key, c, db, ds, gb, mem in self._segments(members):
+            if len(db):
+                per_class[c].append((key, db, ds, gb, mem))
+        weights = np.uint64(1) << np.arange(S, dtype=np.uint64)
+        seg_key, seg_cat, dbs, dss, gbs, gms, tops, n_dt, n_gt = [], [], [], [], [], [], [], [], []
+        for c, segs in enumerate(per_class):
+            for key, db, ds, gb, mem in segs:
+                order = np.argsort(ds)[::-1][: self.cap]
+                pos = np.flatnonzero(order == int(np.argmax(ds)))
+                seg_key.append(key)
+                seg_cat.append(c)
+                dbs.append(db[order])
+                dss.append(ds[order])
+                gbs.append(gb)
+                gms.append((mem.astype(np.uint64) * weights[None, :]).sum(1, dtype=np.uint64))
+                tops.append(int(pos[0]) if len(pos) else -1)
+                n_dt.append(len(order))
+                n_gt.append(len(gb))
+        cat = lambda parts, shape, dtype: (np.concatenate(parts) if parts else np.zeros(0)).astype(dtype).reshape(shape)
+        return dict(seg_key=seg_key, seg_cat=np.asarray(seg_cat, np.int64), top_pos=np.asarray(tops, np.int64),
+                    dt_off=np.concatenate([[0], np.cumsum(n_dt)]).astype(np.int64),
+                    gt_off=np.concatenate([[0], np.cumsum(n_gt)]).astype(np.int64),
+                    dt_boxes=cat(dbs, (-1, 4), np.float64), dt_scores=cat(dss, (-1,), np.float64),
+                    gt_boxes=cat(gbs, (-1, 4), np.float64), gt_member=cat(gms, (-1,), np.uint64))
+
+    def match_on_device(self, members, S, timings=None):
+        """tp / drop [S, ND] bool and hit [ND] bool of every segment in ONE ops.pascal_match launch and one copy back;
+        a segment with more groundtruth boxes than the kernel holds goes through _tp_fp instead. timings (a dict)
+        receives the seconds of the table build, the kernel and the copy."""
+        import time
+
+        import torch
+        from . import ops
+        t0 = time.perf_counter()
+        tab = self._segment_tables(members, S)
+        ND = len(tab["dt_boxes"])
+        dt_off, gt_off, n_gt = tab["dt_off"], tab["gt_off"], np.diff(tab["gt_off"])
+        large = np.flatnonzero(n_gt > ops.PASCAL_MATCH_MAX_GT)
+        gkeep = np.ones(int(gt_off[-1]), bool)
+        for s in large:                                    # the kernel sees such a segment without groundtruth
+            gkeep[gt_off[s]:gt_off[s + 1]] = False
+        dev_gt_off = np.concatenate([[0], np.cumsum(np.where(n_gt > ops.PASCAL_MATCH_MAX_GT, 0, n_gt))])
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+        args = (up(tab["dt_boxes"]), up(tab["gt_boxes"][gkeep]), up(tab["gt_member"][gkeep].view(np.int64)))
+        if timings is not None:
+            torch.cuda.synchronize(self.device)
+        t1 = time.perf_counter()
+        with torch.cuda.device(self.device):
+            packed = ops.pascal_match(dt_off, dev_gt_off, *args, self.thr, S)[3]
+        if timings is not None:
+            torch.cuda.synchronize(self.device)
+        t2 = time.perf_counter()
+        host = packed.cpu().numpy()
+        t3 = time.perf_counter()
+        raw_hit = host[2 * ND:].view(np.uint8)[:ND]
+        if ND and raw_hit.max() > 1:
+            raise RuntimeError("pascal_match left a detection out (hit %d)" % int(raw_hit.max()))
+        bits = np.arange(S, dtype=np.uint64).reshape(S, 1)
+        one = np.uint64(1)
+        tp = ((host[:ND].view(np.uint64)[None, :] >> bits) & one).astype(bool)
+        drop = ((host[ND:2 * ND].view(np.uint64)[None, :] >> bits) & one).astype(bool)
+        hit = raw_hit.astype(bool)
+        for s in large:
+            d0, d1, g0, g1 = dt_off[s], dt_off[s + 1], gt_off[s], gt_off[s + 1]
+            db, gb, gm = tab["dt_boxes"][d0:d1], tab["gt_boxes"][g0:g1], tab["gt_member"][g0:g1]
+            iou = iou_matrix(db, gb)
+            best = iou.argmax(1)
+            over = iou[np.arange(len(db)), best] >= self.thr
+            hit[d0:d1] = over
+            for j in range(S):
+                member = ((gm >> np.uint64(j)) & one).astype(bool)
+                taken = np.zeros(len(gb), bool)
+                for i, g in enumerate(best):               # _tp_fp's loop on the rows the table already sorted
+                    tp[j, d0 + i] = drop[j, d0 + i] = False
+                    if over[i]:
+                        if not member[g]:
+                            drop[j, d0 + i] = True
+                        elif not taken[g]:
+                            tp[j, d0 + i] = taken[g] = True
+        if timings is not None:
+            timings.update(table_build_s=t1 - t0, kernel_s=t2 - t1, copy_s=t3 - t2)
+        return tab, tp, drop, hit
+
+    def _labels_device(self, members, S):
+        """_labels_host's result from one device match: per class one run of the flat arrays, per subset one mask."""
+        tab, tp, drop, hit = self.match_on_device(members, S, self.timings)
+        dt_off, seg_cat = tab["dt_off"], tab["seg_cat"]
+        first = np.searchsorted(seg_cat, np.arange(self.K + 1))          # segments are ordered by class
+        scores = [[[] for _ in range(self.K)] for _ in range(S)]
+        labels = [[[] for _ in range(self.K)] for _ in range(S)]
+        for c in range(self.K):
+            d0, d1 = dt_off[first[c]], dt_off[first[c + 1]]
+            for s in range(S):
+                keep = ~drop[s, d0:d1]
+                scores[s][c].append(tab["dt_scores"][d0:d1][keep])
+                labels[s][c].append(tp[s, d0:d1][keep])
+        correct = np.zeros(self.K)
+        has_gt = np.diff(tab["gt_off"]) > 0
+        for i in np.flatnonzero(has_gt):
+            pos = tab["top_pos"][i]
+            if pos >= 0:
+                correct[seg_cat[i]] += float(hit[dt_off[i] + pos])
+            else:                                          # the cap cut the arg-max detection off: ask the host
+                key, c = tab["seg_key"][i], int(seg_cat[i])
+                boxes, sc, cls = self.dt[key]
+                db, ds = boxes[cls == c], sc[cls == c]
+                gb, gc = self.gt[key][:2]
+                top = int(np.argmax(ds))
+                correct[c] += float(iou_matrix(db[top:top + 1], gb[gc == c]).max() >= self.thr)
+        return scores, labels, correct
+
+    def evaluate(self):
+        """-> dict(subset_names [S] sorted, ap_per_class {name: [K]}, mean_ap {name: float}, precisions / recalls
+        {name: list of per-class arrays}, num_gt {name: [K]}, corloc_per_class [K], mean_corloc)."""
+        import time
+        import warnings
+        names = self.subset_names()
+        S = len(names)
+        if not S:
+            warnings.warn("PascalSubsetEvaluator: no groundtruth box names a subset: there are no subset metrics")
+        members = self._members(names)
+        self.timings = {}
+        t0 = time.perf_counter()
+        if self.device is None or S > self.MAX_DEVICE_SUBSETS or not S:
+            scores, labels, correct = self._labels_host(members, S)
+            self.timings["match_s"] = time.perf_counter() - t0
+        else:
+            scores, labels, correct = self._labels_device(members, S)
+        t0 = time.perf_counter()
+        num_gt_imgs = np.zeros(self.K, int)
+        num_gt = np.zeros((S, self.K), int)
+        for key, (boxes, cls, diff, subsets) in self.gt.items():
+            for c in range(self.K):
+                num_gt_imgs[c] += int(np.any(cls == c))
+                num_gt[:, c] += members[key][cls == c].sum(0)
+        out = dict(subset_names=names, ap_per_class={}, mean_ap={}, precisions={}, recalls={}, num_gt={})
+        acc = self._pascal
+        acc.clear()
+        acc.num_gt_imgs, acc.correct_imgs = num_gt_imgs, correct
+        for s, name in enumerate(names):                   # PascalDetectionEvaluator.evaluate() on this subset's lists
+            acc.num_gt, acc.scores, acc.labels = num_gt[s], scores[s], labels[s]
+            res = acc.evaluate()
+            out["ap_per_class"][name], out["mean_ap"][name] = res["ap_per_class"], res["mean_ap"]
+            out["precisions"][name], out["recalls"][name] = res["precisions"], res["recalls"]
+            out["num_gt"][name] = num_gt[s].copy()
+        acc.num_gt, acc.scores, acc.labels = np.zeros(self.K, int), [[] for _ in range(self.K)], [[] for _ in range(self.K)]
+        res = acc.evaluate()
+        out["corloc_per_class"], out["mean_corloc"] = res["corloc_per_class"], res["mean_corloc"]
+        acc.clear()
+        self.timings["accumulate_s"] = time.perf_counter() - t0
+        return out
+
+
+def macro_pr_curve(precisions, recalls):
+    """eval_util.compute_pr_curve (eval_util.py:100-173): the macro-averaged precision/recall curve of the per-class
+    curves. Classes without a curve (None) or with a single point are skipped; per class, equal recalls keep their
+    highest precision and the precision becomes its running maximum from the high-recall end; then, for every distinct
+    recall value of any class in descending order, the mean over the kept classes of the precision at the first point
+    whose recall reaches it (a class that never reaches it adds 0). -> (precisions, recalls), recalls descending.
+    PARITY UNPINNED: the reference's file imports TensorFlow and cannot be run next to this one."""
+    if len(precisions) != len(recalls):
+        raise ValueError("precision/recall number of class not matched")
+    for p, r in zip(precisions, recalls):
+        if p is not None and r is not None and len(p) != len(r):
+            raise ValueError("precision/recall number of class not matched")
+    new_p, new_r = [], []
+    for p, r in zip(precisions, recalls):
+        if p is None or r is None or len(p) <= 1:
+            continue
+        pm, rn = [float(p[0])], [float(r[0])]
+        for i in range(1, len(p)):
+            if r[i] != rn[-1]:
+                pm.append(float(p[i]))
+                rn.append(float(r[i]))
+            else:
+                pm[-1] = max(pm[-1], float(p[i]))
+        top = 0.0
+        for i in reversed(range(len(pm))):
+            top = max(pm[i], top)
+            pm[i] = top
+        new_p.append(pm)
+        new_r.append(rn)
+    thresholds = sorted({v for r in new_r for v in r}, reverse=True)
+    index = [len(r) for r in new_r]
+    out_p, out_r = [], []
+    for th in thresholds:
+        total = 0.0
+        for i, (p, r) in enumerate(zip(new_p, new_r)):
+            while index[i] > 0 and r[index[i] - 1] >= th:
+                index[i] -= 1
+            if index[i] < len(r):
+                total += p[index[i]]
+        out_p.append(total / len(new_p))
+        out_r.append(th)
+    return out_p, out_r
+
+
+def nms_string(nms_type, nms_iou_threshold, soft_nms_sigma):
+    """'_'.join(eval_util.get_string_list_for_nms(...)) (eval_util.py:49-56): 'standard_1.0', 'soft-gaussian_0.5'."""
+    if nms_type in ("standard", "soft-linear"):
+        return "%s_%s" % (nms_type, str(nms_iou_threshold))
+    if nms_type == "soft-gaussian":
+        return "%s_%s" % (nms_type, str(soft_nms_sigma))
+    raise ValueError("Cannot identify NMS type.")
+
+
+def write_pr_curves(eval_dir, precisions, recalls, nms_type, nms_iou_threshold, soft_nms_sigma):
+    """eval_util.visualize_pr_curve's text files (eval_util.py:186-203): <eval_dir>/pr_curve_<subset>_<nms str>.txt, one
+    '%f\\t%f\\n' line (precision, recall) per point of macro_pr_curve; precisions / recalls as evaluate() returns
+    them. The matplotlib image summary is not written. Returns the paths."""
+    import os
+    tail = nms_string(nms_type, nms_iou_threshold, soft_nms_sigma)
+    paths = []
+    for name in precisions:
+        p, r = macro_pr_curve(precisions[name], recalls[name])
+        path = os.path.join(eval_dir, "pr_curve_" + name + "_" + tail + ".txt")
+        with open(path, "w") as fh:
+            for a, b in zip(p, r):
+                fh.write("%f\t%f\n" % (a, b))
+        paths.append(path)
+    return paths
+
+
 # ------------------------------------------------------------------------------ MS-COCO metrics
 class CocoDetectionEvaluator:
     """The 12 MS-COCO box metrics of `eval_util.evaluate_detection_results_coco` (eval_util.py:393-550) /

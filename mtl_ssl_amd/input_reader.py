@@ -227,6 +227,14 @@ def _dense_from_text(strings, width):
     return np.asarray(vals, np.float32).reshape(-1, width)
 
 
+def groundtruth_subset(features):
+    """image/object/subset of a parsed example (tf_example_decoder.py:54, 101): one '|'-joined string of subset names
+    per groundtruth box, as a list of str; None when the record lacks the field."""
+    if "image/object/subset" not in features:
+        return None
+    return [s.decode("utf-8") for s in features["image/object/subset"]]
+
+
 def decode_example(serialized, num_classes):
     """TfExampleDecoder.decode + trainer._get_inputs for one example. Returns the per-image dict of
     the `synthetic.make_batch` contract: image float32 [H,W,3] (0..255), groundtruth_boxes [G,4]
@@ -265,6 +273,10 @@ def decode_example_uint8(serialized, num_classes, timings=None):
                groundtruth_difficult=np.asarray(f.get("image/object/difficult", np.zeros(0, np.int64))).astype(bool),
                filename=(f.get("image/filename") or [b""])[0].decode("utf-8"),
                source_id=(f.get("image/source_id") or [b""])[0].decode("utf-8"))
+    if "image/object/subset" in f:
+        # evaluation only: collate_labels does not pass it on, so no batch, augmentation program or stream state
+        # carries it (eval reads it per record, beside the stream)
+        out["groundtruth_subset"] = groundtruth_subset(f)
     if "image/window/bbox/ymin" in f:
         out["window_boxes"] = boxes("image/window/bbox/")
         out["window_classes"] = _dense_from_text(f.get("image/window/labels/text", []), K + 1)

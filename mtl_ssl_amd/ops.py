@@ -1077,6 +1077,44 @@ def coco_match(dt_offsets, gt_offsets, dt_boxes, gt_boxes, gt_area, gt_crowd, io
     return dt_match, dt_ignore, npig, packed
 
 
+PASCAL_MATCH_MAX_GT = 256            # MTLSSL_PASCAL_MATCH_MAX_GT: groundtruth boxes of one segment (a lane's claimed set)
+PASCAL_MATCH_MAX_SUBSETS = 64        # one lane of the wavefront per subset
+PASCAL_MATCH_LEFT_OUT = 2            # MTLSSL_PASCAL_MATCH_LEFT_OUT: `hit` of a segment the kernel refused
+
+
+def pascal_match(dt_offsets, gt_offsets, dt_boxes, gt_boxes, gt_member, iou_threshold, num_subsets):
+    """mtlssl_pascal_match: PascalDetectionEvaluator._tp_fp's labelling of every segment — one (image, class) pair
+    with a detection — for every groundtruth subset in one launch. dt_offsets / gt_offsets: host ints [S+1], the
+    segments' row ranges in dt_boxes [ND,4] (per segment already filtered, sorted and capped as _tp_fp does) and
+    gt_boxes [NG,4] (float64, device) / gt_member [NG] (int64 device, read as uint64: bit j = member of subset j).
+    A segment holds at most PASCAL_MATCH_MAX_GT groundtruth boxes, num_subsets <= PASCAL_MATCH_MAX_SUBSETS.
+    -> (tp [ND] int64, drop [ND] int64, hit [ND] uint8, packed): bit j of tp / drop is the detection's label in subset
+    j (read the words as uint64), hit = best IoU >= threshold whatever the membership; the three are views of `packed`,
+    one int64 device buffer, so that a single copy brings all of them to the host."""
+    dto = np.ascontiguousarray(dt_offsets, np.int64).reshape(-1)
+    gto = np.ascontiguousarray(gt_offsets, np.int64).reshape(-1)
+    S = len(dto) - 1
+    assert S >= 0 and len(gto) == S + 1 and dto[0] == 0 and gto[0] == 0, (dto.shape, gto.shape)
+    assert (np.diff(dto) >= 0).all() and (np.diff(gto) >= 0).all(), "segment offsets must not decrease"
+    ND, NG = int(dto[-1]), int(gto[-1])
+    assert max(ND, NG) < 2 ** 29, "offsets are int32"
+    dev = dt_boxes.device
+    assert tuple(dt_boxes.shape) == (ND, 4) and tuple(gt_boxes.shape) == (NG, 4) and tuple(gt_member.shape) == (NG,), \
+        (dt_boxes.shape, gt_boxes.shape, gt_member.shape)
+    f64 = torch.float64
+    packed = torch.empty((2 * ND + (ND + 7) // 8,), dtype=torch.int64, device=dev)
+    if POISON_WS:                        # a detection the kernel skips shows as hit = 255 (all subset bits set)
+        packed.fill_(-1)
+    tp, drop = packed[:ND], packed[ND:2 * ND]
+    hit = packed[2 * ND:].view(torch.uint8)[:ND]
+    offs = torch.from_numpy(np.concatenate([dto, gto]).astype(np.int32)).to(dev)
+    lib().pascal_match(ptr(offs), ptr(offs) + 4 * (S + 1), S, int(np.diff(gto).max()) if S else 0,
+                       ptr(_chk(dt_boxes, f64)) if ND else None, ptr(_chk(gt_boxes, f64)) if NG else None,
+                       ptr(_chk(gt_member, torch.int64)) if NG else None, float(iou_threshold), int(num_subsets),
+                       ptr(tp) if ND else None, ptr(drop) if ND else None, ptr(hit) if ND else None, _stream())
+    return tp, drop, hit, packed
+
+
 def draw_boxes(image, boxes, colors, thickness):
     """mtlssl_draw_boxes: paints the outlines of boxes [n,4] int32 (ymin, xmin, ymax, xmax absolute, half open) in
     colors [n,3] uint8 into image, a uint8 [H,W,3] device tensor whose rows may be strided (a column slice of a wider
