@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 19
+#define MTLSSL_ABI_VERSION 20
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -713,6 +713,10 @@ int mtlssl_relu6_bwd(const float* y, const float* dy, float* dx, int64_t n, mtls
  * models/faster_rcnn_resnet_v1_feature_extractor.py:74-90 (pass the negated means). */
 int mtlssl_bias_add_channels(const float* x, const float* bias, float* out, int64_t rows, int C,
                              mtlssl_stream_t s);
+/* out[p,c] = x[p,2-c] - mean[c] for p < npix, c < 3 (mean: 3 device floats, in the OUTPUT's channel order): RGB -> BGR
+ * and Caffe's mean subtraction of models/faster_rcnn_vgg_16_feature_extractor.py:43-49 in one pass. One IEEE
+ * subtraction per element; out may be x. */
+int mtlssl_preprocess_bgr(const float* x, const float* mean, float* out, int64_t npix, mtlssl_stream_t s);
 /* tf.one_hot(depth=2) of a 0/1 float vector (faster_rcnn_meta_arch.py:1646-1647). */
 int mtlssl_onehot2(const float* t, float* out, int64_t n, mtlssl_stream_t s);
 

@@ -299,6 +299,30 @@ __global__ void __launch_bounds__(256)
   }
   reinterpret_cast<float4*>(out)[i4] = make_float4(o[0], o[1], o[2], o[3]);
 }
+// out[p, c] = x[p, 2 - c] - mean[c] over [npix, 3] rows: the channel flip and mean subtraction of the VGG-16 extractor in
+// one pass. Thread t < n4 owns pixels 4t .. 4t+3 = 12 consecutive floats = three float4 loads and three float4 stores
+// (vec != 0: both pointers 16-byte aligned); threads n4 .. n4+tail-1 own one pixel of the tail each (every pixel when
+// vec == 0). A thread reads all of its pixels before it writes any and no two threads share a pixel, so out may be x.
+__global__ void __launch_bounds__(256)
+    k_preprocess_bgr(const float* x, const float* mean, float* out, int64_t n4, int64_t npix, int vec) {
+  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const float m0 = mean[0], m1 = mean[1], m2 = mean[2];
+  if (vec && t < n4) {
+    const float4* xi = reinterpret_cast<const float4*>(x) + t * 3;
+    float4 a = xi[0], b = xi[1], c = xi[2];
+    float4* o = reinterpret_cast<float4*>(out) + t * 3;
+    o[0] = make_float4(a.z - m0, a.y - m1, a.x - m2, b.y - m0);
+    o[1] = make_float4(b.x - m1, a.w - m2, c.x - m0, b.w - m1);
+    o[2] = make_float4(b.z - m2, c.w - m0, c.z - m1, c.y - m2);
+    return;
+  }
+  int64_t p = vec ? n4 * 4 + (t - n4) : t;
+  if (p >= npix) return;
+  float r = x[p * 3 + 0], g = x[p * 3 + 1], bl = x[p * 3 + 2];
+  out[p * 3 + 0] = bl - m0;
+  out[p * 3 + 1] = g - m1;
+  out[p * 3 + 2] = r - m2;
+}
 __global__ void k_relu_bwd(const float* y, const float* dy, float* dx, int64_t n) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < n) dx[i] = y[i] > 0.f ? dy[i] : 0.f;
@@ -465,6 +489,16 @@ int mtlssl_bias_add_channels(const float* x, const float* bias, float* out, int6
     hipLaunchKernelGGL(k_bias_add_channels, dim3(cdiv(total, 256)), dim3(256), 0, S(stream), x, bias,
                        out, total, C);
   return check_launch("bias_add_channels");
+}
+int mtlssl_preprocess_bgr(const float* x, const float* mean, float* out, int64_t npix, mtlssl_stream_t stream) {
+  if (npix <= 0) return MTLSSL_OK;
+  int vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  int64_t n4 = vec ? npix / 4 : 0;
+  int64_t threads = vec ? n4 + (npix - n4 * 4) : npix;
+  MTLSSL_REQUIRE(cdiv(threads, 256) < (1ll << 31), "preprocess_bgr: npix = %lld is too large", (long long)npix);
+  hipLaunchKernelGGL(k_preprocess_bgr, dim3((unsigned)cdiv(threads, 256)), dim3(256), 0, S(stream), x, mean, out, n4,
+                     npix, vec);
+  return check_launch("preprocess_bgr");
 }
 int mtlssl_relu_bwd(const float* y, const float* dy, float* dx, int64_t n, mtlssl_stream_t stream) {
   if (!n) return MTLSSL_OK;

@@ -34,6 +34,14 @@ def _l2_from_hyperparams(hp):
         return float(reg.l2_regularizer.weight)
     return 0.0
 
+def _out_mask(tower, feat):
+    """mask_ref / mask6 of a predictor's backward for the features `tower` produced: the tower's output activation
+    fused into the gradient. Every tower that runs layers ends in ReLU (ReLU6 with `out_relu6`); a tower whose
+    `out_act` is None (the VGG-16 extractor's identity) has no activation of its own, and the gradient passes through
+    the exact zeros of its output unmasked."""
+    if getattr(tower, "out_act", "relu") is None:
+        return dict(mask_ref=None, mask6=False)
+    return dict(mask_ref=feat, mask6=bool(getattr(tower, "out_relu6", False)))
 
 
 class MaskRCNNBoxPredictor:
@@ -969,9 +977,8 @@ class FasterRCNNMetaArch:
         c = self.cfg
         # main head -> tower -> crops -> dF
         feat = pd["_feat"]
-        m6 = getattr(self.tower, "out_relu6", False)
         g_feat = self.box_predictor.backward(pd["_bp"], d_cls, d["refined_box_encodings"].view(feat.shape[0], -1),
-                                             feat.shape, mask_ref=feat, mask6=m6)
+                                             feat.shape, **_out_mask(self.tower, feat))
         stop = bool(mtl.stop_gradient_for_aux_tasks)
         shared = self._shared_classifier
         gw_shared = None
@@ -980,7 +987,7 @@ class FasterRCNNMetaArch:
             # main tower's output: its gradient joins the main head's before the tower's backward (or stops there).
             if mtl.closeness:
                 gcl = self.closeness_predictor.backward(pd["_cp"], d["closeness_predictions"], None, feat.shape,
-                                                        need_feat_grad=not stop, mask_ref=feat, mask6=m6)
+                                                        need_feat_grad=not stop, **_out_mask(self.tower, feat))
                 if not stop:
                     ops.axpby(gcl, g_feat, 1.0, 1.0)
             # The window crops went through the SAME tower variables. Without stop_gradient their gradient makes a
@@ -989,7 +996,7 @@ class FasterRCNNMetaArch:
             if mtl.window and not stop:
                 wfeat = pd["_wfeat"]
                 g = self.window_predictor.backward(pd["_wp"], d["window_class_predictions"], None, wfeat.shape,
-                                                   mask_ref=wfeat, mask6=m6)
+                                                   **_out_mask(self.window_tower, wfeat))
                 hook, self.ps.grad_ready_hook = self.ps.grad_ready_hook, None
                 gw_shared = self.tower.backward(g, wfeat, pd["_wctx"], need_input_grad=True, masked=True)
                 self.ps.grad_ready_hook = hook
@@ -1008,14 +1015,14 @@ class FasterRCNNMetaArch:
             if mtl.closeness:
                 cfeat = pd["_cfeat"]
                 g = self.closeness_predictor.backward(pd["_cp"], d["closeness_predictions"], None, cfeat.shape,
-                                                      mask_ref=cfeat, mask6=m6)
+                                                      **_out_mask(self.closeness_tower, cfeat))
                 gc = self.closeness_tower.backward(g, cfeat, pd["_cctx"], need_input_grad=not stop, masked=True)
                 if not stop:
                     todo.append((gc, pd["_argmax"], pd["proposal_boxes_normalized"].view(-1, 4), pd["_box_ind"]))
             if mtl.window:                       # behind the closeness tower, on the same stream
                 wfeat = pd["_wfeat"]
                 g = self.window_predictor.backward(pd["_wp"], d["window_class_predictions"], None, wfeat.shape,
-                                                   mask_ref=wfeat, mask6=m6)
+                                                   **_out_mask(self.window_tower, wfeat))
                 gw = self.window_tower.backward(g, wfeat, pd["_wctx"], need_input_grad=not stop, masked=True)
                 if not stop:
                     todo.append((gw, pd["_wargmax"], pd["_wboxes"], pd["_wbox_ind"]))

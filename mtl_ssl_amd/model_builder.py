@@ -3,7 +3,7 @@
 `FASTER_RCNN_FEATURE_EXTRACTOR_CLASS_MAP` is the reference's plugin registry: feature
 extractors register by the `feature_extractor.type` string of the pipeline config.
 """
-from . import frcnn, inception_resnet_v2, mobilenet, resnet, rfcn
+from . import frcnn, inception_resnet_v2, mobilenet, resnet, rfcn, vgg
 from .params import ParamStore
 
 
@@ -50,7 +50,21 @@ def _inception_resnet_v2(ps, fe_cfg, is_training):
         ps, is_training, int(fe_cfg.first_stage_features_stride), **kwargs)
 
 
+def _vgg_16(ps, fe_cfg, is_training):
+    # The reference's builder always passes `batch_norm_trainable` (builders/model_builder.py:235) to a constructor that
+    # does not take it (models/faster_rcnn_vgg_16_feature_extractor.py:86-92): every config dies in a TypeError there.
+    # Here the class is built as it is defined; the flag's default is accepted and `true` is refused.
+    if bool(fe_cfg.batch_norm_trainable):
+        raise ValueError("feature_extractor.batch_norm_trainable: true — faster_rcnn_vgg_16 has no BatchNorm")
+    kwargs = {}
+    if fe_cfg.has("weight_decay"):
+        kwargs["weight_decay"] = float(fe_cfg.weight_decay)
+    return vgg.FasterRCNNVgg16FeatureExtractor(
+        ps, is_training, int(fe_cfg.first_stage_features_stride), freeze_layer=str(fe_cfg.freeze_layer), **kwargs)
+
+
 FASTER_RCNN_FEATURE_EXTRACTOR_CLASS_MAP = {
+    "faster_rcnn_vgg_16": _vgg_16,
     "faster_rcnn_inception_resnet_v2": _inception_resnet_v2,
     # builders/model_builder.py:64-65 registers this name with the SAME Inception-ResNet-v2 class
     # (paper configs model61/62/91/92 use it)

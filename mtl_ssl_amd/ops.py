@@ -1616,6 +1616,16 @@ def bias_add_channels(x, bias):
     return out
 
 
+def preprocess_bgr(x, mean, out=None):
+    """out[..., c] = x[..., 2 - c] - mean[c] over a [..., 3] fp32 tensor (`mean`: 3 device floats in the output's channel
+    order): the VGG-16 extractor's RGB -> BGR flip and mean subtraction. `out` may be x itself."""
+    if x.shape[-1] != 3 or mean.numel() != 3:
+        raise ValueError("preprocess_bgr expects [..., 3] inputs and 3 means")
+    out = torch.empty_like(x) if out is None else out
+    lib().preprocess_bgr(ptr(_chk(x)), ptr(_chk(mean)), ptr(_chk(out)), x.numel() // 3, _stream())
+    return out
+
+
 def onehot2(t):
     out = torch.empty(tuple(t.shape) + (2,), dtype=f32, device=t.device)
     lib().onehot2(ptr(_chk(t)), ptr(out), t.numel(), _stream())

@@ -80,6 +80,11 @@ class RfcnBoxPredictor:
 
 class RFCNMetaArch(FasterRCNNMetaArch):
     def __init__(self, ps, is_training, frcnn, mtl, feature_extractor, seed=0):
+        if not getattr(feature_extractor, "supports_rfcn", True):
+            # R-FCN runs the extractor's second-stage tower once on the whole map (block4 at stride 16); an extractor
+            # whose tower is the identity would put reduce_depth straight on the RPN's map — not built, not tested
+            raise ValueError("rfcn_box_predictor with feature_extractor %s is not built: its second-stage tower is the "
+                             "identity; use mask_rcnn_box_predictor" % type(feature_extractor).__name__)
         super().__init__(ps, is_training, frcnn, mtl, feature_extractor, seed=seed)
         # mtl.shared_feature 'classifier_feature_maps' under R-FCN (rfcn_meta_arch.py:292-300, 346-362) is not what it
         # is under Faster R-CNN: the closeness predictor reads the MAIN tower's whole-map features (stopped or not) and
