@@ -34,15 +34,6 @@ def _l2_from_hyperparams(hp):
         return float(reg.l2_regularizer.weight)
     return 0.0
 
-def _out_mask(tower, feat):
-    """mask_ref / mask6 of a predictor's backward for the features `tower` produced: the tower's output activation
-    fused into the gradient. Every tower that runs layers ends in ReLU (ReLU6 with `out_relu6`); a tower whose
-    `out_act` is None (the VGG-16 extractor's identity) has no activation of its own, and the gradient passes through
-    the exact zeros of its output unmasked."""
-    if getattr(tower, "out_act", "relu") is None:
-        return dict(mask_ref=None, mask6=False)
-    return dict(mask_ref=feat, mask6=bool(getattr(tower, "out_relu6", False)))
-
 
 class MaskRCNNBoxPredictor:
     """core/box_predictor.py:339-611: RoI features -> (spatial mean | flatten) -> optional FC_i_depth layers, each
@@ -249,6 +240,9 @@ class FasterRCNNMetaArch:
         self._gt = None
         self._window = None
         self._edgemask = None
+        # made on the device when first needed (the constructor stays on the host: model_builder.variable_specs)
+        self._aux_stream_obj = self._wgrad_stream_obj = None
+        self._bn_table = self._frozen_w_bn = self._dedup_overflow = None
 
     def _make_predictor(self, scope, num_classes, bp_cfg, class_only, slot0=0):
         """builders/box_predictor_builder.py:23-110 (mask_rcnn_box_predictor branch)."""
@@ -257,10 +251,9 @@ class FasterRCNNMetaArch:
                              "rfcn_box_predictor)")
         c = self.cfg
         P = (int(c.initial_crop_size) - int(c.maxpool_kernel_size)) // int(c.maxpool_stride) + 1
-        hw = self.tower.out_hw(P) if hasattr(self.tower, "out_hw") else None
         return MaskRCNNBoxPredictor(self.ps, scope, self.tower.cout, num_classes, bp_cfg.mask_rcnn_box_predictor,
                                     self._is_training and bp_cfg.trainable and not self._first_stage_only,
-                                    class_only, feat_hw=hw, slot0=slot0)
+                                    class_only, feat_hw=self.tower.out_hw(P), slot0=slot0)
 
     # ------------------------------------------------------------------ properties / plumbing
     @property
@@ -276,7 +269,7 @@ class FasterRCNNMetaArch:
         MTLSSL_AUX_STREAM=0)."""
         if self.ps.device.type != "cuda" or os.environ.get("MTLSSL_AUX_STREAM", "1") == "0":
             return None
-        if getattr(self, "_aux_stream_obj", None) is None:
+        if self._aux_stream_obj is None:
             self._aux_stream_obj = torch.cuda.Stream(device=self.ps.device)
         return self._aux_stream_obj
 
@@ -287,9 +280,9 @@ class FasterRCNNMetaArch:
         gradients gain — 5.10 vs 4.97 ms; MTLSSL_WGRAD_STREAM=1 forces it on)."""
         env = os.environ.get("MTLSSL_WGRAD_STREAM")
         if self.ps.device.type != "cuda" or env == "0" or (
-                env is None and not getattr(self._feature_extractor, "supports_wgrad_stream", False)):
+                env is None and not self._feature_extractor.supports_wgrad_stream):
             return nn.INLINE_WGRAD
-        if getattr(self, "_wgrad_stream_obj", None) is None:
+        if self._wgrad_stream_obj is None:
             self._wgrad_stream_obj = nn.WgradStream(torch.cuda.Stream(device=self.ps.device))
         return self._wgrad_stream_obj
 
@@ -303,14 +296,14 @@ class FasterRCNNMetaArch:
         if s is not None:
             out.append(s)
         w = self._wgrad_exec()
-        if getattr(w, "stream", None) is not None:
+        if w.stream is not None:
             out.append(w.stream)
         return out
 
     def prepare(self):
         for l in self.layers:
             l.prepare()
-        self._bn_table = None          # the layers' scale / shift tensors were re-created
+        self._bn_table = self._frozen_w_bn = None          # the layers' scale / shift / shadow tensors were re-created
         ops.fold_scales(self.ps)
         # transformed filters of the Winograd layers are kept per optimizer step (ops.FilterXfCache); the frozen
         # layers' shadow filters were just re-created, so start from an empty cache
@@ -320,20 +313,20 @@ class FasterRCNNMetaArch:
         """After an optimizer step: ONE batched refresh of the normaliser constants of the layers whose
         BatchNorm parameters train, then ONE batched fold of every scale into the shadow weights (`folded`: the
         optimizer launch already wrote them, mtlssl_sgd_momentum_clip_fold)."""
+        if self._frozen_w_bn is None:
+            # a trained normaliser (gamma / beta among grad_vars) on a frozen filter with a shadow copy
+            self._frozen_w_bn = [l for l in self.layers
+                                 if l.beta in l.grad_vars() and l.w not in l.grad_vars() and l.w_eff is not None]
         if self.ps.device.type == "cuda":
-            if getattr(self, "_bn_table", None) is None:
+            if self._bn_table is None:
                 # every layer whose gamma / beta train — with resnet's batch_norm_trainable that includes layers whose
                 # FILTERS are frozen (root conv, frozen blocks: slim/nets/resnet_utils.py:203-237)
                 self._bn_table = ops.BnRefreshTable(self.layers, self.ps.device)
-                self._frozen_w_bn = [l for l in self.layers if getattr(l, "bn_trainable", False)
-                                     and not l.w.trainable and getattr(l, "w_eff", None) is not None]
             ops.bn_refresh(self._bn_table)
         else:
             for l in self.layers:
-                if getattr(l, "trainable", False) or getattr(l, "bn_trainable", False):
+                if l.grad_vars():
                     l.refold()
-            self._frozen_w_bn = [l for l in self.layers if getattr(l, "bn_trainable", False) and not l.w.trainable
-                                 and getattr(l, "w_eff", None) is not None]
         for l in self._frozen_w_bn:
             # a frozen filter under a trained normaliser: its shadow copy is not one of the batched folds (those cover
             # the trainable filters' flat buffer), so it is re-scaled here — a handful of layers of an unusual config
@@ -643,7 +636,7 @@ class FasterRCNNMetaArch:
     def check_device_flags(self):
         """Raise if a device-side invariant was violated since the last check (reads one int: call it where the
         host synchronises anyway, e.g. with the loss NaN check)."""
-        f = getattr(self, "_dedup_overflow", None)
+        f = self._dedup_overflow
         if f is not None and int(f.item()) != 0:
             raise RuntimeError("refiner window de-duplication overflowed its %d slots per image (non-finite or "
                                "out-of-range proposal boxes?)" % self.DEDUP_SLOTS)
@@ -659,7 +652,7 @@ class FasterRCNNMetaArch:
             # The last window of every proposal is the whole image (up to the last bit of z + (1 - z)): crop
             # and run the tower once per DISTINCT box instead of once per proposal, then expand the predictions
             # back — bit-identical outputs, 4*N2 + 8 ROIs per image through the tower instead of 5*N2.
-            if getattr(self, "_dedup_overflow", None) is None:
+            if self._dedup_overflow is None:
                 self._dedup_overflow = torch.zeros((1,), dtype=torch.int32, device=F.device)
             rois, src_row = ops.dedup_windows(ew, self.DEDUP_SLOTS, self._dedup_overflow)
             R = rois.shape[1]
@@ -681,7 +674,7 @@ class FasterRCNNMetaArch:
         # stream — HIP multiplexes streams onto a few hardware queues (4 by default), and with the data-parallel
         # trainer's own step and communication streams a further one ended up sharing a queue with another compute
         # stream (measured with a 1-rank communicator: 60.2 ms/step against 55.5)
-        return getattr(self._wgrad_exec(), "stream", None)
+        return self._wgrad_exec().stream
 
     def _expand_window_class_predictions(self, pd):
         """Window-class predictions of every proposal's N_EXPAND windows, [B, N_EXPAND, N2] row order: the step of
@@ -978,7 +971,7 @@ class FasterRCNNMetaArch:
         # main head -> tower -> crops -> dF
         feat = pd["_feat"]
         g_feat = self.box_predictor.backward(pd["_bp"], d_cls, d["refined_box_encodings"].view(feat.shape[0], -1),
-                                             feat.shape, **_out_mask(self.tower, feat))
+                                             feat.shape, **self.tower.out_mask(feat))
         stop = bool(mtl.stop_gradient_for_aux_tasks)
         shared = self._shared_classifier
         gw_shared = None
@@ -987,7 +980,7 @@ class FasterRCNNMetaArch:
             # main tower's output: its gradient joins the main head's before the tower's backward (or stops there).
             if mtl.closeness:
                 gcl = self.closeness_predictor.backward(pd["_cp"], d["closeness_predictions"], None, feat.shape,
-                                                        need_feat_grad=not stop, **_out_mask(self.tower, feat))
+                                                        need_feat_grad=not stop, **self.tower.out_mask(feat))
                 if not stop:
                     ops.axpby(gcl, g_feat, 1.0, 1.0)
             # The window crops went through the SAME tower variables. Without stop_gradient their gradient makes a
@@ -996,7 +989,7 @@ class FasterRCNNMetaArch:
             if mtl.window and not stop:
                 wfeat = pd["_wfeat"]
                 g = self.window_predictor.backward(pd["_wp"], d["window_class_predictions"], None, wfeat.shape,
-                                                   **_out_mask(self.window_tower, wfeat))
+                                                   **self.window_tower.out_mask(wfeat))
                 hook, self.ps.grad_ready_hook = self.ps.grad_ready_hook, None
                 gw_shared = self.tower.backward(g, wfeat, pd["_wctx"], need_input_grad=True, masked=True)
                 self.ps.grad_ready_hook = hook
@@ -1015,14 +1008,14 @@ class FasterRCNNMetaArch:
             if mtl.closeness:
                 cfeat = pd["_cfeat"]
                 g = self.closeness_predictor.backward(pd["_cp"], d["closeness_predictions"], None, cfeat.shape,
-                                                      **_out_mask(self.closeness_tower, cfeat))
+                                                      **self.closeness_tower.out_mask(cfeat))
                 gc = self.closeness_tower.backward(g, cfeat, pd["_cctx"], need_input_grad=not stop, masked=True)
                 if not stop:
                     todo.append((gc, pd["_argmax"], pd["proposal_boxes_normalized"].view(-1, 4), pd["_box_ind"]))
             if mtl.window:                       # behind the closeness tower, on the same stream
                 wfeat = pd["_wfeat"]
                 g = self.window_predictor.backward(pd["_wp"], d["window_class_predictions"], None, wfeat.shape,
-                                                   **_out_mask(self.window_tower, wfeat))
+                                                   **self.window_tower.out_mask(wfeat))
                 gw = self.window_tower.backward(g, wfeat, pd["_wctx"], need_input_grad=not stop, masked=True)
                 if not stop:
                     todo.append((gw, pd["_wargmax"], pd["_wboxes"], pd["_wbox_ind"]))
@@ -1046,13 +1039,11 @@ class FasterRCNNMetaArch:
             aux.wait_stream(cur)
             with torch.cuda.stream(aux):
                 aux_backward(collect=pending)
-        if getattr(self.tower, "supports_wgrad_stream", False) and not shared:
-            # the main tower's filter gradients feed nothing but the optimizer: on the filter-gradient stream (joined at
-            # the end of backward) they leave this stream the dgrad chain that the trunk's backward is waiting for
-            g_crops = self.tower.backward(g_feat, feat, pd["_tower_ctx"], need_input_grad=True, masked=True,
-                                          wgrad=self._wgrad_exec())
-        else:
-            g_crops = self.tower.backward(g_feat, feat, pd["_tower_ctx"], need_input_grad=True, masked=True)
+        # the main tower's filter gradients feed nothing but the optimizer: on the filter-gradient stream (joined at
+        # the end of backward) they leave this stream the dgrad chain that the trunk's backward is waiting for. With shared
+        # classifier features (the window crops went through this tower too) they stay inline
+        g_crops = self.tower.backward(g_feat, feat, pd["_tower_ctx"], need_input_grad=True, masked=True,
+                                      wgrad=nn.INLINE_WGRAD if shared else self._wgrad_exec())
         ops.roi_crop_pool_bwd(g_crops, pd["_argmax"], F.shape, pd["proposal_boxes_normalized"].view(-1, 4),
                               pd["_box_ind"], *crop_args, dfeat=dF, accumulate=False)
         if gw_shared is not None:
@@ -1098,13 +1089,10 @@ class FasterRCNNMetaArch:
         wg.run(self.rpn_conv, F, g_rf)
         # last consumer of F: accumulate and apply the ReLU mask of the trunk output
         gpF = self.rpn_conv.dgrad(F.shape, g_rf, out=dF, accum=True, mask_ref=F,
-                                  mask6=getattr(self._feature_extractor, "output_relu6", False))
+                                  mask6=self._feature_extractor.out_act == "relu6")
         pd["_gpF"] = gpF
         ops.mark("heads_backward")
-        if getattr(self._feature_extractor, "supports_wgrad_stream", False):
-            self._feature_extractor.backward_proposal_features(gpF, pd["_trunk_ctx"], wgrad=wg)
-        else:
-            self._feature_extractor.backward_proposal_features(gpF, pd["_trunk_ctx"])
+        self._feature_extractor.backward_proposal_features(gpF, pd["_trunk_ctx"], wgrad=wg)
         if side is not None:
             ops.wait_on(side, "backward end: aux stream")
         if wg.stream is not None:

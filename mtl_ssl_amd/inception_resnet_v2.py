@@ -25,18 +25,12 @@ def _conv(ps, scope, cin, cout, k, stride=1, padding="SAME", rate=1, trainable=T
                      bn_trainable=trainable, bn_scale=False)
 
 
-class Pool:
+class Pool(nn.Layer):
     """slim.max_pool2d / slim.avg_pool2d as a parameter-free chain element."""
-    trainable = False
 
     def __init__(self, kind, k, stride, padding):
+        super().__init__()
         self.kind, self.k, self.stride, self.padding = kind, k, stride, padding
-
-    def prepare(self):
-        pass
-
-    def refold(self):
-        pass
 
     def forward(self, x, out=None):
         """out: the pooling branch's channel slice of a concatenated map (max pooling only), or None."""
@@ -52,25 +46,22 @@ class Pool:
         _, _, OH, OW = ops.pool_geometry(H, W, self.k, self.stride, self.padding)
         return (N, OH, OW, C)
 
-    def wgrad(self, x, g):
-        pass
-
     def input_grad(self, x, y, g):
         if self.kind == "max":
             return ops.maxpool_bwd(x, y, g, self.k, self.stride, self.pads)
         return ops.avgpool_bwd(g, x.shape, self.k, self.stride, self.pads)
 
 
-class ResidualUp:
+class ResidualUp(nn.Layer):
     """The `up` convolution of block35/17/8: 1x1 conv with biases, no normaliser, whose output is
     scaled and added to the block input: net = act(net + scale * (conv(mixed) + b)). The scale is
     folded into a shadow copy of the filter and bias (inception_resnet_v2.py:47-52)."""
 
     def __init__(self, ps, scope, cin, cout, scale, trainable, wd):
+        super().__init__()
         self.ps, self.scope, self.cin, self.cout, self.scale, self.trainable = ps, scope, cin, cout, scale, trainable
         self.w = ps.add(scope + "/weights", (1, 1, cin, cout), XAVIER, trainable, wd)
         self.b = ps.add(scope + "/biases", (cout,), ("zeros",), trainable, wd)   # biases_regularizer
-        self._desc = {}
 
     def prepare(self):
         ps, dev = self.ps, self.ps.device
@@ -84,18 +75,11 @@ class ResidualUp:
             ops.axpby(ps.value(self.w.name), self.w_eff, self.scale, 0.0)
             ops.axpby(ps.value(self.b.name), self.b_eff, self.scale, 0.0)
 
-    def refold(self):
-        pass
-
-    def desc(self, shape):
-        d = self._desc.get(tuple(shape))
-        if d is None:
-            d = ops.conv_desc(shape, self.w.shape, 1, 1, "SAME")
-            self._desc[tuple(shape)] = d
-        return d
+    def geometry(self):
+        return self.w.shape, 1, 1, "SAME"
 
     def forward(self, mixed, residual, relu):
-        epi = ops.EPI_BIAS | ops.EPI_RESIDUAL | (ops.EPI_RELU if relu else 0)
+        epi = ops.EPI_BIAS | ops.EPI_RESIDUAL | nn.act_epilogue("relu" if relu else None)
         return ops.conv2d_fwd(self.desc(mixed.shape), mixed, self.w_eff, self.b_eff, residual, epi)
 
     def wgrad(self, mixed, gp):
@@ -107,8 +91,7 @@ class ResidualUp:
         self.ps.grad_ready(self.w, self.b)
 
     def dgrad(self, mixed_shape, gp, mask_ref):
-        epi = ops.EPI_MASK if mask_ref is not None else 0
-        return ops.conv2d_dgrad(self.desc(mixed_shape), gp, self.w_eff, None, mask_ref, epi)
+        return ops.conv2d_dgrad(self.desc(mixed_shape), gp, self.w_eff, None, mask_ref, nn.dgrad_epilogue(mask_ref=mask_ref))
 
 
 class Branches:
@@ -170,7 +153,7 @@ class Branches:
             probs = []
             for ci in first:
                 l = self.chains[ci][0]
-                epi = ops.EPI_BIAS | {None: 0, "relu": ops.EPI_RELU, "relu6": ops.EPI_RELU6}[l.act]
+                epi = ops.EPI_BIAS | nn.act_epilogue(l.act)
                 probs.append((l.desc(x.shape), l.w_eff, l.shift, epi, views[ci] if len(self.chains[ci]) == 1 else None))
             for ci, y in zip(first, ops.conv2d_fwd_grouped(x, probs)):
                 acts[ci].append(y)
@@ -223,8 +206,7 @@ class Branches:
                 segs.append((ch[0].desc(x.shape), gp, ch[0].w_eff))
             if not need_input_grad:
                 return None
-            epi = (ops.EPI_RESIDUAL if residual is not None else 0) | (ops.EPI_MASK if mask_ref is not None else 0)
-            return ops.conv2d_dgrad_segmented(segs, residual, mask_ref, epi)
+            return ops.conv2d_dgrad_segmented(segs, residual, mask_ref, nn.dgrad_epilogue(residual, mask_ref=mask_ref))
         # pooling-first chains go first so that a convolution's dgrad epilogue applies the final mask
         order = sorted(range(len(self.chains)), key=lambda i: not isinstance(self.chains[i][0], Pool))
         assert not isinstance(self.chains[order[-1]][0], Pool)
@@ -328,8 +310,10 @@ def block8(ps, s, t, wd, scale=0.20, relu=True):
     return ResBlock(ps, s, 2080, ch, scale, relu, t, wd)
 
 
-class InceptionTower:
+class InceptionTower(nn.Tower):
     """models/faster_rcnn_inception_resnet_v2_feature_extractor.py:118-171 on ROI crops."""
+    out_act = "relu"
+    supports_wgrad_stream = True
 
     def __init__(self, ps, scope, trainable, wd):
         p, t = scope + "/InceptionResnetV2/", trainable
@@ -366,8 +350,6 @@ class InceptionTower:
         out = self.conv_7b.forward(x)
         return out, ((c7, ctxs, x) if save else None)
 
-    supports_wgrad_stream = True
-
     def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD):
         c7, ctxs, pre7b = ctx
         gp = g_out if masked else ops.relu_bwd(out, g_out)
@@ -378,12 +360,14 @@ class InceptionTower:
         return self.mixed_7a.backward(gp, c7, mask_input=False, need_input_grad=need_input_grad, wgrad=wgrad)
 
 
-class FasterRCNNInceptionResnetV2FeatureExtractor:
+class FasterRCNNInceptionResnetV2FeatureExtractor(nn.FeatureExtractor):
+    out_act = "relu"
+    supports_wgrad_stream = True       # backward_proposal_features(..., wgrad=) can run filter gradients on a side stream
+    min_image_size = None
+
     def __init__(self, ps, is_training, first_stage_features_stride=16, weight_decay=0.0,
                  first_stage_scope="FirstStageFeatureExtractor"):
-        if first_stage_features_stride not in (8, 16):
-            raise ValueError("`first_stage_features_stride` must be 8 or 16.")
-        self.ps, self.is_training, self.weight_decay = ps, is_training, weight_decay
+        super().__init__(ps, is_training, first_stage_features_stride, weight_decay)
         t, wd = is_training, weight_decay
         atrous = first_stage_features_stride == 8
         p = first_stage_scope + "/InceptionResnetV2/"
@@ -415,7 +399,6 @@ class FasterRCNNInceptionResnetV2FeatureExtractor:
         rate = 2 if atrous else 1
         self.blocks17 = [block17(ps, p + "Repeat_1/block17_%d" % (i + 1), t, wd, rate) for i in range(20)]
         self.cout = 1088
-        self._neg_one = None
 
     def layers(self):
         return (list(self.stem) + self.mixed_5b.layers() + [l for b in self.blocks35 for l in b.layers()]
@@ -423,16 +406,10 @@ class FasterRCNNInceptionResnetV2FeatureExtractor:
 
     def preprocess(self, resized_inputs):
         """Maps pixel values to [-1, 1] (models/...inception_resnet_v2...:63-77)."""
-        x = torch.empty_like(resized_inputs)
-        ops.axpby(resized_inputs, x, 2.0 / 255.0, 0.0)
-        if self._neg_one is None:
-            self._neg_one = torch.full((3,), -1.0, dtype=torch.float32, device=x.device)
-        return ops.bias_add_channels(x, self._neg_one)
+        return self.to_unit_range(resized_inputs)
 
     def extract_proposal_features(self, x, save=True):
-        if x.dim() != 4:
-            raise ValueError("`preprocessed_inputs` must be 4 dimensional, got a tensor of shape %s"
-                             % (tuple(x.shape),))
+        self.check_inputs(x)
         acts = [x]
         for l in self.stem:
             acts.append(l.forward(acts[-1]))
@@ -447,8 +424,6 @@ class FasterRCNNInceptionResnetV2FeatureExtractor:
             x, c = b.forward(x, save)
             c17.append(c)
         return x, ((acts, c5, c35, c6, c17) if save else None)
-
-    supports_wgrad_stream = True       # backward_proposal_features(..., wgrad=) can run filter gradients on a side stream
 
     def backward_proposal_features(self, gp, ctx, wgrad=nn.INLINE_WGRAD):
         """gp: dL/d(pre-activation of the RPN feature map) (already ReLU-masked)."""

@@ -8,8 +8,6 @@ slim/nets/mobilenet_v1.py:120-266,376-413: conv 3x3/2 + 11 depthwise-separable b
 slim's MobileNet arg-scope runs BatchNorm in inference mode (train_batch_norm False) but leaves
 gamma/beta trainable, unlike the ResNet extractor; `bn_trainable=True` reproduces that.
 """
-import torch
-
 from . import nn, ops
 
 # (kind, stride, depth) — slim/nets/mobilenet_v1.py:120-140 up to Conv2d_11
@@ -27,26 +25,20 @@ class _PlainDepthwise(nn.DepthwiseBN):
     """Depthwise stage of slim.separable_conv2d(num_outputs=K): no normaliser, no activation."""
 
     def __init__(self, ps, scope, c, stride, trainable):
-        self.ps, self.scope, self.c = ps, scope, c
-        self.k, self.stride, self.dilation, self.eps, self.act = 3, stride, 1, EPS, None
-        self.trainable, self.bn_trainable = trainable, False
-        self.w = ps.add(scope + "/depthwise_weights", (3, 3, c, 1), _INIT, trainable, 0.0)
-        self._desc = {}
+        super().__init__(ps, scope, c, 3, stride, 1, trainable, 0.0, EPS, None, _INIT, batch_norm=False)
 
     def prepare(self):
         self.scale = None
         self.shift = None
-        self.w_eff = self.ps.value(self.w.name).view(3, 3, self.c)
-
-    def refold(self):
-        pass
+        self.w_eff = self.ps.value(self.w.name).view(self.w_eff_shape)
 
     def forward(self, x):
         return ops.depthwise_fwd(self.desc(x.shape), x, self.w_eff, None, 0)
 
 
-class MobilenetTower:
+class MobilenetTower(nn.Tower):
     """models/faster_rcnn_mobilenet_v1_feature_extractor.py:145-184 on ROI crops."""
+    out_act = "relu6"
 
     def __init__(self, ps, scope, cin, trainable, weight_decay):
         p = scope + "/MobilenetV1/"
@@ -72,9 +64,8 @@ class MobilenetTower:
         a13 = self.pw13.forward(d13)
         return a13, ((crops, d12, a12, d13) if save else None)
 
-    out_relu6 = True
-
-    def backward(self, g_out, out, ctx, need_input_grad, masked=False):
+    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD):
+        """A few ~10-us kernels: the filter gradients run inline whatever `wgrad` is (FasterRCNNMetaArch._wgrad_exec)."""
         crops, d12, a12, d13 = ctx
         gp = g_out if masked else ops.relu6_bwd(out, g_out)
         self.pw13.bn_grad(out, gp)
@@ -96,16 +87,14 @@ def _sep_pointwise(ps, scope, cin, cout, trainable):
                      bn_trainable=trainable, weights_name="pointwise_weights")
 
 
-class FasterRCNNMobilenetV1FeatureExtractor:
-    output_relu6 = True
+class FasterRCNNMobilenetV1FeatureExtractor(nn.FeatureExtractor):
+    out_act = "relu6"
 
     def __init__(self, ps, is_training, first_stage_features_stride=16, weight_decay=0.0,
                  first_stage_scope="FirstStageFeatureExtractor"):
-        if first_stage_features_stride not in (8, 16):
-            raise ValueError("`first_stage_features_stride` must be 8 or 16.")
+        super().__init__(ps, is_training, first_stage_features_stride, weight_decay)
         if first_stage_features_stride != 16:
             raise ValueError("MobileNet extractor: only first_stage_features_stride 16 is built")
-        self.ps, self.is_training, self.weight_decay = ps, is_training, weight_decay
         p = first_stage_scope + "/MobilenetV1/"
         self.stages = []
         cin = 3
@@ -123,32 +112,24 @@ class FasterRCNNMobilenetV1FeatureExtractor:
                                              bn_trainable=is_training))
             cin = depth
         self.cout = cin
-        self._neg_one = None
 
     def layers(self):
         return list(self.stages)
 
     def preprocess(self, resized_inputs):
         """Maps pixel values to [-1, 1] (models/...mobilenet...:93-103)."""
-        x = torch.empty_like(resized_inputs)
-        ops.axpby(resized_inputs, x, 2.0 / 255.0, 0.0)
-        if self._neg_one is None:
-            self._neg_one = torch.full((3,), -1.0, dtype=torch.float32, device=x.device)
-        return ops.bias_add_channels(x, self._neg_one)
+        return self.to_unit_range(resized_inputs)
 
     def extract_proposal_features(self, x, save=True):
-        if x.dim() != 4:
-            raise ValueError("`preprocessed_inputs` must be 4 dimensional")
-        if x.shape[1] < 33 or x.shape[2] < 33:
-            raise ValueError("image size must at least be 33 in both height and width.")
+        self.check_inputs(x)
         acts = [x]
         for l in self.stages:
             x = l.forward(x)
             acts.append(x)
         return x, (acts if save else None)
 
-    def backward_proposal_features(self, gp, acts):
-        """gp: dL/d(pre-activation of the RPN feature map) (already ReLU6-masked)."""
+    def backward_proposal_features(self, gp, acts, wgrad=nn.INLINE_WGRAD):
+        """gp: dL/d(pre-activation of the RPN feature map) (already ReLU6-masked). Filter gradients inline."""
         if not self.is_training:
             return
         for i in range(len(self.stages) - 1, -1, -1):

@@ -7,15 +7,17 @@ from . import frcnn, inception_resnet_v2, mobilenet, resnet, rfcn, vgg
 from .params import ParamStore
 
 
+def _weight_decay(fe_cfg):
+    """The `weight_decay` keyword of an extractor's constructor: its own default holds where the config has none."""
+    return {"weight_decay": float(fe_cfg.weight_decay)} if fe_cfg.has("weight_decay") else {}
+
+
 def _resnet(arch):
     def make(ps, fe_cfg, is_training):
-        kwargs = {}
-        if fe_cfg.has("weight_decay"):
-            kwargs["weight_decay"] = float(fe_cfg.weight_decay)
         return resnet.FasterRCNNResnetV1FeatureExtractor(
             ps, arch, is_training, int(fe_cfg.first_stage_features_stride),
             freeze_layer=fe_cfg.freeze_layer, batch_norm_trainable=bool(fe_cfg.batch_norm_trainable),
-            **kwargs)
+            **_weight_decay(fe_cfg))
     return make
 
 
@@ -31,11 +33,8 @@ def _no_batch_statistics(fe_cfg):
 
 def _mobilenet(ps, fe_cfg, is_training):
     _no_batch_statistics(fe_cfg)
-    kwargs = {}
-    if fe_cfg.has("weight_decay"):
-        kwargs["weight_decay"] = float(fe_cfg.weight_decay)
     return mobilenet.FasterRCNNMobilenetV1FeatureExtractor(
-        ps, is_training, int(fe_cfg.first_stage_features_stride), **kwargs)
+        ps, is_training, int(fe_cfg.first_stage_features_stride), **_weight_decay(fe_cfg))
 
 
 def _inception_resnet_v2(ps, fe_cfg, is_training):
@@ -43,11 +42,8 @@ def _inception_resnet_v2(ps, fe_cfg, is_training):
     # stores the flag (models/faster_rcnn_inception_resnet_v2_feature_extractor.py:59) and never reads it — both of its
     # arg scopes force slim.batch_norm(is_training=False) (:105-106, :136-137), so a config with the flag builds the
     # same variables and computes the same losses as one without it.
-    kwargs = {}
-    if fe_cfg.has("weight_decay"):
-        kwargs["weight_decay"] = float(fe_cfg.weight_decay)
     return inception_resnet_v2.FasterRCNNInceptionResnetV2FeatureExtractor(
-        ps, is_training, int(fe_cfg.first_stage_features_stride), **kwargs)
+        ps, is_training, int(fe_cfg.first_stage_features_stride), **_weight_decay(fe_cfg))
 
 
 def _vgg_16(ps, fe_cfg, is_training):
@@ -56,11 +52,9 @@ def _vgg_16(ps, fe_cfg, is_training):
     # Here the class is built as it is defined; the flag's default is accepted and `true` is refused.
     if bool(fe_cfg.batch_norm_trainable):
         raise ValueError("feature_extractor.batch_norm_trainable: true — faster_rcnn_vgg_16 has no BatchNorm")
-    kwargs = {}
-    if fe_cfg.has("weight_decay"):
-        kwargs["weight_decay"] = float(fe_cfg.weight_decay)
     return vgg.FasterRCNNVgg16FeatureExtractor(
-        ps, is_training, int(fe_cfg.first_stage_features_stride), freeze_layer=str(fe_cfg.freeze_layer), **kwargs)
+        ps, is_training, int(fe_cfg.first_stage_features_stride), freeze_layer=str(fe_cfg.freeze_layer),
+        **_weight_decay(fe_cfg))
 
 
 FASTER_RCNN_FEATURE_EXTRACTOR_CLASS_MAP = {

@@ -59,37 +59,75 @@ class _InlineWgrad:
 INLINE_WGRAD = _InlineWgrad()
 
 
-class ConvBN:
-    """slim.conv2d + frozen slim.batch_norm (+ReLU) — slim/nets/resnet_v1.py:102-119."""
+_ACT_EPILOGUE = {None: 0, "relu": ops.EPI_RELU, "relu6": ops.EPI_RELU6, "tanh": ops.EPI_TANH}
 
-    def __init__(self, ps, scope, cin, cout, k, stride=1, dilation=1, padding="SAME",
-                 trainable=True, weight_decay=0.0, eps=1e-5, gamma_init=1.0, relu=True, act=None,
-                 init=("variance_scaling", 2.0, "FAN_IN", False), bn_trainable=False,
-                 weights_name="weights", bn_scale=True):
-        """k: int or (kh, kw). bn_scale=False: slim.batch_norm(scale=False) — no gamma variable
-        (Inception arg scopes); bn_trainable: gamma/beta receive gradients (moving stats never do)."""
-        self.ps, self.scope = ps, scope
-        self.bn_trainable = bn_trainable
-        self.k, self.stride, self.dilation, self.padding, self.eps = k, stride, dilation, padding, eps
-        self.trainable = trainable
-        self.act = act if act is not None else ("relu" if relu else None)     # 'relu' | 'relu6' | None
-        self.relu = self.act is not None
-        kh, kw = k if isinstance(k, tuple) else (k, k)
-        self.w = ps.add(scope + "/" + weights_name, (kh, kw, cin, cout), init, trainable, weight_decay)
-        bn = scope + "/BatchNorm/"
-        self.gamma = (ps.add(bn + "gamma", (cout,), ("uniform", 0.8 * gamma_init, 1.2 * gamma_init), bn_trainable)
-                      if bn_scale else None)
-        self.beta = ps.add(bn + "beta", (cout,), ("uniform", -0.1, 0.1), bn_trainable)
-        self.mean = ps.add(bn + "moving_mean", (cout,), ("uniform", -0.1, 0.1), False)
-        self.var = ps.add(bn + "moving_variance", (cout,), ("uniform", 0.8, 1.2), False)
+
+def act_epilogue(act):
+    """The forward epilogue flag of an output activation: 'relu' | 'relu6' | 'tanh' | None."""
+    return _ACT_EPILOGUE[act]
+
+
+def dgrad_epilogue(residual=None, accum=False, mask_ref=None, mask6=False):
+    """The epilogue flags of an input gradient: + residual, accumulate into `out`, masked by (mask_ref > 0), or by
+    (0 < mask_ref < 6) with mask6."""
+    return ((ops.EPI_RESIDUAL if residual is not None else 0) | (ops.EPI_ACCUM if accum else 0)
+            | ((ops.EPI_MASK6 if mask6 else ops.EPI_MASK) if mask_ref is not None else 0))
+
+
+class Layer:
+    """What every element of `model.layers` is. A subclass registers its variables in __init__ (host
+    only), allocates in prepare(), and supplies geometry() for the one cached desc()."""
+    trainable = False            # the filter `w` (and the bias that goes with it) receives a gradient
+    bn_trainable = False         # gamma / beta receive gradients (the moving statistics never do)
+    gamma = beta = None
+    w_eff = None                 # the filter the kernels read when it is a folded shadow copy of `w`
+    # > 0: this layer's output is a channel slice of a concatenated map with `ldy` channels (set by the owner of the
+    # concat before the first call): forward(out=view) writes it in place, dgrad / wgrad read dy views in place
+    ldy = 0
+
+    def __init__(self):
         self._desc = {}
-        self._kept = {}          # x.data_ptr() -> (Winograd-transformed x, variant), between forward(keep=True) and wgrad
-        self.w_eff = None
-        # > 0: this layer's output is a channel slice of a concatenated map with `ldy` channels (set by the owner of the
-        # concat before the first call): forward(out=view) writes it in place, dgrad / wgrad read dy views in place
-        self.ldy = 0
 
     def prepare(self):
+        """Allocate what depends on the finalized ParamStore (shadow filters, normaliser constants)."""
+
+    def refold(self):
+        """Recompute the normaliser constants after an optimizer step (the CPU path of FasterRCNNMetaArch.refold)."""
+
+    def wgrad(self, x, g):
+        """Accumulate the gradients of the layer's variables and report them final (ParamStore.grad_ready)."""
+
+    def grad_vars(self):
+        """The variables of this layer that receive a gradient: the filter if it trains (a bias trains, and is reported,
+        with its filter), gamma / beta if the normaliser's parameters train."""
+        bn = (self.gamma, self.beta) if self.bn_trainable else ()
+        return tuple(v for v in ((self.w,) if self.trainable else ()) + bn if v is not None)
+
+    def geometry(self):
+        """-> (filter shape [kh, kw, C, K], stride, dilation, padding) of the layer's convolution."""
+        raise NotImplementedError
+
+    def desc(self, shape):
+        d = self._desc.get(tuple(shape))
+        if d is None:
+            d = self._desc[tuple(shape)] = ops.conv_desc(shape, *self.geometry(), ldy=self.ldy)
+        return d
+
+
+class _FrozenBN(Layer):
+    """A filter followed by slim.batch_norm in inference mode, folded (module docstring): the normaliser's variables and
+    constants, stated once for ConvBN and DepthwiseBN."""
+
+    def _add_batch_norm(self, c, gamma_init, bn_scale=True):
+        ps, bn, t = self.ps, self.scope + "/BatchNorm/", self.bn_trainable
+        if bn_scale:
+            self.gamma = ps.add(bn + "gamma", (c,), ("uniform", 0.8 * gamma_init, 1.2 * gamma_init), t)
+        self.beta = ps.add(bn + "beta", (c,), ("uniform", -0.1, 0.1), t)
+        self.mean = ps.add(bn + "moving_mean", (c,), ("uniform", -0.1, 0.1), False)
+        self.var = ps.add(bn + "moving_variance", (c,), ("uniform", 0.8, 1.2), False)
+
+    def prepare(self):
+        """w_eff in the shape the layer's kernels read: `w_eff_shape`."""
         ps = self.ps
         b = ps.value(self.beta.name)
         m, v = ps.value(self.mean.name), ps.value(self.var.name)
@@ -98,10 +136,10 @@ class ConvBN:
                       else self.inv_std.clone()).contiguous()
         self.shift = (b - m * self.scale).contiguous()
         if self.w.trainable:       # refreshed by the batched fold (ops.fold_scales) after each update
-            self.w_eff = ps.register_fold(self.w, self.scale)
+            self.w_eff = ps.register_fold(self.w, self.scale).view(self.w_eff_shape)
         else:
-            self.w_eff = torch.empty(self.w.shape, dtype=f32, device=ps.device)
-            ops.scale_channels(ps.value(self.w.name), self.scale, self.w_eff)
+            self.w_eff = torch.empty(self.w_eff_shape, dtype=f32, device=ps.device)
+            ops.scale_channels(ps.value(self.w.name).view(self.w_eff_shape), self.scale, self.w_eff)
 
     def refold(self):
         _refresh_bn(self)
@@ -115,20 +153,38 @@ class ConvBN:
                                ps.grad(self.gamma.name), ps.grad(self.beta.name), beta=1.0)
             ps.grad_ready(self.gamma, self.beta)
 
-    def desc(self, shape):
-        d = self._desc.get(tuple(shape))
-        if d is None:
-            d = ops.conv_desc(shape, self.w.shape, self.stride, self.dilation, self.padding, ldy=self.ldy)
-            self._desc[tuple(shape)] = d
-        return d
+
+class ConvBN(_FrozenBN):
+    """slim.conv2d + frozen slim.batch_norm (+ReLU) — slim/nets/resnet_v1.py:102-119."""
+
+    def __init__(self, ps, scope, cin, cout, k, stride=1, dilation=1, padding="SAME",
+                 trainable=True, weight_decay=0.0, eps=1e-5, gamma_init=1.0, relu=True, act=None,
+                 init=("variance_scaling", 2.0, "FAN_IN", False), bn_trainable=False,
+                 weights_name="weights", bn_scale=True):
+        """k: int or (kh, kw). bn_scale=False: slim.batch_norm(scale=False) — no gamma variable
+        (Inception arg scopes); bn_trainable: gamma/beta receive gradients (moving stats never do)."""
+        super().__init__()
+        self.ps, self.scope = ps, scope
+        self.bn_trainable = bn_trainable
+        self.k, self.stride, self.dilation, self.padding, self.eps = k, stride, dilation, padding, eps
+        self.trainable = trainable
+        self.act = act if act is not None else ("relu" if relu else None)     # 'relu' | 'relu6' | None
+        self.relu = self.act is not None
+        kh, kw = k if isinstance(k, tuple) else (k, k)
+        self.w = ps.add(scope + "/" + weights_name, (kh, kw, cin, cout), init, trainable, weight_decay)
+        self.w_eff_shape = self.w.shape
+        self._add_batch_norm(cout, gamma_init, bn_scale)
+        self._kept = {}          # x.data_ptr() -> (Winograd-transformed x, variant), between forward(keep=True) and wgrad
+
+    def geometry(self):
+        return self.w.shape, self.stride, self.dilation, self.padding
 
     def forward(self, x, residual=None, relu=None, keep=False, out=None):
         """keep: this forward will be followed by wgrad(x, .) of the same x (training with saved activations) —
         a Winograd layer then keeps its transformed input for the filter gradient.
         out: where to write (required when self.ldy is set: the layer's slice of the concatenated map)."""
         act = self.act if relu is None else ("relu" if relu else None)
-        epi = ops.EPI_BIAS | {None: 0, "relu": ops.EPI_RELU, "relu6": ops.EPI_RELU6}[act] \
-            | (ops.EPI_RESIDUAL if residual is not None else 0)
+        epi = ops.EPI_BIAS | act_epilogue(act) | (ops.EPI_RESIDUAL if residual is not None else 0)
         return ops.conv2d_fwd(self.desc(x.shape), x, self.w_eff, self.shift, residual, epi, out=out,
                               xf_cache=self.ps.filter_cache,
                               keep_input_xf=self._keep_slot() if (keep and self.trainable and self.k == 3) else None)
@@ -147,58 +203,32 @@ class ConvBN:
             self.ps.grad_ready(self.w, self.beta if db is not None else None)
 
     def dgrad(self, x_shape, g, residual=None, mask_ref=None, out=None, accum=False, mask6=False):
-        epi = ((ops.EPI_RESIDUAL if residual is not None else 0) | (ops.EPI_ACCUM if accum else 0)
-               | ((ops.EPI_MASK6 if mask6 else ops.EPI_MASK) if mask_ref is not None else 0))
-        return ops.conv2d_dgrad(self.desc(x_shape), g, self.w_eff, residual, mask_ref, epi, out=out,
-                                xf_cache=self.ps.filter_cache)
+        return ops.conv2d_dgrad(self.desc(x_shape), g, self.w_eff, residual, mask_ref,
+                                dgrad_epilogue(residual, accum, mask_ref, mask6), out=out, xf_cache=self.ps.filter_cache)
 
 
-class DepthwiseBN:
+class DepthwiseBN(_FrozenBN):
     """slim.separable_conv2d(num_outputs=None, depth_multiplier=1) + frozen batch_norm + ReLU6
     (slim/nets/mobilenet_v1.py:229-245). Filter [k,k,C,1] named `depthwise_weights` like slim."""
 
     def __init__(self, ps, scope, c, k=3, stride=1, dilation=1, trainable=True, weight_decay=0.0, eps=1e-3,
-                 act="relu6", init=("truncated_normal", 0.09), bn_trainable=False, gamma_init=1.0):
+                 act="relu6", init=("truncated_normal", 0.09), bn_trainable=False, gamma_init=1.0, batch_norm=True):
+        """batch_norm=False: the bare filter — no normaliser variables; the subclass supplies prepare / forward."""
+        super().__init__()
         self.ps, self.scope, self.c = ps, scope, c
         self.bn_trainable = bn_trainable
         self.k, self.stride, self.dilation, self.eps, self.act = k, stride, dilation, eps, act
         self.trainable = trainable
         self.w = ps.add(scope + "/depthwise_weights", (k, k, c, 1), init, trainable, weight_decay)
-        bn = scope + "/BatchNorm/"
-        self.gamma = ps.add(bn + "gamma", (c,), ("uniform", 0.8 * gamma_init, 1.2 * gamma_init), bn_trainable)
-        self.beta = ps.add(bn + "beta", (c,), ("uniform", -0.1, 0.1), bn_trainable)
-        self.mean = ps.add(bn + "moving_mean", (c,), ("uniform", -0.1, 0.1), False)
-        self.var = ps.add(bn + "moving_variance", (c,), ("uniform", 0.8, 1.2), False)
-        self._desc = {}
+        self.w_eff_shape = (k, k, c)
+        if batch_norm:
+            self._add_batch_norm(c, gamma_init)
 
-    def prepare(self):
-        ps = self.ps
-        g, b = ps.value(self.gamma.name), ps.value(self.beta.name)
-        m, v = ps.value(self.mean.name), ps.value(self.var.name)
-        self.inv_std = torch.rsqrt(v + self.eps)
-        self.scale = (g * self.inv_std).contiguous()
-        self.shift = (b - m * self.scale).contiguous()
-        if self.w.trainable:
-            self.w_eff = ps.register_fold(self.w, self.scale).view(self.k, self.k, self.c)
-        else:
-            self.w_eff = torch.empty((self.k, self.k, self.c), dtype=f32, device=ps.device)
-            ops.scale_channels(ps.value(self.w.name).view(self.k, self.k, self.c), self.scale, self.w_eff)
-
-    bn_grad = ConvBN.bn_grad
-
-    def refold(self):
-        _refresh_bn(self)
-
-    def desc(self, shape):
-        d = self._desc.get(tuple(shape))
-        if d is None:
-            d = ops.conv_desc(shape, (self.k, self.k, self.c, self.c), self.stride, self.dilation, "SAME")
-            self._desc[tuple(shape)] = d
-        return d
+    def geometry(self):
+        return (self.k, self.k, self.c, self.c), self.stride, self.dilation, "SAME"
 
     def forward(self, x):
-        epi = ops.EPI_BIAS | {None: 0, "relu": ops.EPI_RELU, "relu6": ops.EPI_RELU6}[self.act]
-        return ops.depthwise_fwd(self.desc(x.shape), x, self.w_eff, self.shift, epi)
+        return ops.depthwise_fwd(self.desc(x.shape), x, self.w_eff, self.shift, ops.EPI_BIAS | act_epilogue(self.act))
 
     def wgrad(self, x, g):
         if self.trainable:
@@ -207,15 +237,16 @@ class DepthwiseBN:
             self.ps.grad_ready(self.w)
 
     def dgrad(self, x_shape, g, mask_ref=None, mask6=False):
-        epi = (ops.EPI_MASK6 if mask6 else ops.EPI_MASK) if mask_ref is not None else 0
-        return ops.depthwise_dgrad(self.desc(x_shape), g, self.w_eff, mask_ref, epi)
+        return ops.depthwise_dgrad(self.desc(x_shape), g, self.w_eff, mask_ref,
+                                   dgrad_epilogue(None, False, mask_ref, mask6))
 
 
-class Conv:
+class Conv(Layer):
     """slim.conv2d / slim.fully_connected with biases, no normaliser (RPN conv, predictors)."""
 
     def __init__(self, ps, scope, cin, cout, k, init, trainable=True, weight_decay=0.0,
                  activation=None, fc=False, rate=1):
+        super().__init__()
         self.ps, self.scope, self.k, self.trainable, self.activation = ps, scope, k, trainable, activation
         self.rate = rate
         shape = (cin, cout) if fc else (k, k, cin, cout)
@@ -223,29 +254,18 @@ class Conv:
         self.w = ps.add(scope + "/weights", shape, init, trainable, weight_decay)
         self.b = ps.add(scope + "/biases", (cout,), ("zeros",), trainable)
         self.cin, self.cout = cin, cout
-        self._desc = {}
-
-    def prepare(self):
-        pass
-
-    def refold(self):
-        pass
 
     def _w4(self):
         w = self.ps.value(self.w.name)
         return w.view(1, 1, self.cin, self.cout) if self.fc else w
 
-    def desc(self, shape):
-        d = self._desc.get(tuple(shape))
-        if d is None:
-            d = ops.conv_desc(shape, (self.k, self.k, self.cin, self.cout), 1, self.rate, "SAME")
-            self._desc[tuple(shape)] = d
-        return d
+    def geometry(self):
+        return (self.k, self.k, self.cin, self.cout), 1, self.rate, "SAME"
 
     def forward(self, x):
         """x: NHWC, or [rows, cin] for fc=True (treated as rows x 1 x 1 x cin)."""
         x4 = x.view(x.shape[0], 1, 1, self.cin) if self.fc else x
-        epi = ops.EPI_BIAS | {None: 0, "relu": ops.EPI_RELU, "tanh": ops.EPI_TANH}[self.activation]
+        epi = ops.EPI_BIAS | act_epilogue(self.activation)
         y = ops.conv2d_fwd(self.desc(x4.shape), x4, self._w4(), self.ps.value(self.b.name), None, epi,
                            xf_cache=self.ps.filter_cache)
         return y.view(x.shape[0], self.cout) if self.fc else y
@@ -263,10 +283,8 @@ class Conv:
     def dgrad(self, x_shape, g, residual=None, mask_ref=None, out=None, accum=False, mask6=False):
         x4s = (x_shape[0], 1, 1, self.cin) if self.fc else tuple(x_shape)
         g4 = g.view(g.shape[0], 1, 1, self.cout) if self.fc else g
-        epi = ((ops.EPI_RESIDUAL if residual is not None else 0) | (ops.EPI_ACCUM if accum else 0)
-               | ((ops.EPI_MASK6 if mask6 else ops.EPI_MASK) if mask_ref is not None else 0))
-        dx = ops.conv2d_dgrad(self.desc(x4s), g4, self._w4(), residual, mask_ref, epi, out=out,
-                              xf_cache=self.ps.filter_cache)
+        dx = ops.conv2d_dgrad(self.desc(x4s), g4, self._w4(), residual, mask_ref,
+                              dgrad_epilogue(residual, accum, mask_ref, mask6), out=out, xf_cache=self.ps.filter_cache)
         return dx.view(x_shape) if self.fc else dx
 
 
@@ -429,3 +447,61 @@ class BlockStack:
 
     def layers(self):
         return [l for u in self.units for l in u.layers()]
+
+
+class Tower:
+    """The second-stage feature extractor, on RoI crops (under R-FCN: on the whole map) — DESIGN.md §1.1. A subclass
+    sets `cout`, `trainable` and `out_act`, and has layers() -> [Layer] and forward(crops, save) -> (out, ctx)."""
+    supports_wgrad_stream = False     # False: backward runs its filter gradients inline whatever `wgrad` it is given
+    # out_act: the activation `out` went through, 'relu' | 'relu6', or None when it is not an activation of the tower's
+
+    @staticmethod
+    def out_hw(p):
+        """Spatial size of the output for p x p crops."""
+        return (p, p)
+
+    @classmethod
+    def out_mask(cls, feat):
+        """mask_ref / mask6 of a predictor's backward for the features `feat` the tower produced: the tower's output
+        activation fused into the gradient. Without one (`out_act` None) the gradient passes unmasked, through the exact
+        zeros of the output too."""
+        return dict(mask_ref=None if cls.out_act is None else feat, mask6=cls.out_act == "relu6")
+
+    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=INLINE_WGRAD):
+        """g_out: dL/d(out), or dL/d(pre-activation of out) when `masked`. Returns dL/d(crops) or None.
+        `wgrad`: where the filter gradients may run (inline, or a WgradStream the caller joins)."""
+        raise NotImplementedError
+
+
+class FeatureExtractor:
+    """The first-stage trunk and the factory of its towers — DESIGN.md §1.1. A subclass sets `cout` and `out_act` (the
+    activation of the RPN feature map: 'relu' | 'relu6') and has layers(), preprocess(),
+    extract_proposal_features(x, save) -> (features, ctx) and box_classifier_tower(scope, trainable) -> Tower."""
+    supports_wgrad_stream = False     # as Tower's, for backward_proposal_features
+    supports_rfcn = True              # False: RFCNMetaArch refuses the extractor
+    min_image_size = 33               # None: the extractor takes any image size
+    _neg_one = None
+
+    def __init__(self, ps, is_training, first_stage_features_stride, weight_decay):
+        if first_stage_features_stride not in (8, 16):
+            raise ValueError("`first_stage_features_stride` must be 8 or 16.")
+        self.ps, self.is_training, self.weight_decay = ps, is_training, weight_decay
+
+    def check_inputs(self, x):
+        if x.dim() != 4:
+            raise ValueError("`preprocessed_inputs` must be 4 dimensional, got a tensor of shape %s" % (tuple(x.shape),))
+        m = self.min_image_size
+        if m is not None and (x.shape[1] < m or x.shape[2] < m):
+            raise ValueError("image size must at least be %d in both height and width." % m)
+
+    def to_unit_range(self, resized_inputs):
+        """Maps pixel values to [-1, 1]: the preprocess of the MobileNet and Inception-ResNet-v2 extractors."""
+        x = torch.empty_like(resized_inputs)
+        ops.axpby(resized_inputs, x, 2.0 / 255.0, 0.0)
+        if self._neg_one is None:
+            self._neg_one = torch.full((3,), -1.0, dtype=torch.float32, device=x.device)
+        return ops.bias_add_channels(x, self._neg_one)
+
+    def backward_proposal_features(self, gp, ctx, wgrad=INLINE_WGRAD):
+        """gp: dL/d(pre-activation of the RPN feature map) (already masked by `out_act`). `wgrad`: as Tower.backward's."""
+        raise NotImplementedError

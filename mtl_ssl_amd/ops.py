@@ -1552,7 +1552,7 @@ class BnRefreshTable:
     (the tensors they point to live as long as the model)."""
 
     def __init__(self, layers, device):
-        self.layers = [l for l in layers if getattr(l, "bn_trainable", False)]
+        self.layers = [l for l in layers if l.beta in l.grad_vars()]
         self.n = len(self.layers)
         if not self.n:
             return

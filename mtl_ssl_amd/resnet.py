@@ -13,9 +13,11 @@ RESNET_UNITS = {"resnet_v1_50": (3, 4, 6, 3), "resnet_v1_101": (3, 4, 23, 3),
                 "resnet_v1_152": (3, 8, 36, 3)}
 
 
-class BoxClassifierTower:
+class BoxClassifierTower(nn.Tower):
     """block4 applied to ROI crops (models/...resnet...:148-185), one weight copy per scope
-    (SecondStageFeatureExtractor / ClosenessBoxPredictor / WindowBoxPredictor)."""
+    (SecondStageFeatureExtractor / ClosenessBoxPredictor / WindowBoxPredictor). It runs at stride 1: out_hw(p) = (p, p)."""
+    out_act = "relu"
+    supports_wgrad_stream = True
 
     def __init__(self, ps, scope, arch, cin, trainable, weight_decay, bn_trainable=False):
         self.stack = nn.BlockStack(ps, "%s/%s" % (scope, arch), cin,
@@ -26,19 +28,12 @@ class BoxClassifierTower:
     def layers(self):
         return self.stack.layers()
 
-    @staticmethod
-    def out_hw(p):
-        """Spatial size of the tower's output for p x p crops (block4 runs at stride 1)."""
-        return (p, p)
-
     def forward(self, crops, save):
         x, ctxs = crops, []
         for u in self.stack.units:
             x, c = u.forward(x, save)
             ctxs.append(c)
         return x, (ctxs if save else None)
-
-    supports_wgrad_stream = True
 
     def backward(self, g_out, out, ctxs, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD):
         """g_out: dL/d(out) (post-ReLU), or dL/d(pre-activation) when `masked`. Returns
@@ -52,21 +47,21 @@ class BoxClassifierTower:
         return gp
 
 
-class FasterRCNNResnetV1FeatureExtractor:
+class FasterRCNNResnetV1FeatureExtractor(nn.FeatureExtractor):
     channel_means = (123.68, 116.779, 103.939)
+    out_act = "relu"
     supports_wgrad_stream = True       # backward_proposal_features(..., wgrad=) can run filter gradients on a side stream
 
     def __init__(self, ps, architecture, is_training, first_stage_features_stride=16,
                  weight_decay=0.0, freeze_layer="block1", batch_norm_trainable=False,
                  first_stage_scope="FirstStageFeatureExtractor"):
-        if first_stage_features_stride not in (8, 16):
-            raise ValueError("`first_stage_features_stride` must be 8 or 16.")
+        super().__init__(ps, is_training, first_stage_features_stride, weight_decay)
         # models/faster_rcnn_resnet_v1_feature_extractor.py:131,169 -> resnet_arg_scope(batch_norm_trainable=
         # is_training and batch_norm_trainable) (slim/nets/resnet_utils.py:203-237): gamma / beta of EVERY BatchNorm of the
         # extractor become trainable variables — the frozen root conv and frozen blocks included, only their filters are
         # frozen — while the normaliser keeps its moving statistics (is_training=False, :138, :171)
         self.bn_trainable = bool(batch_norm_trainable) and bool(is_training)
-        self.ps, self.arch, self.is_training, self.weight_decay = ps, architecture, is_training, weight_decay
+        self.arch = architecture
         n_freeze = int(freeze_layer[-1]) if freeze_layer else 0
         bt = [False] * n_freeze + [bool(is_training)] * (4 - n_freeze)
         units = RESNET_UNITS[architecture]
@@ -99,11 +94,7 @@ class FasterRCNNResnetV1FeatureExtractor:
         return ops.bias_add_channels(resized_inputs, self._neg_means)
 
     def extract_proposal_features(self, x, save=True):
-        if x.dim() != 4:
-            raise ValueError("`preprocessed_inputs` must be 4 dimensional, got a tensor of shape %s"
-                             % (tuple(x.shape),))
-        if x.shape[1] < 33 or x.shape[2] < 33:
-            raise ValueError("image size must at least be 33 in both height and width.")
+        self.check_inputs(x)
         y1 = self.conv1.forward(x)
         x, pads = ops.maxpool_fwd(y1, 3, 2, "SAME")
         ctxs = []

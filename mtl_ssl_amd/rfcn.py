@@ -80,7 +80,7 @@ class RfcnBoxPredictor:
 
 class RFCNMetaArch(FasterRCNNMetaArch):
     def __init__(self, ps, is_training, frcnn, mtl, feature_extractor, seed=0):
-        if not getattr(feature_extractor, "supports_rfcn", True):
+        if not feature_extractor.supports_rfcn:
             # R-FCN runs the extractor's second-stage tower once on the whole map (block4 at stride 16); an extractor
             # whose tower is the identity would put reduce_depth straight on the RPN's map — not built, not tested
             raise ValueError("rfcn_box_predictor with feature_extractor %s is not built: its second-stage tower is the "
@@ -202,13 +202,13 @@ class RFCNMetaArch(FasterRCNNMetaArch):
         # step at that join, `whole_step.main_stream_joins`). Same-box A/B, three passes: 35.12 -> 34.79 ms/step
         # (profiles/r06_rfcn_tower_wgrad_ab.txt); the main tower's own filter gradients there as well: no gain (35.16), so
         # they stay inline. (Faster R-CNN's aux towers — stop_gradient, nobody waits for them — lose with it.)
-        awg = dict(wgrad=self._wgrad_exec()) if getattr(self.tower, "supports_wgrad_stream", False) else {}
+        awg = self._wgrad_exec()
 
         def aux_backward():
             if mtl.closeness and not shared:
                 cfeat = pd["_cfeat"]
                 g = self.closeness_predictor.backward(pd["_cp"], d["closeness_predictions"], None, cfeat)
-                g_c = self.closeness_tower.backward(g, cfeat, pd["_cctx"], need_input_grad=not stop, **awg)
+                g_c = self.closeness_tower.backward(g, cfeat, pd["_cctx"], need_input_grad=not stop, wgrad=awg)
                 if not stop:
                     held.append(g_c)
             if mtl.window:                        # behind the closeness tower, on the same stream
@@ -217,11 +217,10 @@ class RFCNMetaArch(FasterRCNNMetaArch):
                     self.window_predictor.backward(pd["_wp"], d["window_class_predictions"], None, wfeat,
                                                    need_feat_grad=False)
                     for l in self.window_tower.layers():       # their gradient is final: zero (only weight decay acts)
-                        self.ps.grad_ready(l.w if l.trainable else None,
-                                           *((l.gamma, l.beta) if getattr(l, "bn_trainable", False) else ()))
+                        self.ps.grad_ready(*l.grad_vars())
                     return
                 g = self.window_predictor.backward(pd["_wp"], d["window_class_predictions"], None, wfeat)
-                g_w = self.window_tower.backward(g, wfeat, pd["_wctx"], need_input_grad=not stop, **awg)
+                g_w = self.window_tower.backward(g, wfeat, pd["_wctx"], need_input_grad=not stop, wgrad=awg)
                 if not stop:
                     held.append(g_w)
 

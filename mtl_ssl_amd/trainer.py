@@ -333,8 +333,7 @@ class Trainer:
         # normaliser without gamma whose beta alone trains (Inception-ResNet-v2's slim.batch_norm(scale=False): the folded
         # scale is 1/sqrt(var + eps), a constant; beta only moves the shift, which bn_refresh recomputes)
         self.fuse_fold = (os.environ.get("MTLSSL_FUSE_FOLD", "1") != "0"
-                          and not any(getattr(l, "bn_trainable", False) and getattr(l, "gamma", None) is not None
-                                      for l in model.layers))
+                          and not any(l.gamma in l.grad_vars() for l in model.layers))
         # with a communicator the clip + momentum update runs per gradient bucket, right behind that bucket's all-reduce
         # (GradientReducer.finish_by_bucket): the step no longer ends with "last all-reduce -> norms over all 78 M
         # parameters -> update over all of them" in series. Same arithmetic per variable: bit-identical weights.

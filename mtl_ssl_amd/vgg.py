@@ -29,12 +29,11 @@ def trainable_groups(freeze_layer, is_training):
     return [bool(is_training) and g > n for g in range(1, len(_GROUPS) + 1)]
 
 
-class IdentityTower:
+class IdentityTower(nn.Tower):
     """models/faster_rcnn_vgg_16_feature_extractor.py:76-81: `_extract_box_classifier_features` is tf.identity. No
     variables; the output is NOT an activation of the tower's own (`out_act` None): it is a bilinear crop of a ReLU map,
     full of exact zeros through which the predictor's gradient must pass."""
     out_act = None
-    out_relu6 = False
     trainable = False
 
     def __init__(self, cin):
@@ -43,28 +42,22 @@ class IdentityTower:
     def layers(self):
         return []
 
-    @staticmethod
-    def out_hw(p):
-        return (p, p)
-
     def forward(self, crops, save):
         return crops, None
 
-    def backward(self, g_out, out, ctx, need_input_grad, masked=False):
+    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD):
         return g_out if need_input_grad else None
 
 
-class FasterRCNNVgg16FeatureExtractor:
+class FasterRCNNVgg16FeatureExtractor(nn.FeatureExtractor):
     channel_means = (102.9801, 115.9465, 122.7717)         # Caffe's, per BGR channel (:43-49)
-    output_relu6 = False
+    out_act = "relu"
     supports_rfcn = False          # RFCNMetaArch refuses an extractor whose second-stage tower is the identity
 
     def __init__(self, ps, is_training, first_stage_features_stride=16, weight_decay=0.0005, freeze_layer="",
                  first_stage_scope="FirstStageFeatureExtractor"):
-        if first_stage_features_stride not in (8, 16):
-            raise ValueError("`first_stage_features_stride` must be 8 or 16.")
         # the stride is checked and otherwise unused (:86-108): the trunk is always conv5_3 at stride 16
-        self.ps, self.is_training, self.weight_decay = ps, bool(is_training), weight_decay
+        super().__init__(ps, bool(is_training), first_stage_features_stride, weight_decay)
         self.group_trainable = trainable_groups(freeze_layer, is_training)
         self.groups = []
         cin = 3
@@ -92,10 +85,7 @@ class FasterRCNNVgg16FeatureExtractor:
     def extract_proposal_features(self, x, save=True):
         """-> (conv5_3 after its ReLU, ctx). ctx, kept only for the trainable groups: per group (the inputs of its
         convolutions, its last activation, the pooled map, the pool's pads)."""
-        if x.dim() != 4:
-            raise ValueError("`preprocessed_inputs` must be 4 dimensional, got a tensor of shape %s" % (tuple(x.shape),))
-        if x.shape[1] < 33 or x.shape[2] < 33:
-            raise ValueError("image size must at least be 33 in both height and width.")
+        self.check_inputs(x)
         ctx = []
         for g, convs in enumerate(self.groups):
             keep = save and self.is_training and g >= self.first_trainable
@@ -110,10 +100,11 @@ class FasterRCNNVgg16FeatureExtractor:
             ctx.append((xs, last, pooled, pads) if keep else None)
         return x, (ctx if save else None)
 
-    def backward_proposal_features(self, gp, ctx):
+    def backward_proposal_features(self, gp, ctx, wgrad=nn.INLINE_WGRAD):
         """gp: dL/d(pre-activation of conv5_3) (already ReLU-masked). Inside a group the dgrad epilogue masks by the
         input activation. Across a pool the next group's first dgrad is masked by the POOLED map — it is positive exactly
-        where the element that receives the gradient is — and the plain max-pool backward routes it."""
+        where the element that receives the gradient is — and the plain max-pool backward routes it. The filter gradients
+        run inline, whatever `wgrad` is."""
         if not self.is_training:
             return
         for g in range(len(self.groups) - 1, self.first_trainable - 1, -1):

@@ -146,3 +146,35 @@ def test_split_loss_equals_whole_loss_bit_for_bit(cfg_name, refined_weight, monk
         del tr, model
     assert res["1"][0] == res["0"][0]
     assert torch.equal(res["1"][1], res["0"][1])
+
+
+@pytest.mark.parametrize("cfg_name", ["smoke_mobilenet_v1_mtl.config", os.path.join("vgg16", "smoke_vgg16_mtl.config")])
+def test_extractors_that_ignore_the_wgrad_stream_do_not_change_a_bit_with_it(cfg_name, monkeypatch):
+    """MobileNet-v1 and VGG-16 (extractor and tower) take the filter-gradient executor like every family and run their
+    filter gradients inline. MTLSSL_WGRAD_STREAM=1 hands them a real nn.WgradStream: every variable's gradient still
+    comes from the same launches in the same order — only the three head filter gradients move to the side stream — so
+    losses and gradients are bit-identical to the default (inline) schedule: no tolerance."""
+    import __graft_entry__ as g
+    g.build()
+    from mtl_ssl_amd import config, model_builder, nn, synthetic, trainer
+    cfg = config.parse_pipeline_config(open(os.path.join(ROOT, "configs", cfg_name)).read())
+    K = int(cfg.model.faster_rcnn.num_classes)
+    res = {}
+    for mode in (None, "1"):
+        if mode is None:
+            monkeypatch.delenv("MTLSSL_WGRAD_STREAM", raising=False)
+        else:
+            monkeypatch.setenv("MTLSSL_WGRAD_STREAM", mode)
+        model = model_builder.build(cfg.model, True, "cuda", seed=5)
+        assert isinstance(model._wgrad_exec(), nn.WgradStream) == (mode == "1")
+        tr = trainer.Trainer(model, cfg.train_config, 1)
+        batch = tr.stage_batch(synthetic.make_batch(2, 160, 224, K, seed=21, device="cuda", max_gt=4, num_windows=6))
+        tr.forward_backward(batch)
+        loss_dict = tr.forward_backward(batch)
+        losses = {k: float(v.item()) for k, v in loss_dict.items()}
+        torch.cuda.synchronize()
+        res[mode] = (losses, model.ps.grads.clone())
+        del tr, model
+    assert float(res[None][1].abs().sum()) > 0
+    assert res[None][0].keys() == res["1"][0].keys() and res[None][0] == res["1"][0]
+    assert torch.equal(res[None][1], res["1"][1])

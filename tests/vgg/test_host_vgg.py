@@ -120,11 +120,11 @@ def test_rfcn_with_the_identity_tower_is_refused():
 
 def test_tower_output_mask_follows_the_towers_activation():
     """The predictors' backward masks by the tower's output only when that output is an activation of the tower."""
-    from mtl_ssl_amd import frcnn, mobilenet, resnet, vgg
+    from mtl_ssl_amd import mobilenet, resnet, vgg
     feat = object()
-    assert frcnn._out_mask(vgg.IdentityTower(512), feat) == dict(mask_ref=None, mask6=False)
-    assert frcnn._out_mask(resnet.BoxClassifierTower, feat) == dict(mask_ref=feat, mask6=False)
-    assert frcnn._out_mask(mobilenet.MobilenetTower, feat) == dict(mask_ref=feat, mask6=True)
+    assert vgg.IdentityTower(512).out_mask(feat) == dict(mask_ref=None, mask6=False)
+    assert resnet.BoxClassifierTower.out_mask(feat) == dict(mask_ref=feat, mask6=False)
+    assert mobilenet.MobilenetTower.out_mask(feat) == dict(mask_ref=feat, mask6=True)
     t = vgg.IdentityTower(512)
     assert t.layers() == [] and t.out_hw(7) == (7, 7) and t.cout == 512
     x = torch.zeros(2, 7, 7, 512)
