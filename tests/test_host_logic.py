@@ -673,7 +673,7 @@ def test_gpu_suite_order_keeps_kernel_parity_ahead_of_whole_model_cases():
     small_model = {"test_gpu_model", "test_gpu_rfcn", "test_gpu_switches", "test_gpu_multi_rank", "test_gpu_data_parallel"}
     last = {"test_gpu_fullsize_configs", "test_gpu_fullsize", "test_gpu_determinism", "test_gpu_end_to_end", "test_gpu_bench_contract"}
     unnamed = {"test_gpu_plan_table", "test_gpu_head_kernels", "test_gpu_spatial_kernels", "test_gpu_offtable_plans",
-               "test_gpu_option_kernels"}   # not in conftest's _ORDER: the slot after the small models
+               "test_gpu_option_kernels", "test_gpu_fullsize_plans"}   # not in conftest's _ORDER: the slot after the small models
     assert {mod(i) for i in ids} == kernel_modules | small_model | last | {"test_gpu_fullsize_parity"} | unnamed
     first = lambda pred: next(n for n, i in enumerate(ids) if pred(i))
     lastidx = lambda pred: max(n for n, i in enumerate(ids) if pred(i))

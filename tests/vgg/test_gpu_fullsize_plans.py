@@ -1,0 +1,319 @@
+"""Every convolution the Faster R-CNN VGG-16 configuration launches, at the size production runs it, on an MI355X against
+float64: one case per entry of tests/golden/vgg16_conv_problems.json (tools/vgg16_plan_sweep.py; tests/vgg/test_host_plans.py
+keeps the fixture equal to the sweep on a CPU) — the `production` list, every (problem, mode) of one training step of
+configs/vgg16/frcnn_vgg16_voc_mtl.config at 600x1024 and batch 1 under freeze_layer 'conv2' and '', and the
+`representatives`, the cheapest problem of every plan signature other frames or batch 2 reach and nothing else shows.
+
+Each case first asks the planner (ops.conv_plan_info) and requires the recorded signature, so it cannot pass by running
+another plan; then it makes the call the way tests/test_gpu_plan_table.py does (post-ReLU-like x, zero-mean dy, forward
+with bias and residual, dgrad with residual accumulated into previous contents, wgrad with out_scale, dbias and beta = 1)
+and compares sampled outputs with the float64 references of tests/conv_ref.py in units of 2^-24 * (sum |a*b| + |addends|):
+at most 8 for a direct, padded, thin or valu_fallback plan, 400 for a Winograd plan, 8 for the bias gradient. The reference
+samples outputs and never shortens a reduction. Rows: tests/conv_ref.py _rows plus the K-split tail boundaries and the last
+partial Winograd tile (tests/test_gpu_offtable_plans.py _extra_rows); the FC problems have at most 640 rows and every one is
+compared. Where C = 25 088 or K = 4096 the reference is built on a sample of at least 64 output columns, tile boundaries
+included (a float64 copy of the 25 088 x 4096 filter is 822 MB); the filter gradient is sampled by channel blocks as for
+every other layer. After conv1_1's forward — the VALU fallback indexed per element, on the largest map of the project — the
+whole last row and last column of the frame and its corners are compared as well. The ReLU forward epilogue and the
+ReLU-mask dgrad epilogue must be exact functions of the linear result, a second call must give the same bits, and every
+output must be finite under the NaN-poisoned workspaces (conftest: MTLSSL_POISON_WS).
+
+test_one_step_launches_the_production_list builds the full configuration, runs one Trainer.forward_backward at 600x1024 and
+requires that the (mode, problem) set the step launched is the fixture's production list for freeze_layer 'conv2': the host
+enumeration cannot miss a launch without this suite noticing."""
+import importlib.util
+import json
+import os
+import time
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+from tests import parity_report
+from tests.conv_ref import (DIRECT_BOUND, ROWS, WINO_BOUND, _channels, _dgrad_reference, _fwd_reference, _rows,
+                            _wgrad_reference)
+from tests.parity_report import dot_err
+from tests.test_gpu_offtable_plans import _extra_rows
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+MODE_NAMES = ("fwd", "dgrad", "wgrad")
+COLS = 64                       # sampled output columns of the wide FC layers
+# The FC reductions of this configuration are the longest in the project: 25 088 terms, 392 K-steps folded from up to 8
+# splits (the plan table's longest is a few thousand terms). Measured on an MI355X, in 2^-24 * sum|ab| units, worst over
+# the compared outputs (every row, 64 columns), kernel / a torch CPU float32 matmul of the same operands on the same outputs:
+#   25 088 -> 4096 forward   64 rows (K split 8)  0.76 / 0.23      264 rows (K split 4, partial tile)  1.30 / 0.34
+#   25 088 -> 4096 dgrad     64 rows (K split 3, ragged)  1.12 / 0.35      128 rows                     1.04 / 0.38
+#    4096 -> 4096  forward   64 rows (K split 8)  0.66 / 0.41      264 rows (K split 4, partial tile)  1.11 / 0.43
+#    4096 -> 4096  dgrad     64 rows (K split 8)  0.67 / 0.37
+# The kernel is well inside DIRECT_BOUND (the zero-mean filter keeps the partial sums far below sum|ab|), so these cases are
+# held to it like every other direct plan; each run prints both figures again and the parity report carries them.
+FC_BOUND = DIRECT_BOUND
+
+
+def _tool():
+    spec = importlib.util.spec_from_file_location("vgg16_plan_sweep", os.path.join(ROOT, "tools", "vgg16_plan_sweep.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+TOOL = _tool()
+FIXTURE = json.load(open(TOOL.FIXTURE))
+CASES = [(name, tuple(e["descriptor"]), e["mode"], e["signature"])
+         for name in ("production", "representatives") for e in FIXTURE[name]]
+_RUN = {}                       # (list, problem, mode) -> (family, worst error)
+_FC = {}                        # (problem, mode) -> (kernel error, torch CPU float32 error) of the long FC reductions
+_T0 = [None]
+
+
+def _pid(name, prob, mode):
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    return "%s-%s-%dx%dx%dx%d-k%d-%dx%d" % (name[:4], MODE_NAMES[mode], N, H, W, C, K, R, S)
+
+
+@pytest.fixture(scope="module")
+def ops():
+    import __graft_entry__ as g
+    g.build()
+    from mtl_ssl_amd import ops
+    assert torch.cuda.is_available()
+    assert ops.POISON_WS, "the suite runs with NaN-poisoned workspaces (tests/conftest.py)"
+    assert not [k for k in TOOL.PLANNING_SWITCHES if k in os.environ], "a planning switch is set"
+    prev = ops.set_fp32_engine(0)
+    ops.reset_tuning(use_plan_db=True, autotune=False)
+    _T0[0] = time.time()
+    yield ops
+    ops.set_fp32_engine(prev)
+    ops.reset_tuning()
+    torch.cuda.empty_cache()
+    _report()
+
+
+def _signature(ops, prob, mode):
+    return json.loads(json.dumps(TOOL.signature(ops, prob, mode)))
+
+
+def _is_fc(prob):
+    return prob[1:3] == (1, 1) and prob[5:9] == (1, 1, 1, 1)
+
+
+def _wide_fc(prob):
+    """The layers whose float64 filter does not fit a few seconds: FC_0_4096 (25 088 -> 4096) and FC_1_4096 (4096 -> 4096)."""
+    return _is_fc(prob) and (prob[3] == 25088 or prob[4] == 4096)
+
+
+def _sample_rows(ops, prob, mode, n_img, hs, ws, rng):
+    if _is_fc(prob):
+        assert n_img <= 640
+        return np.arange(n_img)                                         # every row of an FC problem
+    extra = _extra_rows(ops, prob, mode, n_img, hs, ws)
+    assert len(extra) <= ROWS // 2
+    base = _rows(n_img, hs, ws, rng, n=ROWS - len(extra))
+    return np.array(sorted(set(base.tolist()) | extra), np.int64)
+
+
+def _columns(prob, width, rng):
+    """Output columns the reference is built on: all of them, or for the wide FC layers COLS of them — the 64 / 128 /
+    256 tile boundaries, the last column, the rest at random."""
+    if not _wide_fc(prob) or width <= COLS:
+        return np.arange(width)
+    cols = _channels(width, rng, n=COLS)
+    assert len(cols) >= COLS and {0, 63, 64, 127, 128, 255, 256, width - 1} <= set(cols.tolist())
+    return cols
+
+
+def _frame_edge_rows(OH, OW):
+    """conv1_1: three corners of the frame and its whole last row and last column (the fourth corner is on both)."""
+    pick = {0, OW - 1, (OH - 1) * OW}
+    pick.update((OH - 1) * OW + x for x in range(OW))
+    pick.update(y * OW + OW - 1 for y in range(OH))
+    return np.array(sorted(pick), np.int64)
+
+
+def _inputs(prob):
+    N, H, W, C, K, R, S, OH, OW = prob[:9]
+    seed = zlib.crc32(repr(prob).encode())
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    x = rand(N, H, W, C) * 2 - 0.6                                      # post-ReLU-like: mostly positive
+    w = (rand(R, S, C, K) - 0.5) * (2.0 / np.sqrt(R * S * C))
+    dy = rand(N, OH, OW, K) - 0.5                                       # zero-mean
+    return np.random.default_rng(seed), rand, x, w, dy
+
+
+def test_fixture_is_parametrized_whole():
+    c = FIXTURE["counts"]
+    assert len(CASES) == c["production"] + c["representatives"] and c["production"] > 0 and c["representatives"] > 0
+    assert len({(p, m) for _, p, m, _ in CASES}) == len(CASES)
+    reps = [json.dumps(s) for name, _, _, s in CASES if name == "representatives"]
+    assert len(set(reps)) == len(reps)                                  # one representative per signature
+    assert not set(reps) & {json.dumps(s) for name, _, _, s in CASES if name == "production"}
+
+
+@pytest.mark.parametrize("name,prob,mode,want", CASES, ids=[_pid(n, p, m) for n, p, m, _ in CASES])
+def test_vgg16_plan_matches_float64(ops, name, prob, mode, want):
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    d = TOOL.desc_of(prob)
+    rng, rand, x, w, dy = _inputs(prob)
+    sig = _signature(ops, prob, mode)
+    assert sig == want, ("the planner no longer gives this case the plan it stands for", sig, want)
+    wino = sig[1].startswith("winograd")
+    cpu32 = None
+
+    if mode == 0:
+        bias, res = rand(K) - 0.5, rand(N, OH, OW, K) - 0.5
+        epi = ops.EPI_BIAS | ops.EPI_RESIDUAL
+        rows = _sample_rows(ops, prob, mode, N, OH, OW, rng)
+        cols = _columns(prob, K, rng)
+        rows_t, cols_t = torch.from_numpy(rows).cuda(), torch.from_numpy(cols).cuda()
+        sel = lambda t: t.reshape(-1, K)[rows_t][:, cols_t]
+        w_sub = w[..., cols_t]
+        addend = [bias[cols_t].double().cpu()[None, :], sel(res).double().cpu()]
+        sub = prob[:4] + (len(cols),) + prob[5:]                        # the same geometry on the sampled columns
+        reference = lambda r: _fwd_reference(sub, x, w_sub.double().cpu(), r)
+        ref, mag = reference(rows)
+        if _wide_fc(prob):                                              # the same outputs by a torch CPU float32 matmul
+            cpu32 = dot_err(x.reshape(N, C)[rows_t].cpu() @ w_sub.reshape(C, -1).cpu(), ref, mag)
+        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
+        call = lambda e=epi: ops.conv2d_fwd(d, x, w, bias, res, e)
+        y = call()
+        got, outs = [(sel(y), ref, mag)], (y,)
+        if C == 3:                                                      # conv1_1: the frame's border, element by element
+            edge = _frame_edge_rows(OH, OW)
+            edge_t = torch.from_numpy(edge).cuda()
+            eref, emag = reference(edge)
+            ea = [bias.double().cpu()[None, :], res.reshape(-1, K)[edge_t].double().cpu()]
+            e_edge = dot_err(y.reshape(-1, K)[edge_t], eref + ea[0] + ea[1], emag + ea[0].abs() + ea[1].abs())
+            print("%s: last row, last column and corners of the frame (%d pixels): %.2f" % (_pid(name, prob, mode), len(edge), e_edge))
+            assert e_edge <= DIRECT_BOUND, ("conv1_1 frame border", e_edge)
+    elif mode == 1:
+        resd, prev, mask = rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5
+        epi = ops.EPI_RESIDUAL | ops.EPI_ACCUM
+        rows = _sample_rows(ops, prob, mode, N, H, W, rng)
+        cols = _columns(prob, C, rng)
+        rows_t, cols_t = torch.from_numpy(rows).cuda(), torch.from_numpy(cols).cuda()
+        sel = lambda t: t.reshape(-1, C)[rows_t][:, cols_t]
+        sub = prob[:3] + (len(cols),) + prob[4:]                        # the same geometry on the sampled columns
+        ref, mag = _dgrad_reference(sub, dy, w[:, :, cols_t, :].double().cpu(), rows)
+        if _wide_fc(prob):                                              # the same outputs by a torch CPU float32 matmul
+            cpu32 = dot_err(dy.reshape(N, K)[rows_t].cpu() @ w.reshape(C, K)[cols_t].t().cpu(), ref, mag)
+        addend = [sel(t).double().cpu() for t in (resd, prev)]
+        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
+
+        def call(e=epi, m=None):
+            dx = prev.clone()
+            ops.conv2d_dgrad(d, dy, w, resd, m, e, out=dx)
+            return dx
+        dx = call()
+        got, outs = [(sel(dx), ref, mag)], (dx,)
+    else:
+        scale, dw_old, db_old = rand(K) + 0.5, rand(R, S, C, K) - 0.5, rand(K) - 0.5
+        cs, ks = _channels(C, rng), _channels(K, rng)
+        cs_t, ks_t = torch.from_numpy(cs).cuda(), torch.from_numpy(ks).cuda()
+        dy_sub = dy[..., ks_t].double().cpu()
+        ref, mag = _wgrad_reference(prob, x[..., cs_t].double().cpu(), dy_sub)
+        s64, dw0 = scale[ks_t].double().cpu(), dw_old[:, :, cs_t][..., ks_t].double().cpu()
+        db0 = db_old[ks_t].double().cpu()
+
+        def call():
+            dw, db = dw_old.clone(), db_old.clone()
+            ops.conv2d_wgrad(d, x, dy, dw, out_scale=scale, dbias=db, beta=1.0)
+            return dw, db
+        dw, db = call()
+        got = [(dw[:, :, cs_t][..., ks_t], dw0 + s64 * ref, dw0.abs() + s64.abs() * mag),
+               (db[ks_t], db0 + dy_sub.sum((0, 1, 2)), db0.abs() + dy_sub.abs().sum((0, 1, 2)))]
+        outs = (dw, db)
+
+    assert _signature(ops, prob, mode) == want, "the plan changed with the first call"
+    for t in outs:
+        assert bool(torch.isfinite(t).all()), ("non-finite output (a poisoned workspace leaked?)", MODE_NAMES[mode], sig)
+    errs = [dot_err(*g) for g in got]
+    first = WINO_BOUND if wino else (FC_BOUND if _wide_fc(prob) else DIRECT_BOUND)
+    lims = [first] + [DIRECT_BOUND] * (len(errs) - 1)                   # the bias gradient is a plain column sum
+    print("%s %s: errors %s of %s (2^-24 * sum|ab| units)%s" % (
+        _pid(name, prob, mode), sig[1], ["%.2f" % e for e in errs], lims,
+        "" if cpu32 is None else "; torch CPU float32 on the same outputs %.2f" % cpu32))
+    _RUN[(name, prob, mode)] = (sig[1], errs[0])
+    if cpu32 is not None:
+        _FC[(prob, mode)] = (errs[0], cpu32)
+    assert all(e <= lim for e, lim in zip(errs, lims)), (MODE_NAMES[mode], sig, errs, lims)
+
+    # a second call gives the same bits (the K-split fold and the Winograd transforms sum in a fixed order)
+    again = call()
+    for a, b in zip(again if mode == 2 else (again,), outs):
+        assert torch.equal(a, b), ("two calls differ", MODE_NAMES[mode], sig)
+    del again
+    # the nonlinear epilogues are exact functions of the linear result
+    if mode == 0:
+        assert torch.equal(call(epi | ops.EPI_RELU), torch.relu(y)), ("forward ReLU epilogue", sig)
+    if mode == 1:
+        dm = call(epi | ops.EPI_MASK, mask)
+        assert torch.equal(dm, torch.where(mask > 0, dx, torch.zeros_like(dx))), ("dgrad mask epilogue", sig)
+
+
+def test_one_step_launches_the_production_list(ops):
+    """One Trainer.forward_backward of the full configuration at 600x1024, batch 1, plan table on, tuner off: the keys of
+    ops._tuned — every (mode, problem) the step launched — are the fixture's production pairs for freeze_layer 'conv2'."""
+    from mtl_ssl_amd import config, model_builder, synthetic, trainer
+    want = {(e["mode"],) + tuple(e["descriptor"]) for e in FIXTURE["production"] if "conv2" in e["freeze_layers"]}
+    assert len(want) > 40
+    cfg = config.parse_pipeline_config(open(TOOL.CONFIG).read())
+    assert str(cfg.model.faster_rcnn.feature_extractor.freeze_layer) == "conv2"
+    dev = torch.device("cuda", 0)
+    t0 = time.time()
+    # what a step launches does not depend on the weights: the six 25 088 x 4096 / 4096 x 4096 matrices (18 s of host
+    # truncated-normal draws) are tiled from one 2^20-element block of the same distribution; everything else initialises
+    # as in production
+    block = (np.random.default_rng(0).standard_normal(1 << 20).clip(-2, 2) * 0.01).astype(np.float32)
+    values = {s.name: np.resize(block, s.shape) for s in model_builder.variable_specs(cfg.model, True) if s.size >= 1 << 24}
+    assert len(values) == 6, sorted(values)
+    model = model_builder.build(cfg.model, True, dev, seed=0, values=values)
+    tr = trainer.Trainer(model, cfg.train_config, 1)
+    torch.cuda.synchronize()
+    t_build = time.time() - t0
+    batch = synthetic.make_batch(1, 600, 1024, int(cfg.model.faster_rcnn.num_classes), seed=1234, device=dev)
+    ops.reset_tuning(use_plan_db=True, autotune=False)
+    try:
+        t0 = time.time()
+        losses = tr.forward_backward(batch)
+        torch.cuda.synchronize()
+        t_step = time.time() - t0
+        launched = set(ops._tuned)
+        model.check_device_flags()
+        assert all(bool(torch.isfinite(v).all()) for v in losses.values()), losses
+    finally:
+        ops.reset_tuning(use_plan_db=True, autotune=False)
+        del tr, model, batch
+        torch.cuda.empty_cache()
+    line = ("vgg16 full configuration: one step at 600x1024 launched %d (mode, problem) pairs, the host enumeration lists %d; "
+            "model build %.2f s, first forward_backward %.2f s" % (len(launched), len(want), t_build, t_step))
+    print(line)
+    parity_report.add(line)
+    assert launched == want, ("launched, not enumerated", sorted(launched - want), "enumerated, not launched", sorted(want - launched))
+
+
+def _report():
+    if not _RUN:
+        return
+    c = FIXTURE["counts"]
+    parity_report.add("vgg16 plans at full size (%d production pairs, %d representatives; %d signatures reached, %d covered by the "
+                      "plan table or the off-table fixture); per family (fwd / dgrad / wgrad):" % (
+                          sum(1 for k in _RUN if k[0] == "production"), sum(1 for k in _RUN if k[0] == "representatives"),
+                          c["signatures_reached"], c["signatures_covered_by_table_or_offtable"]))
+    fams = {}
+    for (name, prob, mode), (fam, err) in _RUN.items():
+        f = fams.setdefault(fam, [[0, 0.0], [0, 0.0], [0, 0.0]])
+        f[mode][0] += 1
+        f[mode][1] = max(f[mode][1], err)
+    for fam, f in sorted(fams.items()):
+        parity_report.add("    %-16s %d / %d / %d cases; worst error in 2^-24*sum|ab| units %s" % (
+            fam, f[0][0], f[1][0], f[2][0], " / ".join("%.2f" % v[1] for v in f)))
+    for (prob, mode), (e, e32) in sorted(_FC.items()):
+        parity_report.add("    FC %d rows, %d -> %d, %s (%d-term reduction): kernel %.2f, torch CPU float32 matmul on the same "
+                          "outputs %.2f (asserted: %.0f)" % (prob[0], prob[3], prob[4], MODE_NAMES[mode],
+                                                             prob[4] if mode == 1 else prob[3], e, e32, FC_BOUND))
+    parity_report.add("    wall time of tests/vgg/test_gpu_fullsize_plans.py: %.0f s" % (time.time() - _T0[0]))
