@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 20
+#define MTLSSL_ABI_VERSION 21
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -196,6 +196,28 @@ int mtlssl_conv2d_set_winograd(int mode);
  * instantiation instead — same sums in the same order, bit-identical results, 12-20 % slower — so that the suite can
  * hold one against the other. Returns the previous setting; a value outside 0..1 only queries. Process-wide. */
 int mtlssl_conv2d_set_pointwise(int on);
+/* Row-group activity (no reference counterpart). The _xf / _ex calls with two more arguments: group_active holds one
+ * byte per group of rows_per_group consecutive GEMM rows (pixels of dy; the 49 pixels of a 7x7 RoI), and a 0 is the
+ * caller's PROMISE that every dy row of that group is exactly zero (an RoI whose loss scale is 0: every backward kernel
+ * of a RoI tower maps a zero RoI to a zero RoI). A pointwise (1x1, stride 1) problem on the tile engine then leaves the
+ * known zeros out: the filter gradient walks only the 16-row K-steps of each block's unchanged pixel range that touch an
+ * active group, the input gradient runs a zero-length K loop in tiles whose rows are all inactive (the epilogue still
+ * writes them). Launch grids, split boundaries and the order of every sum stay as they are and a zero product leaves an
+ * fp32 accumulator unchanged, so the results are BIT-IDENTICAL to the unflagged call. Every other problem (3x3, Winograd,
+ * strided, the small-channel kernels, the split-bf16 engine) ignores the flags; group_active = NULL is the _xf / _ex call.
+ * The filter gradient keeps its step list in the workspace (mtlssl_conv2d_wgrad_workspace_bytes covers it). */
+int mtlssl_conv2d_dgrad_rs(const mtlssl_conv_desc* d, const float* dy, const float* w, const float* residual,
+                           const float* mask_ref, float* dx, int epilogue, void* workspace, const float* filter_xf,
+                           int xf_variant, const uint8_t* group_active, int rows_per_group, mtlssl_stream_t stream);
+int mtlssl_conv2d_wgrad_rs(const mtlssl_conv_desc* d, const float* x, const float* dy,
+                           const float* out_scale, float* dw, float* dbias, const float* dbias_scale, float beta,
+                           void* workspace, const float* input_xf, int input_variant, const uint8_t* group_active,
+                           int rows_per_group, mtlssl_stream_t stream);
+/* flags[i] = scale[i] != 0 for n groups: the per-RoI loss scale as the byte flags the calls above take. */
+int mtlssl_row_group_flags(const float* scale, int n, uint8_t* flags, mtlssl_stream_t stream);
+/* 0: the calls above ignore their flags (the A/B and test switch), 1 (default): they use them. Returns the previous
+ * setting; any other value only queries. Process-wide. */
+int mtlssl_conv2d_set_row_skip(int on);
 /* fp32 matrix engine of the large implicit GEMMs. 0 (default; MTLSSL_FP32_ENGINE unset): v_mfma_f32_32x32x2_f32,
  * exact fp32 products with fp32 accumulation. 1 (MTLSSL_FP32_ENGINE=split): problems with at least 192 tiles of
  * 256 x 256 run on the bf16 matrix datapath with every operand split EXACTLY into three bf16 pieces (hi + mid + lo

@@ -23,6 +23,44 @@
 
 namespace mtlssl {
 
+// Row-group activity (mtlssl_row_group_flags, mtlssl_conv2d_dgrad_rs / _wgrad_rs). A group is a run of `rpg` consecutive
+// GEMM rows (the 49 pixels of a 7x7 RoI); flag 0 = the caller vouches that every dy row of the group is exactly zero.
+__global__ void __launch_bounds__(256) k_row_group_flags(const float* __restrict__ scale, int n, uint8_t* __restrict__ flags) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) flags[i] = scale[i] != 0.f;
+}
+// What a flagged pointwise filter gradient walks instead of every K-step: block z = split z of the launch, pixels
+// [z * pps, min(P, (z + 1) * pps)) in BK-row steps. out[z] = number of steps that touch an active group, out[KSTEP_HDR +
+// z * stride ...] = their indices, ascending (the partial sums keep their order). stride >= ceil(pps / BK).
+__global__ void __launch_bounds__(256) k_active_ksteps(const uint8_t* __restrict__ flags, int rpg, int P, int pps, int stride,
+                                                       int* __restrict__ out) {
+  const int z = blockIdx.x, pix0 = z * pps, pix1 = min(P, pix0 + pps);
+  const int ksteps = (max(pix1 - pix0, 0) + BK - 1) / BK;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int* list = out + KSTEP_HDR + (int64_t)z * stride;
+  __shared__ int wave_cnt[4];
+  int base = 0;
+  for (int s0 = 0; s0 < ksteps; s0 += 256) {
+    const int s = s0 + threadIdx.x;
+    bool act = false;
+    if (s < ksteps) {
+      const int r0 = pix0 + s * BK, r1 = min(r0 + BK, pix1) - 1;     // r1 < P: the last group index stays in range
+      for (int g = r0 / rpg; g <= r1 / rpg; ++g) act |= flags[g] != 0;
+    }
+    const unsigned long long m = __ballot(act);
+    if (lane == 0) wave_cnt[w] = __popcll(m);
+    __syncthreads();
+    int off = base;
+    for (int i = 0; i < w; ++i) off += wave_cnt[i];
+    if (act) list[off + __popcll(m & ((1ull << lane) - 1ull))] = s;
+    base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[z] = base;
+}
+// room for the list behind a pointwise filter gradient's partials: n splits of ceil(K-steps / n) entries each
+static inline int64_t kstep_list_bytes(int64_t P) { return align_up((KSTEP_HDR + 2 * cdiv(P, BK) + 128) * 4, 256); }
+static std::atomic<int>& row_skip_ref() { static std::atomic<int> v{1}; return v; }   // mtlssl_conv2d_set_row_skip
 
 // wgrad split-K fold: dw = beta*dw + scale[k] * sum_split ws[split]; float4 over k. Four lanes share one
 // output quad and stride over the splits (the sum of 8-64 partials is a latency chain, not bandwidth), then
@@ -1537,7 +1575,15 @@ int mtlssl_conv2d_dgrad(const mtlssl_conv_desc* d, const float* dy, const float*
 int mtlssl_conv2d_dgrad_xf(const mtlssl_conv_desc* d, const float* dy, const float* w,
                            const float* residual, const float* mask_ref, float* dx, int epi,
                            void* workspace, const float* filter_xf, int xf_variant, mtlssl_stream_t stream) {
+  return mtlssl_conv2d_dgrad_rs(d, dy, w, residual, mask_ref, dx, epi, workspace, filter_xf, xf_variant, nullptr, 0, stream);
+}
+
+int mtlssl_conv2d_dgrad_rs(const mtlssl_conv_desc* d, const float* dy, const float* w,
+                           const float* residual, const float* mask_ref, float* dx, int epi,
+                           void* workspace, const float* filter_xf, int xf_variant, const uint8_t* group_active,
+                           int rows_per_group, mtlssl_stream_t stream) {
   if (int rc = check_desc(d)) return rc;
+  MTLSSL_REQUIRE(!group_active || rows_per_group > 0, "conv_dgrad: group_active needs rows_per_group > 0");
   MTLSSL_REQUIRE(!(epi & MASK_ANY) || mask_ref, "conv_dgrad: mask_ref pointer required");
   MTLSSL_REQUIRE(!(epi & MTLSSL_EPI_RESIDUAL) || residual, "conv_dgrad: residual pointer required");
   ConvArgs p = make_args(d);
@@ -1558,6 +1604,11 @@ int mtlssl_conv2d_dgrad_xf(const mtlssl_conv_desc* d, const float* dy, const flo
       parity_dgrad(r, d, dy, w, residual, mask_ref, dx, epi, workspace, S(stream));
       break;
     case FAM_DIRECT:
+      // the flags reach the pointwise tile kernels only; every other kernel of the family never looks at them
+      if (group_active && row_skip_ref().load() != 0 && desc_is_pointwise(d)) {
+        p.group_active = group_active;
+        p.rows_per_group = rows_per_group;
+      }
       launch_planned<MODE_DGRAD>(r.plan, p, (float*)workspace, S(stream));
       break;
     case FAM_PADDED: {        // dy -> [M, Kp], w -> [C, Kp], zero columns
@@ -1638,6 +1689,19 @@ int mtlssl_conv2d_set_winograd(int mode) {
   return prev;
 }
 
+int mtlssl_conv2d_set_row_skip(int on) {
+  const int prev = row_skip_ref().load();
+  if (on == 0 || on == 1) row_skip_ref().store(on);
+  return prev;
+}
+
+int mtlssl_row_group_flags(const float* scale, int n, uint8_t* flags, mtlssl_stream_t stream) {
+  if (n <= 0) return MTLSSL_OK;
+  MTLSSL_REQUIRE(scale && flags, "row_group_flags: null pointer");
+  hipLaunchKernelGGL(k_row_group_flags, dim3(cdiv(n, 256)), dim3(256), 0, S(stream), scale, n, flags);
+  return check_launch("row_group_flags");
+}
+
 int mtlssl_conv2d_set_pointwise(int on) {
   const int prev = pointwise_ref().load();
   if (on == 0 || on == 1) pointwise_ref().store(on);
@@ -1703,7 +1767,9 @@ int mtlssl_conv2d_plan_info(const mtlssl_conv_desc* d, int mode, int parity_clas
 
 int64_t mtlssl_conv2d_wgrad_workspace_bytes(const mtlssl_conv_desc* d) {
   if (!d) return 256;                                                   // no check_desc here either
-  return colsum_bytes(d) + route(d, MODE_WGRAD).bytes;
+  // a pointwise problem may be called with row-group flags: its list of active K-steps sits behind the partials
+  return colsum_bytes(d) + route(d, MODE_WGRAD).bytes +
+         (desc_is_pointwise(d) ? kstep_list_bytes((int64_t)d->N * d->OH * d->OW) : 0);
 }
 
 // Plan of a grouped wgrad: the tile and the split of the pixel range that fill the chip with n problems' tiles.
@@ -1771,7 +1837,16 @@ int mtlssl_conv2d_wgrad_xf(const mtlssl_conv_desc* d, const float* x, const floa
 int mtlssl_conv2d_wgrad_ex(const mtlssl_conv_desc* d, const float* x, const float* dy,
                            const float* out_scale, float* dw, float* dbias, const float* dbias_scale, float beta,
                            void* workspace, const float* input_xf, int input_variant, mtlssl_stream_t stream) {
+  return mtlssl_conv2d_wgrad_rs(d, x, dy, out_scale, dw, dbias, dbias_scale, beta, workspace, input_xf, input_variant,
+                                nullptr, 0, stream);
+}
+
+int mtlssl_conv2d_wgrad_rs(const mtlssl_conv_desc* d, const float* x, const float* dy,
+                           const float* out_scale, float* dw, float* dbias, const float* dbias_scale, float beta,
+                           void* workspace, const float* input_xf, int input_variant, const uint8_t* group_active,
+                           int rows_per_group, mtlssl_stream_t stream) {
   if (int rc = check_desc(d)) return rc;
+  MTLSSL_REQUIRE(!group_active || rows_per_group > 0, "conv_wgrad: group_active needs rows_per_group > 0");
   hipStream_t st = S(stream);
   ConvArgs p = make_args(d);
   p.a = x; p.b = dy;
@@ -1813,6 +1888,15 @@ int mtlssl_conv2d_wgrad_ex(const mtlssl_conv_desc* d, const float* x, const floa
       p.out = ws_main;
       p.M = d->C; p.NG = d->K; p.nsplit = ns; p.pix_per_split = pps;
       p.cs_part = ride ? (float*)workspace : nullptr;
+      if (group_active && row_skip_ref().load() != 0 && !split && desc_is_pointwise(d) && pointwise_ref().load() != 0 &&
+          ns <= KSTEP_HDR) {
+        // the blocks keep their pixel ranges and walk only the K-steps that hold a live row: listed here, per split
+        int* list = (int*)((char*)ws_main + r.bytes);
+        const int stride = (int)cdiv(pps, BK);
+        hipLaunchKernelGGL(k_active_ksteps, dim3(ns), dim3(256), 0, st, group_active, rows_per_group, (int)P, pps, stride, list);
+        p.k_steps = list;
+        p.k_stride = stride;
+      }
       if (split) launch_split<MODE_WGRAD, false>(p, dim3(1, d->R * d->S, ns), st);
       else launch_mfma<MODE_WGRAD>(r.wg.cfg, p, dim3(1, d->R * d->S, ns), st);
       int64_t total4 = (int64_t)d->R * d->S * d->C * d->K / 4;

@@ -54,7 +54,23 @@ struct ConvArgs {
   // problem * nsplit + split; the partial tiles land in the workspace in that order
   const float* const* a_tab;
   const float* const* b_tab;
+  // Row-group activity of a pointwise dgrad / wgrad (mtlssl_conv2d_dgrad_rs / _wgrad_rs): the caller's promise that every
+  // dy row of an inactive group is exactly zero. A zero product leaves an fp32 accumulator as it is (and one that starts
+  // at +0 never turns -0), so leaving those rows out changes no bit of the result.
+  const uint8_t* group_active;   // dgrad: one flag per group of `rows_per_group` consecutive GEMM rows; nullptr = all live
+  int rows_per_group;
+  const int* k_steps;            // wgrad: [split] counts, then from KSTEP_HDR on `k_stride` ints per split: the ascending
+  int k_stride;                  // indices of the split's K-steps that touch an active group (k_active_ksteps, conv.hip)
 };
+constexpr int KSTEP_HDR = 64;    // the most splits a filter gradient is planned with
+
+// Does any of the tile's rows [m0, m0 + bm) belong to an active group? (block-uniform: a few byte loads per block)
+__device__ __forceinline__ bool tile_rows_active(const ConvArgs& p, int m0, int bm) {
+  const int g1 = (min(m0 + bm, p.M) - 1) / p.rows_per_group;
+  bool any = false;
+  for (int g = m0 / p.rows_per_group; g <= g1; ++g) any |= p.group_active[g] != 0;
+  return any;
+}
 
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 __host__ __device__ __forceinline__ int args_ldy(const ConvArgs& p) { return p.ldy ? p.ldy : p.K; }
@@ -274,6 +290,8 @@ __device__ __forceinline__ void conv_mfma_body(ConvArgs p, const SegArgs sg = Se
   const int ldy = args_ldy(p);     // row stride of dy (the A operand of dgrad, the B operand of wgrad)
   // ---- K-loop extent
   int rs_fixed = 0, pix0 = 0, pix1 = 0, ksteps, ks_begin = 0;
+  // flagged pointwise wgrad: the list of this block's K-steps that hold a live row (else nullptr: every step, in order)
+  const int* steps = nullptr;
   if constexpr (MODE == MODE_FWD) {
     ksteps = p.R * p.S * (p.C / BKT);
   } else if constexpr (MODE == MODE_DGRAD) {
@@ -285,6 +303,11 @@ __device__ __forceinline__ void conv_mfma_body(ConvArgs p, const SegArgs sg = Se
     pix0 = split * p.pix_per_split;
     pix1 = min(P, pix0 + p.pix_per_split);
     ksteps = (max(pix1 - pix0, 0) + BKT - 1) / BKT;
+    if constexpr (PW && !BATCH)
+      if (p.k_steps) {             // same pixel range, same order: only the steps of all-zero dy rows are left out
+        steps = p.k_steps + KSTEP_HDR + split * p.k_stride;
+        ksteps = p.k_steps[split];
+      }
   }
   // Pointwise wgrad: both operands are pixel-major ([pixel][C], [pixel][K]), so cutting the buffers off at this block's
   // last pixel makes the hardware range check supply the zeros of the ragged last K-step.
@@ -301,6 +324,10 @@ __device__ __forceinline__ void conv_mfma_body(ConvArgs p, const SegArgs sg = Se
       ksteps = min(ksteps, ks_begin + p.ks_per_split);
     }
   }
+  // flagged pointwise dgrad: a tile of all-zero dy rows runs a zero-length K loop; its epilogue (residual, mask,
+  // accumulate, split-K partial) still writes the tile
+  if constexpr (PW && MODE == MODE_DGRAD && !SEG && !BATCH)
+    if (p.group_active && !tile_rows_active(p, m0, BM)) ksteps = ks_begin;
 
   // ---- per-thread gather state (32-bit element offsets; the host guarantees < 2^30 elements)
   // KC loaders: thread -> (row = tid/4 + 64*i, 4 consecutive k at kq4)
@@ -595,17 +622,25 @@ __device__ __forceinline__ void conv_mfma_body(ConvArgs p, const SegArgs sg = Se
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
   const int nk = ksteps - ks_begin;
+  // K-step index of the it-th tile of the loop; `step_pf` holds the list entry of the tile the next kstep() loads,
+  // fetched one K-step ahead so that the scalar load's latency never sits in front of the operand loads
+  auto kmap = [&](int it) { return steps ? steps[it] : ks_begin + it; };
+  int step_pf = 0;
   if (nk > 0) {
-    load_tile(ks_begin, Set0{});
+    load_tile(kmap(0), Set0{});
     store_tile(0, Set0{});
   }
-  if (nk > 1) load_tile(ks_begin + 1, Set1{});
+  if (nk > 1) load_tile(kmap(1), Set1{});
+  if (steps && nk > 2) step_pf = steps[2];
   __syncthreads();
   // One K-step: `next` holds tile it+1 (loaded during step it-1), `spare` is free for tile it+2.
   auto kstep = [&](int it, auto next, auto spare) {
     const int cur = it & 1;
     if constexpr (!(LAB & 1))
-      if (it + 2 < nk) load_tile(ks_begin + it + 2, spare);
+      if (it + 2 < nk) {
+        load_tile(steps ? step_pf : ks_begin + it + 2, spare);
+        if (steps && it + 3 < nk) step_pf = steps[it + 3];
+      }
     const float* a = sA + cur * (BKT * LDA) + wr * (BM / WR) + lo;
     const float* b = sB + cur * (BKT * LDB) + wc * (BN / 2) + lo;
     // Software-pipelined fragments: the ds_reads of k-pair kk+1 are issued BEFORE the MFMAs of
@@ -727,6 +762,7 @@ __device__ __forceinline__ void conv_glds_body(ConvArgs p) {
     if constexpr (MODE != MODE_WGRAD) p.out += (int64_t)blockIdx.y * p.o_bs;
   }
   int rs_fixed = 0, pix0 = 0, pix1 = 0, ksteps, ks_begin = 0;
+  const int* steps = nullptr;
   if constexpr (MODE == MODE_FWD) {
     ksteps = p.R * p.S * (p.C / BKT);
   } else if constexpr (MODE == MODE_DGRAD) {
@@ -738,6 +774,11 @@ __device__ __forceinline__ void conv_glds_body(ConvArgs p) {
     pix0 = split * p.pix_per_split;
     pix1 = min(P, pix0 + p.pix_per_split);
     ksteps = (max(pix1 - pix0, 0) + BKT - 1) / BKT;
+    if constexpr (PWISE && !BATCH)
+      if (p.k_steps) {             // flagged pointwise wgrad: see conv_mfma_body
+        steps = p.k_steps + KSTEP_HDR + split * p.k_stride;
+        ksteps = p.k_steps[split];
+      }
   }
   if constexpr (MODE != MODE_WGRAD) {
     if (p.nsplit > 1) {
@@ -745,6 +786,8 @@ __device__ __forceinline__ void conv_glds_body(ConvArgs p) {
       ksteps = min(ksteps, ks_begin + p.ks_per_split);
     }
   }
+  if constexpr (PWISE && MODE == MODE_DGRAD && !BATCH)     // flagged pointwise dgrad: see conv_mfma_body
+    if (p.group_active && !tile_rows_active(p, m0, BM)) ksteps = ks_begin;
 
   const int ldy = args_ldy(p);                       // row stride of dy (A of dgrad, B of wgrad)
   unsigned a_rec = p.a_bytes, b_rec = p.b_bytes;     // pointwise wgrad: see conv_mfma_body
@@ -946,9 +989,11 @@ __device__ __forceinline__ void conv_glds_body(ConvArgs p) {
   const int nk = ksteps - ks_begin;
   constexpr int NDMA = ((LAB & 64) ? 0 : PA) + ((LAB & 128) ? 0 : PB);   // LDS-DMA instructions per wave per tile
   // ---- prologue: NSTAGE-1 tiles in flight, the first one landed
+  int step_pf = 0;                               // list entry of the tile the next K-step issues (see conv_mfma_body)
 #pragma unroll
   for (int s = 0; s < NSTAGE - 1; ++s)
-    if (s < nk) issue_tile(ks_begin + s, s);
+    if (s < nk) issue_tile(steps ? steps[s] : ks_begin + s, s);
+  if (steps && NSTAGE - 1 < nk) step_pf = steps[NSTAGE - 1];
   if (NSTAGE == 3 && nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -964,7 +1009,10 @@ __device__ __forceinline__ void conv_glds_body(ConvArgs p) {
   for (int it = 0; it < nk; ++it) {
     const bool more = it + NSTAGE - 1 < nk;
     if constexpr (!(LAB & 1))
-      if (more) issue_tile(ks_begin + it + NSTAGE - 1, nxt);
+      if (more) {
+        issue_tile(steps ? step_pf : ks_begin + it + NSTAGE - 1, nxt);
+        if (steps && it + NSTAGE < nk) step_pf = steps[it + NSTAGE];
+      }
     const float* a = smem + cur * STAGE;
     const float* b = a + A_FL;
     if constexpr (CS)

@@ -897,6 +897,9 @@ class FasterRCNNMetaArch:
             losses["closeness_classification_loss"] = ops.reduce_sum(rl)
             if want_grad:
                 d["closeness_predictions"] = d_clo
+                # a proposal that matched no groundtruth box has scale 0 and an all-zero row of d_clo (at least three
+                # in four of a balanced batch): the closeness tower's backward leaves those RoIs out of its 1x1 GEMMs
+                pd["_clo_active"] = ops.row_group_flags(clo_s)
         return cls_s
 
     def _loss_refined_classifier(self, pd, cls_s, losses, d, want_grad):
@@ -1009,7 +1012,11 @@ class FasterRCNNMetaArch:
                 cfeat = pd["_cfeat"]
                 g = self.closeness_predictor.backward(pd["_cp"], d["closeness_predictions"], None, cfeat.shape,
                                                       **self.closeness_tower.out_mask(cfeat))
-                gc = self.closeness_tower.backward(g, cfeat, pd["_cctx"], need_input_grad=not stop, masked=True)
+                active = pd.get("_clo_active")
+                if active is not None:
+                    active.record_stream(torch.cuda.current_stream())
+                gc = self.closeness_tower.backward(g, cfeat, pd["_cctx"], need_input_grad=not stop, masked=True,
+                                                   active=active)
                 if not stop:
                     todo.append((gc, pd["_argmax"], pd["proposal_boxes_normalized"].view(-1, 4), pd["_box_ind"]))
             if mtl.window:                       # behind the closeness tower, on the same stream

@@ -350,7 +350,7 @@ class InceptionTower(nn.Tower):
         out = self.conv_7b.forward(x)
         return out, ((c7, ctxs, x) if save else None)
 
-    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD):
+    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD, active=None):
         c7, ctxs, pre7b = ctx
         gp = g_out if masked else ops.relu_bwd(out, g_out)
         wgrad.run(self.conv_7b, pre7b, gp)

@@ -64,7 +64,7 @@ class MobilenetTower(nn.Tower):
         a13 = self.pw13.forward(d13)
         return a13, ((crops, d12, a12, d13) if save else None)
 
-    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD):
+    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD, active=None):
         """A few ~10-us kernels: the filter gradients run inline whatever `wgrad` is (FasterRCNNMetaArch._wgrad_exec)."""
         crops, d12, a12, d13 = ctx
         gp = g_out if masked else ops.relu6_bwd(out, g_out)

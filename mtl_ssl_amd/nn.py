@@ -36,24 +36,24 @@ class WgradStream:
     def __init__(self, stream):
         self.stream = stream
 
-    def run(self, layer, x, g):
+    def run(self, layer, x, g, **kw):
         if not layer.trainable:
             return
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         self.stream.wait_event(ev)
-        for t in (x, g):                      # keep the caching allocator from recycling them under the side stream
+        for t in (x, g) + tuple(kw.values()):  # keep the caching allocator from recycling them under the side stream
             t.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
-            layer.wgrad(x, g)
+            layer.wgrad(x, g, **kw)
 
 
 class _InlineWgrad:
     stream = None
 
     @staticmethod
-    def run(layer, x, g):
-        layer.wgrad(x, g)
+    def run(layer, x, g, **kw):
+        layer.wgrad(x, g, **kw)
 
 
 INLINE_WGRAD = _InlineWgrad()
@@ -194,17 +194,19 @@ class ConvBN(_FrozenBN):
             self._kept.clear()
         return self._kept
 
-    def wgrad(self, x, g):
+    def wgrad(self, x, g, active=None):
+        """active: uint8 flag per image (RoI) of g, 0 = its rows of g are all exactly zero (ops.conv2d_wgrad), or None."""
         if self.trainable:
             # without a gamma, d(beta) is just the column sum of g: ride on the wgrad's dbias pass
             db = self.ps.grad(self.beta.name) if (self.bn_trainable and self.gamma is None) else None
             ops.conv2d_wgrad(self.desc(x.shape), x, g, self.ps.grad(self.w.name), out_scale=self.scale,
-                             dbias=db, beta=1.0, input_xf=self._kept.pop(x.data_ptr(), None))
+                             dbias=db, beta=1.0, input_xf=self._kept.pop(x.data_ptr(), None), active=active)
             self.ps.grad_ready(self.w, self.beta if db is not None else None)
 
-    def dgrad(self, x_shape, g, residual=None, mask_ref=None, out=None, accum=False, mask6=False):
+    def dgrad(self, x_shape, g, residual=None, mask_ref=None, out=None, accum=False, mask6=False, active=None):
         return ops.conv2d_dgrad(self.desc(x_shape), g, self.w_eff, residual, mask_ref,
-                                dgrad_epilogue(residual, accum, mask_ref, mask6), out=out, xf_cache=self.ps.filter_cache)
+                                dgrad_epilogue(residual, accum, mask_ref, mask6), out=out, xf_cache=self.ps.filter_cache,
+                                active=active)
 
 
 class DepthwiseBN(_FrozenBN):
@@ -386,9 +388,12 @@ class Bottleneck:
             ctx = ctx + (out, sc)
         return out, ctx
 
-    def backward(self, gp, ctx, need_input_grad=True, mask_input=True, wgrad=INLINE_WGRAD):
+    def backward(self, gp, ctx, need_input_grad=True, mask_input=True, wgrad=INLINE_WGRAD, active=None):
         """gp: dL/d(pre-activation of out). Returns dL/d(pre-activation of x) (masked by x>0 when
-        mask_input), or None. `wgrad`: where the filter gradients run (inline, or a WgradStream)."""
+        mask_input), or None. `wgrad`: where the filter gradients run (inline, or a WgradStream).
+        active: uint8 flag per image (RoI), 0 = gp is exactly zero there — then so is every gradient of the unit, and the
+        1x1 layers leave those rows out (stride-1 units only: a RoI keeps its rows)."""
+        kw = {} if active is None else dict(active=active)
         x, a1, a2, sc_sub = ctx[:4]
         if self.bn_trainable:
             out, sc = ctx[4], ctx[5]
@@ -399,26 +404,26 @@ class Bottleneck:
             del o3
             if self.shortcut is not None:
                 self.shortcut.bn_grad(sc, gp)
-        wgrad.run(self.conv3, a2, gp)
-        gp2 = self.conv3.dgrad(a2.shape, gp, mask_ref=a2)
+        wgrad.run(self.conv3, a2, gp, **kw)
+        gp2 = self.conv3.dgrad(a2.shape, gp, mask_ref=a2, **kw)
         if self.bn_trainable:
             self.conv2.bn_grad(a2, gp2)
         wgrad.run(self.conv2, a1, gp2)
         gp1 = self.conv2.dgrad(a1.shape, gp2, mask_ref=a1)
         if self.bn_trainable:
             self.conv1.bn_grad(a1, gp1)
-        wgrad.run(self.conv1, x, gp1)
+        wgrad.run(self.conv1, x, gp1, **kw)
         if self.shortcut is not None:
-            wgrad.run(self.shortcut, x, gp)
+            wgrad.run(self.shortcut, x, gp, **kw)
         if not need_input_grad:
             return None
         if self.shortcut is not None:
-            addend = self.shortcut.dgrad(x.shape, gp)
+            addend = self.shortcut.dgrad(x.shape, gp, **kw)
         elif self.stride > 1:
             addend = ops.maxpool_bwd(x, sc_sub, gp, 1, self.stride, (0, 0))
         else:
             addend = gp
-        return self.conv1.dgrad(x.shape, gp1, residual=addend, mask_ref=x if mask_input else None)
+        return self.conv1.dgrad(x.shape, gp1, residual=addend, mask_ref=x if mask_input else None, **kw)
 
 
 class BlockStack:
@@ -467,9 +472,11 @@ class Tower:
         zeros of the output too."""
         return dict(mask_ref=None if cls.out_act is None else feat, mask6=cls.out_act == "relu6")
 
-    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=INLINE_WGRAD):
+    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=INLINE_WGRAD, active=None):
         """g_out: dL/d(out), or dL/d(pre-activation of out) when `masked`. Returns dL/d(crops) or None.
-        `wgrad`: where the filter gradients may run (inline, or a WgradStream the caller joins)."""
+        `wgrad`: where the filter gradients may run (inline, or a WgradStream the caller joins).
+        active: uint8 flag per RoI, 0 = g_out is exactly zero there; a tower may use it to leave those RoIs' rows out of
+        its GEMMs (same bits) or ignore it."""
         raise NotImplementedError
 
 

@@ -591,7 +591,29 @@ def conv2d_fwd(d, x, w, bias=None, residual=None, epilogue=0, out=None, xf_cache
     return y
 
 
-def conv2d_dgrad(d, dy, w, residual=None, mask_ref=None, epilogue=0, out=None, xf_cache=None):
+def set_row_skip(on):
+    """Test / A-B switch: 0 makes conv2d_dgrad / conv2d_wgrad ignore their `active` flags (every row is multiplied, as
+    without flags; bit-identical results). Returns the previous setting (on=-1 only queries)."""
+    return lib().conv2d_set_row_skip(int(on))
+
+
+def row_group_flags(scale):
+    """uint8 flags (scale != 0) of a per-RoI float scale: the `active` argument of conv2d_dgrad / conv2d_wgrad."""
+    flags = torch.empty(scale.numel(), dtype=torch.uint8, device=scale.device)
+    lib().row_group_flags(ptr(_chk(scale)), scale.numel(), ptr(flags), _stream())
+    return flags
+
+
+def _active_arg(d, active, rows=None):
+    """(flags pointer, rows per group) of a call whose GEMM rows are d.N groups of one image's (RoI's) pixels each."""
+    if active is None:
+        return None, 0
+    assert active.dtype == torch.uint8 and active.is_contiguous() and active.numel() == d.N, (active.dtype, active.shape, d.N)
+    return ptr(active), rows if rows is not None else d.OH * d.OW
+
+
+def conv2d_dgrad(d, dy, w, residual=None, mask_ref=None, epilogue=0, out=None, xf_cache=None, active=None):
+    """active: uint8 [d.N] or None — 0 promises that image (RoI) n's dy rows are all exactly zero (mtlssl_conv2d_dgrad_rs)."""
     dx = out if out is not None else torch.empty((d.N, d.H, d.W, d.C), dtype=f32, device=dy.device)
     if PROFILER is None:
         def run():                                    # scratch output; no accumulate into it
@@ -604,16 +626,17 @@ def conv2d_dgrad(d, dy, w, residual=None, mask_ref=None, epilogue=0, out=None, x
         ACCOUNT.add(d, 1)
     ws = _conv_ws(d, 1, dy.device)
     U, variant = xf_cache.get(d, 1, w) if (xf_cache is not None and d.R == 3 and d.S == 3) else (None, -1)
-    lib().conv2d_dgrad_xf(ctypes.byref(d), ptr(_chk_y(d, dy)), ptr(_chk(w)), ptr(residual), ptr(mask_ref),
-                          ptr(dx), epilogue, ptr(ws), ptr(U), variant, _stream())
+    lib().conv2d_dgrad_rs(ctypes.byref(d), ptr(_chk_y(d, dy)), ptr(_chk(w)), ptr(residual), ptr(mask_ref),
+                          ptr(dx), epilogue, ptr(ws), ptr(U), variant, *_active_arg(d, active, d.H * d.W), _stream())
     if t0 is not None:
         PROFILER.end(d, 1, t0)
     return dx
 
 
-def conv2d_wgrad(d, x, dy, dw, out_scale=None, dbias=None, beta=0.0, input_xf=None, dbias_scale=None):
+def conv2d_wgrad(d, x, dy, dw, out_scale=None, dbias=None, beta=0.0, input_xf=None, dbias_scale=None, active=None):
     """input_xf: (V, variant) kept by this layer's conv2d_fwd(keep_input_xf=...) for the same x, or None.
-    dbias_scale: per-channel factor on the bias gradient (a bias that enters through a folded factor), or None."""
+    dbias_scale: per-channel factor on the bias gradient (a bias that enters through a folded factor), or None.
+    active: as conv2d_dgrad's (mtlssl_conv2d_wgrad_rs)."""
     if PROFILER is None:
         def run():                                    # scratch filter gradient, beta = 0
             tmp = workspace(4 * d.R * d.S * d.C * d.K, "tune_out", x.device)
@@ -627,8 +650,8 @@ def conv2d_wgrad(d, x, dy, dw, out_scale=None, dbias=None, beta=0.0, input_xf=No
     V, vvar = input_xf if input_xf is not None else (None, -1)
     if V is not None:
         V.record_stream(torch.cuda.current_stream())     # made on the forward's stream, read on this one
-    lib().conv2d_wgrad_ex(ctypes.byref(d), ptr(_chk(x)), ptr(_chk_y(d, dy)), ptr(out_scale), ptr(dw),
-                          ptr(dbias), ptr(dbias_scale), float(beta), ptr(ws), ptr(V), vvar, _stream())
+    lib().conv2d_wgrad_rs(ctypes.byref(d), ptr(_chk(x)), ptr(_chk_y(d, dy)), ptr(out_scale), ptr(dw),
+                          ptr(dbias), ptr(dbias_scale), float(beta), ptr(ws), ptr(V), vvar, *_active_arg(d, active), _stream())
     if t0 is not None:
         PROFILER.end(d, 2, t0)
     return dw

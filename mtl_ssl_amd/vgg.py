@@ -45,7 +45,7 @@ class IdentityTower(nn.Tower):
     def forward(self, crops, save):
         return crops, None
 
-    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD):
+    def backward(self, g_out, out, ctx, need_input_grad, masked=False, wgrad=nn.INLINE_WGRAD, active=None):
         return g_out if need_input_grad else None
 
 
