@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 21
+#define MTLSSL_ABI_VERSION 22
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -223,9 +223,23 @@ int mtlssl_conv2d_set_row_skip(int on);
  * 256 x 256 run on the bf16 matrix datapath with every operand split EXACTLY into three bf16 pieces (hi + mid + lo
  * = the fp32 value) and six of the nine piece products accumulated in fp32; the three dropped products are each below
  * 2^-21 |a*b| in the worst case, about 2^-24 |a*b| on average (the size of one fp32 accumulation rounding). Same error against fp64 as mode 0 (tests/test_gpu_split_engine.py), other
- * summation order (not bit-identical), +-inf operands yield NaN. Returns the previous mode; any other value only
- * queries. Process-wide. */
+ * summation order (not bit-identical), +-inf operands yield NaN.
+ * 2 ("high") and 3 ("medium") are REDUCED levels of the same engine, reachable through this call only (the environment
+ * variable keeps its meaning: split / 1, anything else native). They trade a stated amount of accuracy for matrix rate:
+ *   2: every operand truncated to 16 significant bits (bit pattern & 0xFFFFFF00) as two bf16 pieces h + m, the three
+ *      products (h,h) (h,m) (m,h): |y - exact| <= (3 * 2^-14 + 2^-18) * sum|a||b| on top of mode 0's own error;
+ *   3: every operand rounded to ONE bf16, round-to-nearest-even, one product: |y - exact| <= (2^-8 + 2^-18) * sum|a||b|
+ *      on top of mode 0's error. +-inf operands stay inf; values within half a bf16 ulp of FLT_MAX round to inf.
+ * The reduced levels apply to the DIRECT launches (forward, data gradient, direct filter gradient) of the problems
+ * mode 1 takes; the Winograd-domain GEMMs run with all six products under every mode >= 1 (the Winograd transforms
+ * amplify operand error about a hundredfold: no bound exists for fewer products there), and problems mode 1 leaves to
+ * the native engine stay there bit for bit under every mode.
+ * Returns the previous mode; -1 (and any other value outside 0..3) only queries. Process-wide. */
 int mtlssl_conv2d_set_fp32_engine(int mode);
+/* out[4] = tile-engine GEMM launches made with native fp32 / six / three / one product(s) since the library was loaded
+ * or since the last call with reset != 0 (which returns the counts and then zeroes them). Host-side relaxed atomic
+ * counters, bumped where the launch is chosen: they tell which engine ran without comparing bits. Process-wide. */
+int mtlssl_conv2d_engine_launches(int64_t* out, int reset);
 /* Number of launches of the implicit-GEMM kernel one call makes for this problem (2 when the planner
  * splits off a K-split tail launch) — lets a profiler relate per-call timings to
  * per-dispatch kernel traces. */

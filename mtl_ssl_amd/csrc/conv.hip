@@ -893,8 +893,16 @@ static void small_wgrad_plan(const mtlssl_conv_desc* d, int* nsplit, int* k_per_
 
 static std::atomic<int>& pointwise_ref() { static std::atomic<int> v{1}; return v; }   // mtlssl_conv2d_set_pointwise
 
+// mtlssl_conv2d_engine_launches: tile-engine GEMM launches by product count (native, six, three, one)
+static std::atomic<int64_t>* engine_launch_counts() {
+  static std::atomic<int64_t> v[4];
+  return v;
+}
+void count_engine_launch(int slot) { engine_launch_counts()[slot].fetch_add(1, std::memory_order_relaxed); }
+
 template <int MODE>
 static void launch_mfma(int cfg, ConvArgs& p, dim3 extra, hipStream_t st, int tile_rows = -1) {
+  count_engine_launch(0);
   p.tiles_m = tile_rows >= 0 ? tile_rows : (int)cdiv(p.M, CFG_BM[cfg]);
   p.tiles_n = (int)cdiv(p.NG, CFG_BN[cfg]);
   dim3 grid(p.tiles_m * p.tiles_n, extra.y, extra.z);
@@ -969,7 +977,7 @@ static void launch_planned(const Plan& pl, ConvArgs& p, float* ws, hipStream_t s
   if (pl.nsplit == 1 && args_ldy(p) == p.K &&
       split_engine_takes(pl.cfg, p.M, p.NG, (int64_t)p.R * p.S * (MODE == MODE_FWD ? p.C : p.K))) {
     p.nsplit = 1; p.ks_per_split = 0; p.tile_m0 = 0; p.ws_m0 = 0;     // one launch over every tile, no K-split tail
-    launch_split<MODE, false>(p, dim3(1, 1, 1), st);
+    launch_split_direct<MODE>(p, dim3(1, 1, 1), st);
     return;
   }
   if (pl.tail_rows == 0) {
@@ -1170,7 +1178,7 @@ static int64_t wgrad_partial_bytes(const mtlssl_conv_desc* d, int ns, int* split
   return align_up((int64_t)ns * d->R * d->S * d->C * d->K * 4, 256);
 }
 static bool wgrad_on_split_engine(const Route& r, const mtlssl_conv_desc* d) {
-  return fp32_engine() == 1 && (r.wg.cfg == 0 || r.wg.cfg == 3) && desc_dense(d) && r.split_ns > 0;
+  return fp32_engine() >= 1 && (r.wg.cfg == 0 || r.wg.cfg == 3) && desc_dense(d) && r.split_ns > 0;
 }
 // the small-C stem kernel has no residual / ReLU6 / tanh epilogue: those calls take the scalar kernel
 static inline int stem_fwd_family(int epi) { return (epi & ~(MTLSSL_EPI_BIAS | MTLSSL_EPI_RELU)) ? FAM_SCALAR : FAM_STEM_FWD; }
@@ -1501,6 +1509,7 @@ int mtlssl_conv2d_fwd_grouped(const mtlssl_conv_desc* d, const float* x, int n, 
   p.tiles_m = (int)cdiv(p.M, CFG_BM[cfg]);
   p.tiles_n = (int)cdiv(max_k, CFG_BN[cfg]);
   dim3 grid(p.tiles_m * p.tiles_n, n, 1);
+  count_engine_launch(0);
   switch (cfg) {
     case 0: hipLaunchKernelGGL((k_conv_mfma_pw_grp<128, 128>), grid, dim3(256), 0, S(stream), p, ga); break;
     case 1: hipLaunchKernelGGL((k_conv_mfma_pw_grp<128, 64>), grid, dim3(256), 0, S(stream), p, ga); break;
@@ -1557,6 +1566,7 @@ int mtlssl_conv2d_dgrad_segmented(const mtlssl_conv_desc* d, int n, const mtlssl
   p.tiles_m = (int)cdiv(p.M, CFG_BM[cfg]);
   p.tiles_n = (int)cdiv(p.NG, CFG_BN[cfg]);
   dim3 grid(p.tiles_m * p.tiles_n, 1, 1);
+  count_engine_launch(0);
   switch (cfg) {
     case 0: hipLaunchKernelGGL((k_conv_mfma_pw_seg<128, 128>), grid, dim3(256), 0, S(stream), p, sa); break;
     case 1: hipLaunchKernelGGL((k_conv_mfma_pw_seg<128, 64>), grid, dim3(256), 0, S(stream), p, sa); break;
@@ -1679,8 +1689,16 @@ int mtlssl_conv2d_force_config(const mtlssl_conv_desc* d, int mode, int cfg) {
 
 int mtlssl_conv2d_set_fp32_engine(int mode) {
   const int prev = fp32_engine();
-  if (mode == 0 || mode == 1) fp32_engine_ref().store(mode);
+  if (mode >= 0 && mode <= 3) fp32_engine_ref().store(mode);
   return prev;
+}
+
+int mtlssl_conv2d_engine_launches(int64_t out[4], int reset) {
+  MTLSSL_REQUIRE(out != nullptr, "engine_launches: out required");
+  for (int i = 0; i < 4; ++i)
+    out[i] = reset ? engine_launch_counts()[i].exchange(0, std::memory_order_relaxed)
+                   : engine_launch_counts()[i].load(std::memory_order_relaxed);
+  return MTLSSL_OK;
 }
 
 int mtlssl_conv2d_set_winograd(int mode) {
@@ -1897,7 +1915,7 @@ int mtlssl_conv2d_wgrad_rs(const mtlssl_conv_desc* d, const float* x, const floa
         p.k_steps = list;
         p.k_stride = stride;
       }
-      if (split) launch_split<MODE_WGRAD, false>(p, dim3(1, d->R * d->S, ns), st);
+      if (split) launch_split_direct<MODE_WGRAD>(p, dim3(1, d->R * d->S, ns), st);
       else launch_mfma<MODE_WGRAD>(r.wg.cfg, p, dim3(1, d->R * d->S, ns), st);
       int64_t total4 = (int64_t)d->R * d->S * d->C * d->K / 4;
       const int main_blocks = (int)cdiv(total4 * 4, 256);

@@ -18,10 +18,19 @@
 // Differences a caller can see: +-inf operands give NaN (inf - inf in the split) where the native engine gives
 // inf; sums are formed in another order (not bit-identical to the native engine).
 //
+// Reduced levels (NP = pieces per operand, a template parameter of the one body; mtlssl_conv2d_set_fp32_engine 2 / 3):
+//   NP = 2 "high":   x ~ h + m, x truncated to 16 significant bits (pattern & 0xFFFFFF00), products (h,h) (h,m) (m,h).
+//                    Against the six products this drops (m,m) (h,l) (l,h), each below 2^-14 |a*b|.
+//   NP = 1 "medium": one bf16 per operand, ROUND-TO-NEAREST-EVEN (v_cvt_pk_bf16_f32; truncation would bias every
+//                    operand towards zero), one product: each operand off by at most 2^-9 relative. No subtraction
+//                    is involved, so +-inf stays inf; values within half a bf16 ulp of FLT_MAX round to inf.
+// The LDS stage holds only the pieces that are read (64 KB / 32 KB of operands against 96 KB); the launch asks for at
+// least the 36 KB the epilogue's transpose patches need.
+//
 // Geometry: 512 threads = 8 wavefronts as 4 (m) x 2 (n), 64 x 128 outputs each (2 x 4 MFMA blocks);
-// K-step 16 = one MFMA k extent; LDS image of an operand stage: [piece 3][k-group 2][row 256] x 16 B, the 16 B
+// K-step 16 = one MFMA k extent; LDS image of an operand stage: [piece NP][k-group 2][row 256] x 16 B, the 16 B
 // being the 8 bf16 of one k-group — exactly one lane's MFMA operand (lane l: row l%32, k-group l/32), read with
-// one conflict-free ds_read_b128. Two stages (96 KB, dynamic LDS), register double-buffered global loads two
+// one conflict-free ds_read_b128. Two stages (96 KB with three pieces, dynamic LDS), register double-buffered global loads two
 // K-steps ahead, one barrier per K-step. Loaders, split-K / batched / grouped variants and the epilogue are the
 // native engine's (conv_mfma.h).
 #pragma once
@@ -35,7 +44,12 @@ namespace mtlssl {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int SPLIT_BM = 256, SPLIT_BN = 256;
-constexpr int split_lds_bytes(int bn) { return 2 * (6 * SPLIT_BM + 6 * bn) * 16; }
+// two operand stages of `np` pieces, and never less than the epilogue's eight 32 x 36-float transpose patches
+// (conv_epilogue, conv_mfma.h), which reuse the same allocation
+constexpr int split_lds_bytes(int bn, int np = 3) {
+  const int stages = 2 * np * (2 * SPLIT_BM + 2 * bn) * 16, epilogue = 8 * 32 * 36 * 4;
+  return stages > epilogue ? stages : epilogue;
+}
 
 // x = h + m + l exactly; each returned as the upper 16 bits of its fp32 pattern (a bf16)
 __device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l) {
@@ -44,6 +58,31 @@ __device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsign
   const unsigned mb = __float_as_uint(r1) & 0xFFFF0000u;
   const float r2 = r1 - __uint_as_float(mb);
   h = hb >> 16; m = mb >> 16; l = __float_as_uint(r2) >> 16;
+}
+// The NP pieces of two values that are neighbours along k, packed as the LDS image wants them: w[piece] = piece of x0
+// in the low half, of x1 in the high half.
+//   NP = 3: split3. NP = 2: h + m = x with its low 8 mantissa bits cleared (m = that minus h: 8 significant bits, exact).
+//   NP = 1: the bf16 nearest to x, ties to even (one v_cvt_pk_bf16_f32 for the pair).
+template <int NP>
+__device__ __forceinline__ void split_pair(float x0, float x1, unsigned (&w)[NP]) {
+  if constexpr (NP == 1) {
+    typedef float floatx2_ __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
+    w[0] = __builtin_bit_cast(unsigned, __builtin_convertvector(floatx2_{x0, x1}, bf16x2_));
+  } else if constexpr (NP == 2) {
+    const unsigned t0 = __float_as_uint(x0) & 0xFFFFFF00u, t1 = __float_as_uint(x1) & 0xFFFFFF00u;
+    const unsigned h0 = t0 & 0xFFFF0000u, h1 = t1 & 0xFFFF0000u;
+    const unsigned m0 = __float_as_uint(__uint_as_float(t0) - __uint_as_float(h0));
+    const unsigned m1 = __float_as_uint(__uint_as_float(t1) - __uint_as_float(h1));
+    w[0] = (h0 >> 16) | h1;
+    w[1] = (m0 >> 16) | (m1 & 0xFFFF0000u);
+  } else {
+    unsigned a[3], b[3];
+    split3(x0, a[0], a[1], a[2]);
+    split3(x1, b[0], b[1], b[2]);
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) w[pc] = a[pc] | (b[pc] << 16);
+  }
 }
 
 // offset of a guarded load: x, or the out-of-range offset (the buffer load then returns 0) — as mask arithmetic, so
@@ -63,14 +102,16 @@ __device__ __forceinline__ float bufload1(__amdgpu_buffer_rsrc_t rsrc, unsigned 
 //   BN = 128, NW = 4: 256 x 128 tile, 4 wavefronts as 2 x 2 with 128 x 64 outputs each, 72 KB of LDS, two blocks per CU.
 // PW: the problem is pointwise (1x1, stride 1, no padding — the ROI-tower GEMMs and every Winograd-domain GEMM):
 // the A gather needs no tap / bounds state, which pays for the native engine's four-lanes-per-row load map.
-template <int MODE, bool BATCH, int BN, int NW, bool PW>
+// NP: pieces per operand (3: six products, 2: three, 1: one — see the header).
+template <int MODE, bool BATCH, int BN, int NW, bool PW, int NP = 3>
 __device__ __forceinline__ void conv_split_body(ConvArgs p) {
+  static_assert(NP >= 1 && NP <= 3 && (NP == 3 || NW == 8), "reduced piece counts: the 256-wide tile only");
   constexpr int BM = SPLIT_BM, BKT = 16, NT = 64 * NW, WR = NW / 2;
   constexpr int TM = BM / (32 * WR), TN = BN / 64;
   constexpr bool A_KC = (MODE != MODE_WGRAD);     // A rows are k-contiguous (else m-contiguous, k strided)
   constexpr bool B_KC = (MODE == MODE_DGRAD);
   constexpr unsigned OOB = 0xFFFFFFF0u;
-  constexpr int A_SLOTS = 6 * BM, B_SLOTS = 6 * BN, STAGE = A_SLOTS + B_SLOTS;
+  constexpr int A_SLOTS = 2 * NP * BM, B_SLOTS = 2 * NP * BN, STAGE = A_SLOTS + B_SLOTS;
   // elements per thread and K-step
   constexpr bool QUAD = PW && A_KC;               // A units of 4 floats (row, k quad) instead of 8 (row, k-group)
   constexpr int KCA = (QUAD ? 4 : 2) * BM / NT, KCB = 2 * BN / NT;   // k-contiguous units per thread
@@ -292,12 +333,11 @@ __device__ __forceinline__ void conv_split_body(ConvArgs p) {
 #pragma unroll
     for (int i = 0; i < units; ++i) {
       const int u = tid + NT * i, row = u >> 1, kg = u & 1;
-      unsigned h[8], m[8], l[8];
+      unsigned q[4][NP];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) split3(r[8 * i + e], h[e], m[e], l[e]);
-      s[(0 * 2 + kg) * rows + row] = uintx4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
-      s[(1 * 2 + kg) * rows + row] = uintx4{m[0] | (m[1] << 16), m[2] | (m[3] << 16), m[4] | (m[5] << 16), m[6] | (m[7] << 16)};
-      s[(2 * 2 + kg) * rows + row] = uintx4{l[0] | (l[1] << 16), l[2] | (l[3] << 16), l[4] | (l[5] << 16), l[6] | (l[7] << 16)};
+      for (int e = 0; e < 4; ++e) split_pair<NP>(r[8 * i + 2 * e], r[8 * i + 2 * e + 1], q[e]);
+#pragma unroll
+      for (int pc = 0; pc < NP; ++pc) s[(pc * 2 + kg) * rows + row] = uintx4{q[0][pc], q[1][pc], q[2][pc], q[3][pc]};
     }
   };
   // k-contiguous operand, quad map: 4 consecutive k of one row -> half a slot (8 bytes) per piece
@@ -308,12 +348,11 @@ __device__ __forceinline__ void conv_split_body(ConvArgs p) {
 #pragma unroll
     for (int i = 0; i < units; ++i) {
       const int u = tid + NT * i, row = u >> 2, kg = (u >> 1) & 1, half = u & 1;
-      unsigned h[4], m[4], l[4];
+      unsigned q[2][NP];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) split3(r[4 * i + e], h[e], m[e], l[e]);
-      s2[((0 * 2 + kg) * rows + row) * 2 + half] = uintx2{h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
-      s2[((1 * 2 + kg) * rows + row) * 2 + half] = uintx2{m[0] | (m[1] << 16), m[2] | (m[3] << 16)};
-      s2[((2 * 2 + kg) * rows + row) * 2 + half] = uintx2{l[0] | (l[1] << 16), l[2] | (l[3] << 16)};
+      for (int e = 0; e < 2; ++e) split_pair<NP>(r[4 * i + 2 * e], r[4 * i + 2 * e + 1], q[e]);
+#pragma unroll
+      for (int pc = 0; pc < NP; ++pc) s2[((pc * 2 + kg) * rows + row) * 2 + half] = uintx2{q[0][pc], q[1][pc]};
     }
   };
   // strided operand: r[2j], r[2j+1] = the k pair of unit j -> one dword per piece and column
@@ -323,13 +362,11 @@ __device__ __forceinline__ void conv_split_body(ConvArgs p) {
     unsigned* sw = reinterpret_cast<unsigned*>(s);
 #pragma unroll
     for (int j = 0; j < units; ++j) {
-      unsigned h0, m0_, l0, h1, m1, l1;
-      split3(r[2 * j], h0, m0_, l0);
-      split3(r[2 * j + 1], h1, m1, l1);
+      unsigned q[NP];
+      split_pair<NP>(r[2 * j], r[2 * j + 1], q);
       const int c = cb + 16 * j + mc_cn;
-      sw[((0 * 2 + mc_kg) * rows + c) * 4 + mc_kq] = h0 | (h1 << 16);
-      sw[((1 * 2 + mc_kg) * rows + c) * 4 + mc_kq] = m0_ | (m1 << 16);
-      sw[((2 * 2 + mc_kg) * rows + c) * 4 + mc_kq] = l0 | (l1 << 16);
+#pragma unroll
+      for (int pc = 0; pc < NP; ++pc) sw[((pc * 2 + mc_kg) * rows + c) * 4 + mc_kq] = q[pc];
     }
   };
   auto store_tile = [&](int buf, auto SET) {
@@ -375,12 +412,13 @@ __device__ __forceinline__ void conv_split_body(ConvArgs p) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
     };
     if constexpr (NW == 8) {
-      // all three pieces of both operands in registers, the six piece products in the order the operands arrive
-      bf16x8 fa[3][TM], fb[3][TN];
+      // all pieces of both operands in registers, the piece products (six, three or one) in the order the operands arrive
+      bf16x8 fa[NP][TM], fb[NP][TN];
 #pragma unroll
-      for (int pc = 0; pc < 3; ++pc) read_piece(pc, fa[pc], fb[pc]);
-      group(fa[0], fb[0]); group(fa[0], fb[1]); group(fa[1], fb[0]);
-      group(fa[1], fb[1]); group(fa[0], fb[2]); group(fa[2], fb[0]);
+      for (int pc = 0; pc < NP; ++pc) read_piece(pc, fa[pc], fb[pc]);
+      group(fa[0], fb[0]);
+      if constexpr (NP >= 2) { group(fa[0], fb[1]); group(fa[1], fb[0]); }
+      if constexpr (NP == 3) { group(fa[1], fb[1]); group(fa[0], fb[2]); group(fa[2], fb[0]); }
     } else {
       // the 128-wide tile stages twice as many A values per thread: the hi pieces stay, the lo and then the mid
       // pieces pass through one more register set (48 fragment registers instead of 72)
@@ -402,13 +440,18 @@ __device__ __forceinline__ void conv_split_body(ConvArgs p) {
   conv_epilogue<BM, BN, MODE, NW, true>(p, acc, reinterpret_cast<float*>(split_smem), m0, n0);
 }
 
-template <int MODE, bool BATCH, bool PW>
+template <int MODE, bool BATCH, bool PW, int NP = 3>
 __global__ void __launch_bounds__(512, 1) k_split256(ConvArgs p) {
-  conv_split_body<MODE, BATCH, 256, 8, PW>(p);
+  conv_split_body<MODE, BATCH, 256, 8, PW, NP>(p);
 }
 
-// 0: native fp32 MFMA engine only (default), 1: large problems run on the split-bf16 engine
+// 0: native fp32 MFMA engine only (default); 1, 2, 3: large problems run on the split-bf16 engine with three, two, one
+// piece(s) per operand = six, three, one product(s). The reduced levels hold for the DIRECT launches only: the
+// Winograd-domain GEMMs run with six products under every level >= 1 (their transforms amplify operand error a
+// hundredfold, so no bound exists for a reduced product set there).
 int fp32_engine();
+// mtlssl_conv2d_engine_launches: one more tile-engine GEMM launch with 0 (native) / 6 / 3 / 1 product(s), `slot` 0..3
+void count_engine_launch(int slot);
 // Tile width for a problem of rows x cols outputs (x planes): 256 when there are enough 256 x 256 tiles for the 256 CUs
 // (one block per CU), else 0 = leave it to the native engine. The body also instantiates as a 256 x 128 tile with four
 // wavefronts and two blocks per CU (conv_split_body<.., 128, 4>, 72 KB of LDS); measured on the ROI-tower shapes that
@@ -420,7 +463,7 @@ inline int split_tile_for(int64_t rows, int64_t cols, int64_t planes = 1) {
 }
 // problems the split engine takes over from the 128x128 / 256x128 native tiles
 inline bool split_engine_takes(int cfg, int64_t rows, int64_t cols, int64_t depth, int64_t planes = 1) {
-  return fp32_engine() == 1 && (cfg == 0 || cfg == 3) && depth >= 64 && split_tile_for(rows, cols, planes) != 0;
+  return fp32_engine() >= 1 && (cfg == 0 || cfg == 3) && depth >= 64 && split_tile_for(rows, cols, planes) != 0;
 }
 // Filter gradients on the split engine: 256 x 256 tiles over [C, K] (x planes), the pixel range cut so that about two
 // blocks per CU exist (one block is resident per CU) with at least 256 pixels per cut. The workspace queries size for
@@ -438,28 +481,42 @@ inline bool split_wgrad_plan(int64_t P, int64_t C, int64_t K, int64_t planes, in
   return true;
 }
 
-template <int MODE, bool BATCH>
+template <int MODE, bool BATCH, int NP = 3>
 inline void launch_split(ConvArgs& p, dim3 extra, hipStream_t st, int tile_rows = -1) {
-  // the kernels ask for more than 64 KB of LDS: per (device, kernel), checked (common.h); a refusal shows up as the
+  constexpr int LDS = split_lds_bytes(256, NP);
+  // the kernels may ask for more than 64 KB of LDS: per (device, kernel), checked (common.h); a refusal shows up as the
   // launch error of the call below with the reason in mtlssl_last_error()
   // (per instantiation, a bitmask of the devices already done sits in front of ensure_dynamic_lds' mutex + map: this is a
   // launch path). A refusal keeps its bit clear and the launch below then fails, which the entry point's check_launch reports.
-  static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = dev < 64 ? 1ull << dev : 0ull;
-  if (!(done.load(std::memory_order_acquire) & bit) || !bit) {
-    const int rc0 = ensure_dynamic_lds((const void*)k_split256<MODE, BATCH, false>, split_lds_bytes(256), "split engine");
-    const int rc1 = ensure_dynamic_lds((const void*)k_split256<MODE, BATCH, true>, split_lds_bytes(256), "split engine");
-    if (rc0 == MTLSSL_OK && rc1 == MTLSSL_OK) done.fetch_or(bit, std::memory_order_release);
+  if constexpr (LDS > 64 * 1024) {
+    static std::atomic<unsigned long long> done{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = dev < 64 ? 1ull << dev : 0ull;
+    if (!(done.load(std::memory_order_acquire) & bit) || !bit) {
+      const int rc0 = ensure_dynamic_lds((const void*)k_split256<MODE, BATCH, false, NP>, LDS, "split engine");
+      const int rc1 = ensure_dynamic_lds((const void*)k_split256<MODE, BATCH, true, NP>, LDS, "split engine");
+      if (rc0 == MTLSSL_OK && rc1 == MTLSSL_OK) done.fetch_or(bit, std::memory_order_release);
+    }
   }
+  count_engine_launch(NP == 3 ? 1 : NP == 2 ? 2 : 3);
   p.tiles_m = tile_rows >= 0 ? tile_rows : (int)cdiv(p.M, SPLIT_BM);
   p.tiles_n = (int)cdiv(p.NG, SPLIT_BN);
   dim3 grid(p.tiles_m * p.tiles_n, extra.y, extra.z);
   const bool pw = MODE != MODE_WGRAD && p.R == 1 && p.S == 1 && p.stride == 1 && p.pt == 0 && p.pl == 0 &&
                   p.OH == p.H && p.OW == p.W;
-  if (pw) hipLaunchKernelGGL((k_split256<MODE, BATCH, true>), grid, dim3(512), split_lds_bytes(256), st, p);
-  else hipLaunchKernelGGL((k_split256<MODE, BATCH, false>), grid, dim3(512), split_lds_bytes(256), st, p);
+  if (pw) hipLaunchKernelGGL((k_split256<MODE, BATCH, true, NP>), grid, dim3(512), LDS, st, p);
+  else hipLaunchKernelGGL((k_split256<MODE, BATCH, false, NP>), grid, dim3(512), LDS, st, p);
+}
+// A direct launch at the process's level (read once: the level may change between the caller's gate and here, and a
+// launch that was gated in runs on the split engine whatever it reads)
+template <int MODE>
+inline void launch_split_direct(ConvArgs& p, dim3 extra, hipStream_t st) {
+  switch (fp32_engine()) {
+    case 2: launch_split<MODE, false, 2>(p, extra, st); break;
+    case 3: launch_split<MODE, false, 1>(p, extra, st); break;
+    default: launch_split<MODE, false, 3>(p, extra, st); break;
+  }
 }
 
 }  // namespace mtlssl

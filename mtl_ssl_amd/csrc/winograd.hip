@@ -435,9 +435,10 @@ void run_wgrad_out(const float* dU, int ns, int64_t CK, int K, const float* scal
 template <int MODE>
 void launch_gemm(int cfg, ConvArgs& p, int planes, int nz, hipStream_t st) {
   if (MODE != MODE_WGRAD && split_engine_takes(cfg, p.M, p.NG, p.C, planes)) {
-    launch_split<MODE, true>(p, dim3(1, planes, nz), st);
+    launch_split<MODE, true>(p, dim3(1, planes, nz), st);     // six products at every level >= 1 (conv_split.h)
     return;
   }
+  count_engine_launch(0);
   p.tiles_m = (int)cdiv(p.M, CFG_BM[cfg]);
   p.tiles_n = (int)cdiv(p.NG, CFG_BN[cfg]);
   dim3 grid(p.tiles_m * p.tiles_n, planes, nz);
@@ -598,7 +599,7 @@ void wgrad(const mtlssl_conv_desc* d, int tile, const float* x, const float* dy,
   float* dU = (float*)((char*)dM + align_up((int64_t)PL * g.T * d->K * 4, 256));  // [ns][P^2][C][K]
   int ns, pps;
   wgrad_split(g.T, PL, d->C, d->K, tile, &ns, &pps);
-  const bool split = fp32_engine() == 1 && (tile == 0 || tile == 3) && split_wgrad_plan(g.T, d->C, d->K, PL, &ns, &pps);
+  const bool split = fp32_engine() >= 1 && (tile == 0 || tile == 3) && split_wgrad_plan(g.T, d->C, d->K, PL, &ns, &pps);
   if (V_pre) V = const_cast<float*>(V_pre);        // kept by the forward call of the same layer
   else run_input<S>(x, V, g, d->C, st);
   run_dy<S>(dy, dM, g, d->K, st, d->ldy);

@@ -237,7 +237,8 @@ def _download(post, losses):
     return d, vals
 
 
-def main(argv=None):
+def _flags(argv):
+    from .train import FLOAT32_MATMUL_PRECISIONS
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint_dir", required=True)
     ap.add_argument("--eval_dir", default="")
@@ -250,12 +251,21 @@ def main(argv=None):
     ap.add_argument("--input_pipeline", choices=("async", "host"), default="async",
                     help="async: decode workers + on-device resize (mtl_ssl_amd.input_pipeline); host: the serial "
                          "generator input_reader.batches (the same images, bit for bit)")
-    f = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    ap.add_argument("--float32_matmul_precision", choices=FLOAT32_MATMUL_PRECISIONS, default=None,
+                    help="how the large fp32 GEMMs multiply, for the whole process (ops.set_float32_matmul_precision; "
+                         "see python -m mtl_ssl_amd.train --help). Not given: the process's setting stays")
+    return ap.parse_args(sys.argv[1:] if argv is None else argv)
+
+
+def main(argv=None):
+    f = _flags(argv)
     import torch
     import __graft_entry__ as ge
     ge.build()
     from . import checkpoint, config, eval_workflow, evaluation, model_builder, mtl_metrics, ops
     from .train import record_batches, record_paths
+    if f.float32_matmul_precision is not None:
+        ops.set_float32_matmul_precision(f.float32_matmul_precision)
     cfg = config.parse_pipeline_config(open(f.pipeline_config_path).read())
     ec = cfg.get("eval_config", config.Msg("EvalConfig"))
     use_train = str(f.eval_training_data).lower() in ("1", "true")

@@ -99,9 +99,13 @@ class Detector:
 
     _ALIGN = 256
 
-    def __init__(self, pipeline_config, checkpoint, use_moving_averages=None, input_type="image_tensor", device=None):
+    def __init__(self, pipeline_config, checkpoint, use_moving_averages=None, input_type="image_tensor", device=None,
+                 float32_matmul_precision=None):
         """pipeline_config: path of the pipeline text; checkpoint: a state file of this build (`model.ckpt.npz` or
-        its prefix) or a TensorFlow V1 / V2 checkpoint. use_moving_averages None = eval_config.use_moving_averages."""
+        its prefix) or a TensorFlow V1 / V2 checkpoint. use_moving_averages None = eval_config.use_moving_averages.
+        float32_matmul_precision: a name of ops.FP32_ENGINES ("highest", "split", "high", "medium") sets the level of the
+        large fp32 GEMMs for the whole PROCESS (ops.set_float32_matmul_precision: it is not a property of this detector,
+        and it stays after the detector is gone); None leaves the process's setting alone."""
         if input_type not in INPUT_TYPES:
             raise ValueError("Unknown input type: {}".format(input_type))
         import torch
@@ -109,6 +113,9 @@ class Detector:
         ge.build()
         from . import checkpoint as ckpt
         from . import config, model_builder
+        if float32_matmul_precision is not None:
+            from . import ops
+            ops.set_float32_matmul_precision(float32_matmul_precision)
         self.torch = torch
         cfg = config.parse_pipeline_config(open(pipeline_config).read())
         if cfg.model.faster_rcnn.first_stage_only:
@@ -129,8 +136,9 @@ class Detector:
         self._pinned = None
 
     @classmethod
-    def from_export(cls, directory, device=None):
-        """The output directory of mtl_ssl_amd.export_inference_graph (its moving averages are already applied)."""
+    def from_export(cls, directory, device=None, float32_matmul_precision=None):
+        """The output directory of mtl_ssl_amd.export_inference_graph (its moving averages are already applied).
+        float32_matmul_precision: as in the constructor (process-global; None leaves the setting alone)."""
         from .export_inference_graph import FORMAT_VERSION
         with open(os.path.join(directory, "export.json")) as fh:
             meta = json.load(fh)
@@ -138,7 +146,8 @@ class Detector:
             raise ValueError("%s: export format %s, this build reads %d"
                              % (directory, meta.get("format_version"), FORMAT_VERSION))
         return cls(os.path.join(directory, "pipeline.config"), os.path.join(directory, "model.ckpt"),
-                   use_moving_averages=False, input_type=meta["input_type"], device=device)
+                   use_moving_averages=False, input_type=meta["input_type"], device=device,
+                   float32_matmul_precision=float32_matmul_precision)
 
     def resized_shape(self, height, width):
         return self.model.resized_shape(int(height), int(width), self.config.model.faster_rcnn.image_resizer)

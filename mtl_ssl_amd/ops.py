@@ -422,8 +422,48 @@ def set_pointwise(on):
 
 def set_fp32_engine(mode):
     """0: the native fp32 MFMA engine (default), 1: large implicit GEMMs on the exact split-bf16 engine
-    (csrc/conv_split.h; MTLSSL_FP32_ENGINE=split sets the initial value). Returns the previous mode; -1 only queries."""
+    (csrc/conv_split.h; MTLSSL_FP32_ENGINE=split sets the initial value), 2 / 3: that engine's reduced levels (see
+    set_float32_matmul_precision). Returns the previous mode; -1 (or any value outside 0..3) only queries."""
     return lib().conv2d_set_fp32_engine(int(mode))
+
+
+# float32 matmul precision levels, name -> mode of mtlssl_conv2d_set_fp32_engine
+FP32_ENGINES = {"highest": 0, "split": 1, "high": 2, "medium": 3}
+_FP32_ENGINE_NAMES = {v: k for k, v in FP32_ENGINES.items()}
+
+
+def get_float32_matmul_precision():
+    """Name of the process's float32 matmul precision level (a key of FP32_ENGINES)."""
+    return _FP32_ENGINE_NAMES[lib().conv2d_set_fp32_engine(-1)]
+
+
+def set_float32_matmul_precision(name):
+    """How the large fp32 implicit GEMMs multiply (the analogue of torch.set_float32_matmul_precision):
+
+      "highest"  native fp32 MFMA (default)
+      "split"    bf16 matrix datapath, operands split exactly into three bf16 pieces, six products: as accurate as "highest"
+      "high"     operands truncated to 16 significant bits (two bf16 pieces), three products:
+                 |y - exact| <= (3 * 2^-14 + 2^-18) * sum|a||b| on top of "highest"'s own error
+      "medium"   operands rounded to one bf16 (round-to-nearest-even), one product:
+                 |y - exact| <= (2^-8 + 2^-18) * sum|a||b| on top of "highest"'s own error
+
+    "high" and "medium" apply to the direct forward / data-gradient / filter-gradient launches of the problems the
+    split engine takes (at least 192 tiles of 256 x 256); the Winograd-domain GEMMs run with six products under every
+    level but "highest", and smaller problems stay on the native engine bit for bit.
+    The setting is PROCESS-GLOBAL (one atomic in the library, read at every launch): it holds for every model, trainer
+    and detector of the process until it is set again. Returns the previous name; ValueError on an unknown one."""
+    if name not in FP32_ENGINES:
+        raise ValueError("float32 matmul precision %r: one of %s" % (name, ", ".join(FP32_ENGINES)))
+    return _FP32_ENGINE_NAMES[lib().conv2d_set_fp32_engine(FP32_ENGINES[name])]
+
+
+def engine_launches(reset=False):
+    """Tile-engine GEMM launches since the library was loaded or the last reset, by product count:
+    {"native": n, "six": n, "three": n, "one": n} (mtlssl_conv2d_engine_launches; host-side counters, process-global).
+    reset=True returns the counts and zeroes them."""
+    out = (ctypes.c_int64 * 4)()
+    lib().conv2d_engine_launches(ctypes.cast(out, ctypes.c_void_p), int(bool(reset)))
+    return dict(zip(("native", "six", "three", "one"), (int(v) for v in out)))
 
 
 def _autotune(d, mode, run):

@@ -14,6 +14,8 @@ import sys
 
 import numpy as np
 
+FLOAT32_MATMUL_PRECISIONS = ("highest", "split", "high", "medium")     # the names of ops.FP32_ENGINES
+
 
 def _flags(argv):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -47,6 +49,11 @@ def _flags(argv):
                          "that file left it (shuffle buffer, draws, waiting images; --input_pipeline=async only); restart: "
                          "the stream starts at the first record again")
     ap.add_argument("--log_every", type=int, default=10, help="steps between two printed loss lines")
+    ap.add_argument("--float32_matmul_precision", choices=FLOAT32_MATMUL_PRECISIONS, default=None,
+                    help="how the large fp32 GEMMs multiply, for the whole process (ops.set_float32_matmul_precision): "
+                         "highest = native fp32 MFMA; split = exact three-piece bf16 split, six products; high = 16 "
+                         "significant bits, three products; medium = one bf16 (round-to-nearest-even), one product. "
+                         "Not given: the process's setting stays (highest unless MTLSSL_FP32_ENGINE=split)")
     return ap.parse_args(argv)
 
 
@@ -223,7 +230,7 @@ def main(argv=None):
                       worker_replicas=world, is_chief=rank == 0, train_dir=f.train_dir, model_config=model_config,
                       num_steps=f.num_steps, aux_labels=f.aux_labels, save_summaries_secs=f.save_summaries_secs,
                       total_configs=total_configs, input_queue=stream, input_state=f.input_state,
-                      log_every=max(1, f.log_every))
+                      log_every=max(1, f.log_every), float32_matmul_precision=f.float32_matmul_precision)
     finally:
         if hasattr(stream, "close"):
             stream.close()

@@ -288,11 +288,17 @@ class Trainer:
     AUX_LABEL_MODES = ("record", "generate")
 
     def __init__(self, model, train_config, world_size=1, comm=None, reduce_always=False, aux_labels="record",
-                 aux_seed=None, aux_num_windows=64):
+                 aux_seed=None, aux_num_windows=64, float32_matmul_precision=None):
         """aux_labels: "record" = the window / closeness / edge-mask labels come with the batch (frozen when the record
         was written); "generate" = they are made on the device at every step from the batch's boxes and classes, with
         fresh windows drawn for (aux_seed or the model's seed, global step, rank * B + b); such fields of the batch are
-        ignored."""
+        ignored.
+        float32_matmul_precision: a name of ops.FP32_ENGINES ("highest", "split", "high", "medium") sets the level for
+        the whole PROCESS (ops.set_float32_matmul_precision: every model, trainer and detector of the process sees it,
+        and it stays after this trainer is gone); None leaves the process's setting alone."""
+        if float32_matmul_precision is not None:
+            from . import ops
+            ops.set_float32_matmul_precision(float32_matmul_precision)
         if aux_labels not in self.AUX_LABEL_MODES:
             raise ValueError("aux_labels %r: one of %s" % (aux_labels, ", ".join(self.AUX_LABEL_MODES)))
         self.aux_labels = aux_labels
@@ -591,7 +597,7 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
           worker_replicas=1, clone_on_cpu=False, ps_tasks=0, worker_job_name="lonely_worker",
           is_chief=True, train_dir=None, num_examples=0, total_configs=None, model_config=None,
           is_first_training=True, num_steps=None, log_every=10, save_interval_secs=600, aux_labels="record",
-          save_summaries_secs=None, input_queue=None, input_state="resume"):
+          save_summaries_secs=None, input_queue=None, input_state="resume", float32_matmul_precision=None):
     """object_detection/trainer.py:217-219 signature. `create_tensor_dict_fn()` yields one batch
     dict per call (see mtl_ssl_amd.synthetic.make_batch for the field contract);
     `create_model_fn()` returns a built FasterRCNNMetaArch. Parameter-server arguments
@@ -607,6 +613,8 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
     restore() continues from the state a resumed file holds for this rank (restore_input_state) unless input_state is
     "restart". Streams without these methods (synthetic batches) behave as before; the launcher's host generator has
     state() only, so its files carry the state and the generator itself starts afresh.
+    float32_matmul_precision: a name of ops.FP32_ENGINES sets the PROCESS-GLOBAL level of the large fp32 GEMMs
+    (ops.set_float32_matmul_precision); None leaves the process's setting alone. The first log line names the level.
     train_config.show_image_summary is accepted and ignored: the reference hands the images to
     DetectionModel.provide_image_infos (trainer.py:175-176, core/model.py:288-290), which nothing ever reads."""
     import os
@@ -617,10 +625,13 @@ def train(create_tensor_dict_fn, create_model_fn, train_config, master="", task=
     if input_state not in ("resume", "restart"):
         raise ValueError("input_state %r: resume or restart" % input_state)
     model = create_model_fn()
-    trainer = Trainer(model, train_config, world, aux_labels=aux_labels)
+    trainer = Trainer(model, train_config, world, aux_labels=aux_labels, float32_matmul_precision=float32_matmul_precision)
     if is_chief:
-        print("auxiliary labels: %s" % ("generated on the device from the boxes at every step (fresh windows per step)"
-                                        if aux_labels == "generate" else "read from the records"))
+        from . import ops
+        print("float32 matmul precision: %s; auxiliary labels: %s"
+              % (ops.get_float32_matmul_precision(),
+                 "generated on the device from the boxes at every step (fresh windows per step)"
+                 if aux_labels == "generate" else "read from the records"))
     # Resume from train_dir if a state file is there (slim.learning.train restores the latest checkpoint of
     # logdir), else initialise from fine_tune_checkpoint (trainer.py:309-356: a Saver over restore_map() that
     # FAILS when the checkpoint cannot be read). Containers: this build's .npz keyed by the reference's variable
