@@ -203,9 +203,20 @@ int mtlssl_conv2d_set_pointwise(int on);
  * known zeros out: the filter gradient walks only the 16-row K-steps of each block's unchanged pixel range that touch an
  * active group, the input gradient runs a zero-length K loop in tiles whose rows are all inactive (the epilogue still
  * writes them). Launch grids, split boundaries and the order of every sum stay as they are and a zero product leaves an
- * fp32 accumulator unchanged, so the results are BIT-IDENTICAL to the unflagged call. Every other problem (3x3, Winograd,
- * strided, the small-channel kernels, the split-bf16 engine) ignores the flags; group_active = NULL is the _xf / _ex call.
- * The filter gradient keeps its step list in the workspace (mtlssl_conv2d_wgrad_workspace_bytes covers it). */
+ * fp32 accumulator unchanged, so the results are BIT-IDENTICAL to the unflagged call.
+ * A 3x3 problem on a Winograd plan (F(4x4,3x3) or the whole-7-span variant) honours the flags too when one group is one
+ * batch entry of the descriptor (rows_per_group == H * W; any ldy) and the launch runs on the native engine. Input
+ * gradient: only the active entries' tiles are transformed, packed in ascending order into the first rows of the
+ * Winograd planes; the tiles of the GEMM stack behind them leave at once, and the output transform runs on +0 for an
+ * inactive entry (residual, accumulate and mask as usual). Filter gradient: the splits of the tile range stay as planned;
+ * inside each split the pairs of tiles that one MFMA instruction sums are kept when either tile is active and packed to
+ * the front of the split's range in ascending order — the forward's kept input transform is gathered into the workspace
+ * in that layout — and each block walks the kept K-steps only. Every accumulator still sees its nonzero terms in their
+ * order: bit-identical as well. One tiny index kernel per call builds the maps on the device (no host synchronisation);
+ * they live at the end of the workspace (mtlssl_conv2d_workspace_bytes / _wgrad_workspace_bytes cover them).
+ * Every other problem (direct 3x3, strided, the small-channel kernels, the split-bf16 engine) ignores the flags;
+ * group_active = NULL is the _xf / _ex call. The pointwise filter gradient keeps its step list in the workspace
+ * (mtlssl_conv2d_wgrad_workspace_bytes covers it). */
 int mtlssl_conv2d_dgrad_rs(const mtlssl_conv_desc* d, const float* dy, const float* w, const float* residual,
                            const float* mask_ref, float* dx, int epilogue, void* workspace, const float* filter_xf,
                            int xf_variant, const uint8_t* group_active, int rows_per_group, mtlssl_stream_t stream);

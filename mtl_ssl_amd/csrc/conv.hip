@@ -1607,8 +1607,10 @@ int mtlssl_conv2d_dgrad_rs(const mtlssl_conv_desc* d, const float* dy, const flo
   const Route r = route(d, MODE_DGRAD, workspace != nullptr);
   switch (r.family) {
     case FAM_WINO:
+      // flags of whole batch entries reach the Winograd family: one 7x7 RoI is one M7 tile, th * tw tiles of F43
       wino_dgrad(d, r.wc.variant, r.wc.tile, dy, w, residual, mask_ref, dx, epi, workspace, S(stream),
-                 (filter_xf && xf_variant == r.wc.variant) ? filter_xf : nullptr);
+                 (filter_xf && xf_variant == r.wc.variant) ? filter_xf : nullptr,
+                 (group_active && row_skip_ref().load() != 0 && rows_per_group == d->H * d->W) ? group_active : nullptr);
       break;
     case FAM_PARITY:
       parity_dgrad(r, d, dy, w, residual, mask_ref, dx, epi, workspace, S(stream));
@@ -1757,6 +1759,12 @@ int mtlssl_conv2d_plan_info(const mtlssl_conv_desc* d, int mode, int parity_clas
     case FAM_WINO:
       if (r.wc.variant != 0) out[0] = MTLSSL_PLAN_WINO_M7;
       out[2] = r.wc.tile; out[3] = 1;
+      if (mode == MODE_WGRAD) {        // the split of the tile range (the GEMM stack's reduction), in tiles
+        int ns, pps;
+        wino_wgrad_split(d, r.wc.variant, r.wc.tile, &ns, &pps);
+        const int64_t T = wino_input_bytes(d, r.wc.variant) / ((r.wc.variant != 0 ? 121 : 36) * 4 * (int64_t)d->C);
+        out[3] = ns; out[4] = pps / BK; out[8] = (int32_t)cdiv(T, BK); out[13] = pps;
+      }
       out[9] = (int32_t)(mode == MODE_WGRAD ? d->C : M);
       out[10] = mode == MODE_DGRAD ? d->C : d->K;
       out[11] = CFG_BM[r.wc.tile]; out[12] = CFG_BN[r.wc.tile];
@@ -1894,7 +1902,8 @@ int mtlssl_conv2d_wgrad_rs(const mtlssl_conv_desc* d, const float* x, const floa
   switch (r.family) {
     case FAM_WINO:
       wino_wgrad(d, r.wc.variant, r.wc.tile, x, dy, out_scale, dw, beta, ws_main, st,
-                 (input_xf && input_variant == r.wc.variant) ? input_xf : nullptr);
+                 (input_xf && input_variant == r.wc.variant) ? input_xf : nullptr,
+                 (group_active && row_skip_ref().load() != 0 && rows_per_group == d->OH * d->OW) ? group_active : nullptr);
       break;
     case FAM_DIRECT: {
       const bool split = wgrad_on_split_engine(r, d);

@@ -54,7 +54,8 @@ struct ConvArgs {
   // problem * nsplit + split; the partial tiles land in the workspace in that order
   const float* const* a_tab;
   const float* const* b_tab;
-  // Row-group activity of a pointwise dgrad / wgrad (mtlssl_conv2d_dgrad_rs / _wgrad_rs): the caller's promise that every
+  // Row-group activity of a pointwise dgrad / wgrad (mtlssl_conv2d_dgrad_rs / _wgrad_rs; the Winograd-domain GEMM stacks
+  // of a flagged 3x3 call carry it in packed rows, winograd.hip): the caller's promise that every
   // dy row of an inactive group is exactly zero. A zero product leaves an fp32 accumulator as it is (and one that starts
   // at +0 never turns -0), so leaving those rows out changes no bit of the result.
   const uint8_t* group_active;   // dgrad: one flag per group of `rows_per_group` consecutive GEMM rows; nullptr = all live
@@ -268,6 +269,11 @@ __device__ __forceinline__ void conv_mfma_body(ConvArgs p, const SegArgs sg = Se
     int q = nwg / 8, r = nwg % 8, xcd = bid % 8, loc = bid / 8;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
   }
+  // Flagged Winograd-domain stack: the live rows are packed into the first tile rows of EVERY plane, which the order
+  // above hands to the same one or two XCDs plane after plane. Shift each plane's order by one XCD's share of tiles, so
+  // that the live tiles of the stack go round all eight (which block computes which tile changes no sum).
+  if constexpr (BATCH && MODE == MODE_DGRAD)
+    if (p.group_active) bid = (int)((bid + (unsigned)blockIdx.y * ((nwg + 7) / 8)) % (unsigned)nwg);
   const int tile_m = bid / p.tiles_n + p.tile_m0, tile_n = bid % p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -303,7 +309,7 @@ __device__ __forceinline__ void conv_mfma_body(ConvArgs p, const SegArgs sg = Se
     pix0 = split * p.pix_per_split;
     pix1 = min(P, pix0 + p.pix_per_split);
     ksteps = (max(pix1 - pix0, 0) + BKT - 1) / BKT;
-    if constexpr (PW && !BATCH)
+    if constexpr (PW)
       if (p.k_steps) {             // same pixel range, same order: only the steps of all-zero dy rows are left out
         steps = p.k_steps + KSTEP_HDR + split * p.k_stride;
         ksteps = p.k_steps[split];
@@ -326,8 +332,12 @@ __device__ __forceinline__ void conv_mfma_body(ConvArgs p, const SegArgs sg = Se
   }
   // flagged pointwise dgrad: a tile of all-zero dy rows runs a zero-length K loop; its epilogue (residual, mask,
   // accumulate, split-K partial) still writes the tile
-  if constexpr (PW && MODE == MODE_DGRAD && !SEG && !BATCH)
-    if (p.group_active && !tile_rows_active(p, m0, BM)) ksteps = ks_begin;
+  // (a tile of a Winograd-domain stack leaves at once: its rows lie behind the packed ones and nobody reads them)
+  if constexpr (PW && MODE == MODE_DGRAD && !SEG)
+    if (p.group_active && !tile_rows_active(p, m0, BM)) {
+      if constexpr (BATCH) return;
+      ksteps = ks_begin;
+    }
 
   // ---- per-thread gather state (32-bit element offsets; the host guarantees < 2^30 elements)
   // KC loaders: thread -> (row = tid/4 + 64*i, 4 consecutive k at kq4)
@@ -747,6 +757,11 @@ __device__ __forceinline__ void conv_glds_body(ConvArgs p) {
     int q = nwg / 8, r = nwg % 8, xcd = bid % 8, loc = bid / 8;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
   }
+  // Flagged Winograd-domain stack: the live rows are packed into the first tile rows of EVERY plane, which the order
+  // above hands to the same one or two XCDs plane after plane. Shift each plane's order by one XCD's share of tiles, so
+  // that the live tiles of the stack go round all eight (which block computes which tile changes no sum).
+  if constexpr (BATCH && MODE == MODE_DGRAD)
+    if (p.group_active) bid = (int)((bid + (unsigned)blockIdx.y * ((nwg + 7) / 8)) % (unsigned)nwg);
   const int tile_m = bid / p.tiles_n + p.tile_m0, tile_n = bid % p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -774,7 +789,7 @@ __device__ __forceinline__ void conv_glds_body(ConvArgs p) {
     pix0 = split * p.pix_per_split;
     pix1 = min(P, pix0 + p.pix_per_split);
     ksteps = (max(pix1 - pix0, 0) + BKT - 1) / BKT;
-    if constexpr (PWISE && !BATCH)
+    if constexpr (PWISE)
       if (p.k_steps) {             // flagged pointwise wgrad: see conv_mfma_body
         steps = p.k_steps + KSTEP_HDR + split * p.k_stride;
         ksteps = p.k_steps[split];
@@ -786,8 +801,11 @@ __device__ __forceinline__ void conv_glds_body(ConvArgs p) {
       ksteps = min(ksteps, ks_begin + p.ks_per_split);
     }
   }
-  if constexpr (PWISE && MODE == MODE_DGRAD && !BATCH)     // flagged pointwise dgrad: see conv_mfma_body
-    if (p.group_active && !tile_rows_active(p, m0, BM)) ksteps = ks_begin;
+  if constexpr (PWISE && MODE == MODE_DGRAD)               // flagged pointwise dgrad: see conv_mfma_body
+    if (p.group_active && !tile_rows_active(p, m0, BM)) {
+      if constexpr (BATCH) return;
+      ksteps = ks_begin;
+    }
 
   const int ldy = args_ldy(p);                       // row stride of dy (A of dgrad, B of wgrad)
   unsigned a_rec = p.a_bytes, b_rec = p.b_bytes;     // pointwise wgrad: see conv_mfma_body
@@ -1250,13 +1268,17 @@ void wino_fwd(const mtlssl_conv_desc* d, int variant, int tile, const float* x, 
 int64_t wino_input_bytes(const mtlssl_conv_desc* d, int variant);
 void wino_dgrad(const mtlssl_conv_desc* d, int variant, int tile, const float* dy, const float* w,
                 const float* residual, const float* mask_ref, float* dx, int epi, void* workspace, hipStream_t st,
-                const float* filter_xf = nullptr);
+                const float* filter_xf = nullptr, const uint8_t* batch_active = nullptr);
 int64_t wino_filter_bytes(const mtlssl_conv_desc* d, int variant);
 void wino_filter(const mtlssl_conv_desc* d, int variant, int flip, const float* w, float* U, hipStream_t st);
 void wino_filters_batched(int variant, int n, const void* w_ptrs, const void* u_ptrs, const int64_t* ck,
                           const int32_t* flip, int64_t max_ck, hipStream_t st);
 void wino_wgrad(const mtlssl_conv_desc* d, int variant, int tile, const float* x, const float* dy,
                 const float* out_scale, float* dw, float beta, void* workspace, hipStream_t st,
-                const float* input_xf = nullptr);
+                const float* input_xf = nullptr, const uint8_t* batch_active = nullptr);
+// batch_active (both calls above): one byte per batch entry of the descriptor, 0 = its dy is exactly zero, nullptr = no
+// promise. The native engine then packs the active tiles (dgrad) / MFMA row pairs (wgrad) to the front of the Winograd
+// planes and skips the rest of the GEMM stack; the results keep every bit (winograd.hip, k_wino_active_*).
+void wino_wgrad_split(const mtlssl_conv_desc* d, int variant, int tile, int* ns, int* pps);
 
 }  // namespace mtlssl

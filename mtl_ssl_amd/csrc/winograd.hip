@@ -109,9 +109,15 @@ struct WinoGeom {
 // straddles a row) — the wide problems; VT = float: one channel per thread, four times the threads —
 // the narrow ones (a block3 unit has 320 tiles x 256 channels), which are latency- not bandwidth-bound,
 // and M7, whose 11x11 working set does not fit the registers four channels wide.
-struct TileIdx { int64_t t; int c, n, ty, tx; bool ok; };
+//
+// Row maps of a flagged backward call (k_wino_active_tiles / k_wino_active_pairs below). `row_src` != nullptr: plane row
+// t is not tile t's but holds the tile row_src[t] (ROW_ZERO: the row is zero fill, ROW_SKIP: nobody reads the row and the
+// thread leaves at once) — (n, ty, tx) then name the tile that is read, t the row that is written. In `slot` form (the
+// output transform) the map is used the other way round: slot[t] is the plane row that holds tile t, or < 0.
+constexpr int ROW_ZERO = -1, ROW_SKIP = -2;
+struct TileIdx { int64_t t; int c, n, ty, tx; bool ok, zero; };
 template <typename VT>
-__device__ __forceinline__ TileIdx tile_index(const WinoGeom& g, int C) {
+__device__ __forceinline__ TileIdx tile_index(const WinoGeom& g, int C, const int* row_src = nullptr) {
   constexpr int VW = sizeof(VT) / 4;
   TileIdx r;
   const int cq = C / VW;
@@ -119,8 +125,16 @@ __device__ __forceinline__ TileIdx tile_index(const WinoGeom& g, int C) {
   r.ok = idx < g.T * cq;
   r.c = (int)(idx % cq) * VW;
   r.t = idx / cq;
-  r.tx = (int)(r.t % g.tw);
-  int64_t q = r.t / g.tw;
+  r.zero = false;
+  int64_t src = r.t;
+  if (row_src && r.ok) {
+    const int m = row_src[r.t];
+    r.ok = m != ROW_SKIP;
+    r.zero = m == ROW_ZERO;
+    src = m < 0 ? 0 : m;
+  }
+  r.tx = (int)(src % g.tw);
+  int64_t q = src / g.tw;
   r.ty = (int)(q % g.th);
   r.n = (int)(q / g.th);
   return r;
@@ -191,9 +205,10 @@ __global__ void __launch_bounds__(256) k_wino_filter_batched(const float* const*
 // zero outside the map). The patch is streamed a column at a time, the column-transformed P x I block is
 // held in registers, then rows are transformed and stored plane by plane.
 template <typename S, typename VT>
-__global__ void __launch_bounds__(256) k_wino_input(const float* in, float* V, WinoGeom g, int C, int ld) {
+__global__ void __launch_bounds__(256) k_wino_input(const float* in, float* V, WinoGeom g, int C, int ld,
+                                                    const int* row_src) {
   constexpr int P = S::P, I = S::I;
-  const TileIdx ix = tile_index<VT>(g, C);
+  const TileIdx ix = tile_index<VT>(g, C, row_src);
   if (!ix.ok) return;
   const int y0 = S::O * ix.ty - 1, x0 = S::O * ix.tx - 1;
   const float* base = in + ((int64_t)ix.n * g.H * g.W) * ld + ix.c;     // ld: row stride of `in` (>= C: a channel slice)
@@ -201,7 +216,7 @@ __global__ void __launch_bounds__(256) k_wino_input(const float* in, float* V, W
 #pragma unroll
   for (int j = 0; j < I; ++j) {
     const int x = x0 + j;
-    const bool okx = (unsigned)x < (unsigned)g.W;
+    const bool okx = (unsigned)x < (unsigned)g.W && !ix.zero;
     VT col[I], o[P];
 #pragma unroll
     for (int i = 0; i < I; ++i) {
@@ -227,9 +242,10 @@ __global__ void __launch_bounds__(256) k_wino_input(const float* in, float* V, W
 // Output-gradient transform for the filter gradient: dM[xi][t][k] = (A dY A^T)[xi] of the O x O
 // tile of dY (zero outside the map).
 template <typename S, typename VT>
-__global__ void __launch_bounds__(256) k_wino_dy(const float* dy, float* dM, WinoGeom g, int K, int ld) {
+__global__ void __launch_bounds__(256) k_wino_dy(const float* dy, float* dM, WinoGeom g, int K, int ld,
+                                                 const int* row_src) {
   constexpr int P = S::P, O = S::O;
-  const TileIdx ix = tile_index<VT>(g, K);
+  const TileIdx ix = tile_index<VT>(g, K, row_src);
   if (!ix.ok) return;
   const float* base = dy + ((int64_t)ix.n * g.H * g.W) * ld + ix.c;    // ld: row stride of dy
   VT tmp[P][O];
@@ -240,7 +256,7 @@ __global__ void __launch_bounds__(256) k_wino_dy(const float* dy, float* dM, Win
 #pragma unroll
     for (int i = 0; i < O; ++i) {
       const int y = O * ix.ty + i;
-      const bool ok = y < g.H && x < g.W;
+      const bool ok = y < g.H && x < g.W && !ix.zero;
       col[i] = ok ? *reinterpret_cast<const VT*>(base + ((int64_t)y * g.W + x) * ld) : VT{};
     }
     xform<S, XF_A, P, O>(col, o);
@@ -263,18 +279,22 @@ __global__ void __launch_bounds__(256) k_wino_dy(const float* dy, float* dM, Win
 template <typename S, int MODE, typename VT>
 __global__ void __launch_bounds__(256) k_wino_output(const float* Mb, float* out, WinoGeom g, int K, int ldo,
                                                      const float* bias, const float* residual,
-                                                     const float* mask, int epi) {
+                                                     const float* mask, int epi, const int* slot) {
   constexpr int P = S::P, O = S::O;
   const TileIdx ix = tile_index<VT>(g, K);
   if (!ix.ok) return;
   const int64_t plane = g.T * K;
-  const float* mp = Mb + ix.t * K + ix.c;
+  // flagged input gradient: tile t's products sit in plane row slot[t]; a tile without a row (an all-zero RoI) is
+  // transformed from +0 by the same code and takes the same epilogue — no row of Mb is read for it
+  const int row = slot ? slot[ix.t] : 0;
+  const bool live = row >= 0;
+  const float* mp = Mb + (slot ? (int64_t)(live ? row : 0) : ix.t) * K + ix.c;
   VT tmp[O][P];
 #pragma unroll
   for (int b = 0; b < P; ++b) {
     VT col[P], o[O];
 #pragma unroll
-    for (int a = 0; a < P; ++a) col[a] = *reinterpret_cast<const VT*>(mp + (int64_t)(a * P + b) * plane);
+    for (int a = 0; a < P; ++a) col[a] = live ? *reinterpret_cast<const VT*>(mp + (int64_t)(a * P + b) * plane) : VT{};
     xform<S, XF_AT, O, P>(col, o);
 #pragma unroll
     for (int u = 0; u < O; ++u) tmp[u][b] = o[u];
@@ -356,6 +376,97 @@ __global__ void __launch_bounds__(256) k_wino_wgrad_out(const float* dU, int nsp
   }
 }
 
+// ---- row-group activity (mtlssl_conv2d_dgrad_rs / _wgrad_rs on a Winograd plan). A group is one batch entry = `tpg`
+// consecutive tiles (M7 on a 7x7 RoI: one), flag 0 = the caller vouches that its dy is exactly zero. Both kernels follow
+// k_active_ksteps (conv.hip): ballot + popcount, ascending order, every count stays on the device.
+//
+// Input gradient: the active tiles are packed, ascending, into plane rows [0, n_active). row_src[r] = tile of row r
+// (ROW_SKIP from n_active on), slot[t] = row of tile t or -1, gflags[i] = "rows [64 i, 64 i + 64) hold a packed tile":
+// the GEMM stack's group flags, in packed rows.
+__global__ void __launch_bounds__(256) k_wino_active_tiles(const uint8_t* __restrict__ flags, int tpg, int T,
+                                                           int* __restrict__ slot, int* __restrict__ row_src,
+                                                           uint8_t* __restrict__ gflags) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ int wave_cnt[4];
+  int base = 0;
+  for (int t0 = 0; t0 < T; t0 += 256) {
+    const int t = t0 + threadIdx.x;
+    const bool act = t < T && flags[t / tpg] != 0;
+    const unsigned long long m = __ballot(act);
+    if (lane == 0) wave_cnt[w] = __popcll(m);
+    __syncthreads();
+    int off = base;
+    for (int i = 0; i < w; ++i) off += wave_cnt[i];
+    const int row = off + __popcll(m & ((1ull << lane) - 1ull));
+    if (t < T) slot[t] = act ? row : -1;
+    if (act) row_src[row] = t;
+    base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    __syncthreads();
+  }
+  for (int r = base + threadIdx.x; r < T; r += 256) row_src[r] = ROW_SKIP;
+  for (int i = threadIdx.x; i < (T + 63) / 64; i += 256) gflags[i] = i * 64 < base;
+}
+// Filter gradient: the reduction runs over tiles, so what is packed is the unit one MFMA instruction sums — the two rows
+// of a 16-row K-step that v_mfma_f32_32x32x2_f32 takes together: (2p, 2p + 1) in the register-staged body, (p, p + 8) in
+// the LDS-DMA body (`glds`), p = 0..7 in the order the instructions run. Block z = split z of the launch, tiles
+// [z * pps, min(T, (z + 1) * pps)), pps a multiple of 16. A pair is kept when either tile is active; the kept pairs move,
+// ascending, to the front of the split's own range, so every accumulator sees its nonzero terms in the order it did.
+// row_src[r] = tile whose transform plane row r holds, ROW_ZERO for the rest of the last kept K-step (and a kept pair's
+// row past the range), ROW_SKIP behind it; out[z] = kept K-steps, out[KSTEP_HDR + z * stride + i] = i: the list the GEMM
+// blocks of the split walk (ConvArgs.k_steps).
+__global__ void __launch_bounds__(256) k_wino_active_pairs(const uint8_t* __restrict__ flags, int tpg, int T, int pps, int glds,
+                                                           int stride, int* __restrict__ row_src, int* __restrict__ out) {
+  const int z = blockIdx.x, pix0 = z * pps, pix1 = min(T, pix0 + pps);
+  const int npairs = (max(pix1 - pix0, 0) + BK - 1) / BK * (BK / 2);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  auto row_of = [&](int q, int h) { return pix0 + BK * (q >> 3) + (glds ? (q & 7) + 8 * h : 2 * (q & 7) + h); };
+  auto live = [&](int r) { return r < pix1 && flags[r / tpg] != 0; };
+  __shared__ int wave_cnt[4];
+  int base = 0;
+  for (int q0 = 0; q0 < npairs; q0 += 256) {
+    const int q = q0 + threadIdx.x;
+    const bool act = q < npairs && (live(row_of(q, 0)) || live(row_of(q, 1)));
+    const unsigned long long m = __ballot(act);
+    if (lane == 0) wave_cnt[w] = __popcll(m);
+    __syncthreads();
+    int off = base;
+    for (int i = 0; i < w; ++i) off += wave_cnt[i];
+    if (act) {
+      const int j = off + __popcll(m & ((1ull << lane) - 1ull));      // j <= q: a row never moves up, so dst <= src
+      for (int h = 0; h < 2; ++h) {
+        const int dst = row_of(j, h), src = row_of(q, h);
+        if (dst < pix1) row_src[dst] = src < pix1 ? src : ROW_ZERO;
+      }
+    }
+    base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    __syncthreads();
+  }
+  const int ksteps = (base + 7) / 8;
+  for (int j = base + threadIdx.x; j < npairs; j += 256)
+    for (int h = 0; h < 2; ++h) {
+      const int dst = row_of(j, h);
+      if (dst < pix1) row_src[dst] = j < ksteps * 8 ? ROW_ZERO : ROW_SKIP;
+    }
+  if (threadIdx.x == 0) out[z] = ksteps;
+  for (int i = threadIdx.x; i < ksteps; i += 256) out[KSTEP_HDR + (int64_t)z * stride + i] = i;
+}
+// The forward's kept V = B^T x B (every tile in its own row) gathered into the packed rows of the workspace's planes
+// (blockIdx.y = plane), with the same zero fill as the transforms.
+__global__ void __launch_bounds__(256) k_wino_gather_rows(const float* __restrict__ src, float* __restrict__ dst,
+                                                          const int* __restrict__ row_src, int64_t T, int C) {
+  const int cq = C / 4;
+  const int64_t idx = blockIdx.x * (int64_t)256 + threadIdx.x;
+  if (idx >= T * cq) return;
+  const int64_t r = idx / cq;
+  const int c = (int)(idx % cq) * 4;
+  const int m = row_src[r];
+  if (m == ROW_SKIP) return;
+  const int64_t plane = (int64_t)blockIdx.y * T * C;
+  floatx4 v = {0.f, 0.f, 0.f, 0.f};
+  if (m >= 0) v = *reinterpret_cast<const floatx4*>(src + plane + (int64_t)m * C + c);
+  *reinterpret_cast<floatx4*>(dst + plane + r * C + c) = v;
+}
+
 // ---- host side
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 
@@ -383,40 +494,44 @@ void run_filter(const float* w, float* U, int64_t CK, int flip, hipStream_t st) 
   hipLaunchKernelGGL((k_wino_filter<S, float>), dim3(cdiv(CK, 256)), dim3(256), 0, st, w, U, CK, flip);
 }
 template <typename S>
-void run_input(const float* in, float* V, const WinoGeom& g, int C, hipStream_t st, int ld = 0) {
+void run_input(const float* in, float* V, const WinoGeom& g, int C, hipStream_t st, int ld = 0,
+               const int* row_src = nullptr) {
   if (ld <= 0) ld = C;
   if constexpr (can_vec<S>()) {
     if (wide(g.T, C)) {
-      hipLaunchKernelGGL((k_wino_input<S, floatx4>), dim3(cdiv(g.T * C / 4, 256)), dim3(256), 0, st, in, V, g, C, ld);
+      hipLaunchKernelGGL((k_wino_input<S, floatx4>), dim3(cdiv(g.T * C / 4, 256)), dim3(256), 0, st, in, V, g, C, ld,
+                         row_src);
       return;
     }
   }
-  hipLaunchKernelGGL((k_wino_input<S, float>), dim3(cdiv(g.T * C, 256)), dim3(256), 0, st, in, V, g, C, ld);
+  hipLaunchKernelGGL((k_wino_input<S, float>), dim3(cdiv(g.T * C, 256)), dim3(256), 0, st, in, V, g, C, ld, row_src);
 }
 template <typename S>
-void run_dy(const float* dy, float* dM, const WinoGeom& g, int K, hipStream_t st, int ld = 0) {
+void run_dy(const float* dy, float* dM, const WinoGeom& g, int K, hipStream_t st, int ld = 0,
+            const int* row_src = nullptr) {
   if (ld <= 0) ld = K;
   if constexpr (can_vec<S>()) {
     if (wide(g.T, K)) {
-      hipLaunchKernelGGL((k_wino_dy<S, floatx4>), dim3(cdiv(g.T * K / 4, 256)), dim3(256), 0, st, dy, dM, g, K, ld);
+      hipLaunchKernelGGL((k_wino_dy<S, floatx4>), dim3(cdiv(g.T * K / 4, 256)), dim3(256), 0, st, dy, dM, g, K, ld,
+                         row_src);
       return;
     }
   }
-  hipLaunchKernelGGL((k_wino_dy<S, float>), dim3(cdiv(g.T * K, 256)), dim3(256), 0, st, dy, dM, g, K, ld);
+  hipLaunchKernelGGL((k_wino_dy<S, float>), dim3(cdiv(g.T * K, 256)), dim3(256), 0, st, dy, dM, g, K, ld, row_src);
 }
 template <typename S, int MODE>
 void run_output(const float* Mb, float* out, const WinoGeom& g, int K, const float* bias, const float* residual,
-                const float* mask, int epi, hipStream_t st, int ldo = 0) {
+                const float* mask, int epi, hipStream_t st, int ldo = 0, const int* slot = nullptr) {
   if (ldo <= 0) ldo = K;
   if constexpr (can_vec<S>()) {
     if (wide(g.T, K)) {
       hipLaunchKernelGGL((k_wino_output<S, MODE, floatx4>), dim3(cdiv(g.T * K / 4, 256)), dim3(256), 0, st, Mb, out,
-                         g, K, ldo, bias, residual, mask, epi);
+                         g, K, ldo, bias, residual, mask, epi, slot);
       return;
     }
   }
   hipLaunchKernelGGL((k_wino_output<S, MODE, float>), dim3(cdiv(g.T * K, 256)), dim3(256), 0, st, Mb, out, g, K, ldo,
-                     bias, residual, mask, epi);
+                     bias, residual, mask, epi, slot);
 }
 template <typename S>
 void run_wgrad_out(const float* dU, int ns, int64_t CK, int K, const float* scale, float* dw, float beta,
@@ -529,11 +644,19 @@ double time_us(const mtlssl_conv_desc* d, int mode, int* tile) {
   return tg + bytes / 4.0e6 + 12.0;
 }
 
+// The row maps of a flagged backward call, at the very end of the workspace: input gradient slot[Tp], row_src[Tp],
+// gflags[Tp / 64] (bytes); filter gradient row_src[Tp], then the K-step list (KSTEP_HDR counts + at most Tp / 16 + 16
+// entries: wgrad_split plans at most 16 splits, each rounded up to whole K-steps). Tp = T rounded up to 64.
+inline int64_t index_bytes(int64_t T) {
+  const int64_t Tp = align_up(T, 64);
+  return align_up((2 * Tp + KSTEP_HDR + Tp / 16 + 16) * 4 + Tp / 64, 256);
+}
 template <typename S>
 int64_t workspace_bytes(const mtlssl_conv_desc* d, int mode) {
   constexpr int PL = S::P * S::P;
   WinoGeom g = geom<S>(d);
   int64_t planes = align_up((int64_t)PL * g.T * d->C * 4, 256) + align_up((int64_t)PL * g.T * d->K * 4, 256);
+  if (mode != MODE_FWD) planes += index_bytes(g.T);
   if (mode == MODE_WGRAD) {
     int ns = 1, pps;
     int64_t mx = 1;    // the split depends on the tile; size for the largest split any tile would ask for
@@ -569,7 +692,8 @@ void fwd(const mtlssl_conv_desc* d, int tile, const float* x, const float* w, co
 
 template <typename S>
 void dgrad(const mtlssl_conv_desc* d, int tile, const float* dy, const float* w, const float* residual,
-           const float* mask_ref, float* dx, int epi, void* workspace, hipStream_t st, const float* U_pre = nullptr) {
+           const float* mask_ref, float* dx, int epi, void* workspace, hipStream_t st, const float* U_pre = nullptr,
+           const uint8_t* active = nullptr) {
   constexpr int PL = S::P * S::P;
   WinoGeom g = geom<S>(d);
   const int64_t CK = (int64_t)d->C * d->K;
@@ -578,19 +702,34 @@ void dgrad(const mtlssl_conv_desc* d, int tile, const float* dy, const float* w,
   float* Mb = (float*)((char*)V + align_up((int64_t)PL * g.T * d->K * 4, 256));   // [P^2][T][C]
   if (U_pre) U = const_cast<float*>(U_pre);
   else run_filter<S>(w, U, CK, 1, st);
-  run_input<S>(dy, V, g, d->K, st, d->ldy);
   ConvArgs p = gemm_args(g.T, d->C, d->K);
   p.a = V; p.b = U; p.out = Mb;
   p.M = (int)g.T; p.NG = d->C;
   p.a_bytes = (unsigned)(g.T * d->K * 4); p.b_bytes = (unsigned)(CK * 4);
   p.a_bs = g.T * d->K; p.b_bs = CK; p.o_bs = g.T * d->C;
+  // Flagged call (one flag per batch entry; the split engine never looks at flags): the active tiles' transformed dy goes
+  // to rows [0, n_active) of V, the GEMM tiles behind them leave at once (rows of V and Mb past n_active may be read by
+  // the tile that straddles n_active, never by the output transform), and the output transform finds its tile's row
+  // through `slot`; a tile without a row is transformed from +0 and takes the normal epilogue.
+  const int* slot = nullptr;
+  const int* row_src = nullptr;
+  if (active && !split_engine_takes(tile, p.M, p.NG, p.C, PL)) {
+    const int64_t Tp = align_up(g.T, 64);
+    int* maps = (int*)((char*)workspace + workspace_bytes<S>(d, MODE_DGRAD) - index_bytes(g.T));
+    uint8_t* gflags = (uint8_t*)(maps + 2 * Tp);
+    hipLaunchKernelGGL(k_wino_active_tiles, dim3(1), dim3(256), 0, st, active, g.th * g.tw, (int)g.T, maps, maps + Tp, gflags);
+    slot = maps; row_src = maps + Tp;
+    p.group_active = gflags; p.rows_per_group = 64;
+  }
+  run_input<S>(dy, V, g, d->K, st, d->ldy, row_src);
   launch_gemm<MODE_DGRAD>(tile, p, PL, 1, st);
-  run_output<S, MODE_DGRAD>(Mb, dx, g, d->C, nullptr, residual, mask_ref, epi, st);
+  run_output<S, MODE_DGRAD>(Mb, dx, g, d->C, nullptr, residual, mask_ref, epi, st, 0, slot);
 }
 
 template <typename S>
 void wgrad(const mtlssl_conv_desc* d, int tile, const float* x, const float* dy, const float* out_scale,
-           float* dw, float beta, void* workspace, hipStream_t st, const float* V_pre = nullptr) {
+           float* dw, float beta, void* workspace, hipStream_t st, const float* V_pre = nullptr,
+           const uint8_t* active = nullptr) {
   constexpr int PL = S::P * S::P;
   WinoGeom g = geom<S>(d);
   const int64_t CK = (int64_t)d->C * d->K;
@@ -600,10 +739,24 @@ void wgrad(const mtlssl_conv_desc* d, int tile, const float* x, const float* dy,
   int ns, pps;
   wgrad_split(g.T, PL, d->C, d->K, tile, &ns, &pps);
   const bool split = fp32_engine() >= 1 && (tile == 0 || tile == 3) && split_wgrad_plan(g.T, d->C, d->K, PL, &ns, &pps);
-  if (V_pre) V = const_cast<float*>(V_pre);        // kept by the forward call of the same layer
-  else run_input<S>(x, V, g, d->C, st);
-  run_dy<S>(dy, dM, g, d->K, st, d->ldy);
   ConvArgs p = gemm_args(g.T, d->C, d->K);
+  // Flagged call on the native engine: both operands in the packed row layout of k_wino_active_pairs — the forward's kept
+  // V is gathered into the workspace's own planes — and every split's blocks walk the split's kept K-steps only. Splits,
+  // grid and k_wino_wgrad_out are those of the unflagged call.
+  const int* row_src = nullptr;
+  if (active && !split && ns <= KSTEP_HDR) {
+    int* maps = (int*)((char*)workspace + workspace_bytes<S>(d, MODE_WGRAD) - index_bytes(g.T));
+    int* list = maps + align_up(g.T, 64);
+    hipLaunchKernelGGL(k_wino_active_pairs, dim3(ns), dim3(256), 0, st, active, g.th * g.tw, (int)g.T, pps,
+                       tile >= NCFG ? 1 : 0, pps / BK, maps, list);
+    row_src = maps;
+    p.k_steps = list; p.k_stride = pps / BK;
+  }
+  if (V_pre && row_src)
+    hipLaunchKernelGGL(k_wino_gather_rows, dim3(cdiv(g.T * d->C / 4, 256), PL), dim3(256), 0, st, V_pre, V, row_src, g.T, d->C);
+  else if (V_pre) V = const_cast<float*>(V_pre);   // kept by the forward call of the same layer
+  else run_input<S>(x, V, g, d->C, st, 0, row_src);
+  run_dy<S>(dy, dM, g, d->K, st, d->ldy, row_src);
   p.a = V; p.b = dM; p.out = dU;
   p.M = d->C; p.NG = d->K; p.nsplit = ns; p.pix_per_split = pps;
   p.a_bytes = (unsigned)(g.T * d->C * 4); p.b_bytes = (unsigned)(g.T * d->K * 4);
@@ -640,9 +793,9 @@ int64_t wino_input_bytes(const mtlssl_conv_desc* d, int variant) {
 }
 void wino_dgrad(const mtlssl_conv_desc* d, int variant, int tile, const float* dy, const float* w,
                 const float* residual, const float* mask_ref, float* dx, int epi, void* workspace, hipStream_t st,
-                const float* filter_xf) {
-  if (variant == WINO_M7) dgrad<M7>(d, tile, dy, w, residual, mask_ref, dx, epi, workspace, st, filter_xf);
-  else dgrad<F43>(d, tile, dy, w, residual, mask_ref, dx, epi, workspace, st, filter_xf);
+                const float* filter_xf, const uint8_t* batch_active) {
+  if (variant == WINO_M7) dgrad<M7>(d, tile, dy, w, residual, mask_ref, dx, epi, workspace, st, filter_xf, batch_active);
+  else dgrad<F43>(d, tile, dy, w, residual, mask_ref, dx, epi, workspace, st, filter_xf, batch_active);
 }
 // The transformed filter U = G g G^T of one layer ([P^2][C][K]; `flip`: the dgrad form) on its own, so that a
 // caller can compute it once per optimizer step instead of once per convolution call.
@@ -666,9 +819,17 @@ void wino_filter(const mtlssl_conv_desc* d, int variant, int flip, const float* 
   else run_filter<F43>(w, U, CK, flip, st);
 }
 void wino_wgrad(const mtlssl_conv_desc* d, int variant, int tile, const float* x, const float* dy,
-                const float* out_scale, float* dw, float beta, void* workspace, hipStream_t st, const float* input_xf) {
-  if (variant == WINO_M7) wgrad<M7>(d, tile, x, dy, out_scale, dw, beta, workspace, st, input_xf);
-  else wgrad<F43>(d, tile, x, dy, out_scale, dw, beta, workspace, st, input_xf);
+                const float* out_scale, float* dw, float beta, void* workspace, hipStream_t st, const float* input_xf,
+                const uint8_t* batch_active) {
+  if (variant == WINO_M7) wgrad<M7>(d, tile, x, dy, out_scale, dw, beta, workspace, st, input_xf, batch_active);
+  else wgrad<F43>(d, tile, x, dy, out_scale, dw, beta, workspace, st, input_xf, batch_active);
+}
+// The split of the tile range a filter gradient of (d, variant, tile) runs with (mtlssl_conv2d_plan_info).
+void wino_wgrad_split(const mtlssl_conv_desc* d, int variant, int tile, int* ns, int* pps) {
+  const int PL = variant == WINO_M7 ? M7::P * M7::P : F43::P * F43::P;
+  const int64_t T = variant == WINO_M7 ? geom<M7>(d).T : geom<F43>(d).T;
+  wgrad_split(T, PL, d->C, d->K, tile, ns, pps);
+  if (fp32_engine() >= 1 && (tile == 0 || tile == 3)) split_wgrad_plan(T, d->C, d->K, PL, ns, pps);
 }
 
 }  // namespace mtlssl

@@ -392,7 +392,7 @@ class Bottleneck:
         """gp: dL/d(pre-activation of out). Returns dL/d(pre-activation of x) (masked by x>0 when
         mask_input), or None. `wgrad`: where the filter gradients run (inline, or a WgradStream).
         active: uint8 flag per image (RoI), 0 = gp is exactly zero there — then so is every gradient of the unit, and the
-        1x1 layers leave those rows out (stride-1 units only: a RoI keeps its rows)."""
+        1x1 layers and a 3x3 layer on a Winograd plan leave those RoIs out (stride-1 units only: a RoI keeps its rows)."""
         kw = {} if active is None else dict(active=active)
         x, a1, a2, sc_sub = ctx[:4]
         if self.bn_trainable:
@@ -408,8 +408,8 @@ class Bottleneck:
         gp2 = self.conv3.dgrad(a2.shape, gp, mask_ref=a2, **kw)
         if self.bn_trainable:
             self.conv2.bn_grad(a2, gp2)
-        wgrad.run(self.conv2, a1, gp2)
-        gp1 = self.conv2.dgrad(a1.shape, gp2, mask_ref=a1)
+        wgrad.run(self.conv2, a1, gp2, **kw)
+        gp1 = self.conv2.dgrad(a1.shape, gp2, mask_ref=a1, **kw)
         if self.bn_trainable:
             self.conv1.bn_grad(a1, gp1)
         wgrad.run(self.conv1, x, gp1, **kw)

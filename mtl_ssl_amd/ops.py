@@ -653,7 +653,8 @@ def _active_arg(d, active, rows=None):
 
 
 def conv2d_dgrad(d, dy, w, residual=None, mask_ref=None, epilogue=0, out=None, xf_cache=None, active=None):
-    """active: uint8 [d.N] or None — 0 promises that image (RoI) n's dy rows are all exactly zero (mtlssl_conv2d_dgrad_rs)."""
+    """active: uint8 [d.N] or None — 0 promises that image (RoI) n's dy rows are all exactly zero (mtlssl_conv2d_dgrad_rs:
+    pointwise problems and 3x3 problems on a Winograd plan leave those RoIs out, bit-identical results)."""
     dx = out if out is not None else torch.empty((d.N, d.H, d.W, d.C), dtype=f32, device=dy.device)
     if PROFILER is None:
         def run():                                    # scratch output; no accumulate into it
