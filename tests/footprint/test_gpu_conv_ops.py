@@ -13,8 +13,8 @@ import pytest
 import torch
 
 from tests import parity_report
-from tests.conv_ref import (DIRECT_BOUND, WINO_BOUND, _channels, _dgrad_reference, _fwd_reference, _rows,
-                            _wgrad_reference)
+from tests.conv_ref import (DIRECT_BOUND, WINO_BOUND, _channels, _rows, dgrad_expected, fwd_expected, prob_of as _prob,
+                            tanh_tolerance, wgrad_expected)
 from tests.footprint.guarded import GuardedOutputs, GuardedWorkspaces, GuardSet, check_guards
 from tests.parity_report import dot_err
 from tests.test_gpu_conv_ops import NULL_WS_CASES
@@ -37,10 +37,6 @@ def ops():
 def _lib():
     from mtl_ssl_amd.lib import lib
     return lib()
-
-
-def _prob(d):
-    return (d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.OH, d.OW, d.stride, d.dilation, d.pad_t, d.pad_l)
 
 
 def _err(got, ref, mag):
@@ -69,7 +65,6 @@ class Run:
                       resd=rand(N, H, W, C) - 0.5, mref=rand(N, H, W, C) - 0.5, scale=rand(K) + 0.5,
                       dw_old=rand(R, S, C, K) - 0.5, db_old=rand(K) - 0.5, dx_old=rand(N, H, W, C) - 0.5)
         self.rng = np.random.default_rng(seed)
-        self.w64 = self.o["w"].double().cpu()
         self.gs = GuardSet()
         self.g = {k: self.gs.input(v, k) for k, v in self.o.items() if k not in ("dw_old", "db_old", "dx_old")}
         self.ws = {}                     # (what) -> workspace bytes handed out
@@ -95,26 +90,16 @@ class Run:
             ops.conv2d_fwd(d, g["x"], g["w"], g["bias"] if "BIAS" in epi_names else None,
                            g["res"] if "RESIDUAL" in epi_names else None, epi, out=y, **kw)
         self._done(gw, "fwd", [("y", y)])
-        rows = _rows(d0.N, d0.OH, d0.OW, self.rng)
-        rows_t = torch.from_numpy(rows).cuda()
-        ref, mag = _fwd_reference(_prob(d0), o["x"], self.w64, rows)
-        if "BIAS" in epi_names:
-            a = o["bias"].double().cpu()[None, :]
-            ref, mag = ref + a, mag + a.abs()
-        if "RESIDUAL" in epi_names:
-            a = o["res"].reshape(-1, d0.K)[rows_t].double().cpu()
-            ref, mag = ref + a, mag + a.abs()
-        got = y.reshape(-1, d0.K)[rows_t] if y.is_contiguous() else y.contiguous().reshape(-1, d0.K)[rows_t]
+        sel, ref, mag = fwd_expected(_prob(d0), o["x"], o["w"], _rows(d0.N, d0.OH, d0.OW, self.rng),
+                                     bias=o["bias"] if "BIAS" in epi_names else None,
+                                     res=o["res"] if "RESIDUAL" in epi_names else None, relu="RELU" in epi_names)
+        got = sel(y)
         if "TANH" in epi_names:
-            from tests.test_gpu_offtable_plans import TANH_ULPS
             t64 = torch.tanh(ref)
-            unit = torch.from_numpy(np.spacing(np.maximum(t64.abs().numpy(), np.finfo(np.float32).tiny).astype(np.float32)).astype(np.float64))
             err = (got.double().cpu() - t64).abs()
-            worst = float((err / (bound * 2.0 ** -24 * mag + TANH_ULPS * unit)).max())
+            worst = float((err / torch.from_numpy(tanh_tolerance(mag, t64, bound))).max())
             assert worst <= 1.0, (self.tag, "fwd tanh", worst)
             return y
-        if "RELU" in epi_names:
-            ref = torch.relu(ref)
         e = dot_err(got, ref, mag)
         print("%s fwd: error %.2f of %.0f (2^-24 * sum|ab| units), workspace %d B" % (self.tag, e, bound, self.ws["fwd"]))
         assert e <= bound, (self.tag, "fwd", e)
@@ -134,21 +119,12 @@ class Run:
             ops.conv2d_dgrad(d, dy if dy is not None else g["dy"], g["w"], g["resd"] if "RESIDUAL" in epi_names else None,
                              g["mref"] if "MASK" in epi_names else None, epi, out=dx, active=active, **kw)
         self._done(gw, "dgrad", [("dx", dx)])
-        rows = _rows(d0.N, d0.H, d0.W, self.rng)
-        rows_t = torch.from_numpy(rows).cuda()
-        ref, mag = _dgrad_reference(_prob(d0), o["dy"], self.w64, rows)
-        if "RESIDUAL" in epi_names:
-            a = o["resd"].reshape(-1, d0.C)[rows_t].double().cpu()
-            ref, mag = ref + a, mag + a.abs()
-        if accum:
-            a = o["dx_old"].reshape(-1, d0.C)[rows_t].double().cpu()
-            ref, mag = ref + a, mag + a.abs()
-        got = dx.reshape(-1, d0.C)[rows_t]
+        sel, ref, mag = dgrad_expected(_prob(d0), o["dy"], o["w"], _rows(d0.N, d0.H, d0.W, self.rng),
+                                       resd=o["resd"] if "RESIDUAL" in epi_names else None, prev=o["dx_old"] if accum else None,
+                                       mask=o["mref"] if "MASK" in epi_names else None)
+        got = sel(dx)
         if "MASK" in epi_names:
-            on = (o["mref"].reshape(-1, d0.C)[rows_t] > 0).cpu()
-            assert bool((got.cpu()[~on] == 0).all()), (self.tag, "masked gradient must be exactly 0")
-            ref = ref * on
-            mag = torch.where(on, mag, torch.ones_like(mag))
+            assert bool((got.cpu()[~(sel(o["mref"]) > 0).cpu()] == 0).all()), (self.tag, "masked gradient must be exactly 0")
         if float(mag.max()) == 0.0:                  # no active row at all: every output is exactly 0
             assert not bool(dx.any()), (self.tag, "dgrad of all-zero dy")
             return dx
@@ -176,14 +152,8 @@ class Run:
         self._done(gw, "wgrad", [("dw", dw), ("dbias", db)])
         assert gw.bytes_of("wgrad") == [_lib().conv2d_wgrad_workspace_bytes(ctypes.byref(d))]
         cs, ks = _channels(d0.C, self.rng), _channels(d0.K, self.rng)
-        cs_t, ks_t = torch.from_numpy(cs).cuda(), torch.from_numpy(ks).cuda()
-        dy_sub = o["dy"][..., ks_t].double().cpu()
-        ref, mag = _wgrad_reference(_prob(d0), o["x"][..., cs_t].double().cpu(), dy_sub)
-        s64 = o["scale"][ks_t].double().cpu()
-        dw0 = beta * o["dw_old"][:, :, cs_t][..., ks_t].double().cpu()
-        db0 = beta * o["db_old"][ks_t].double().cpu()
-        pairs = [(dw[:, :, cs_t][..., ks_t], dw0 + s64 * ref, dw0.abs() + s64 * mag),
-                 (db[ks_t], db0 + dy_sub.sum((0, 1, 2)), db0.abs() + dy_sub.abs().sum((0, 1, 2)))]
+        pairs = [(sel(t), ref, mag) for t, (sel, ref, mag) in zip((dw, db), wgrad_expected(
+            _prob(d0), o["x"], o["dy"], cs, ks, o["scale"], beta, o["dw_old"], o["db_old"]))]
         errs = [_err(*p) for p in pairs]
         print("%s wgrad beta %g: errors %s of %.0f / %.0f, workspace %d B" % (self.tag, beta, ["%.2f" % e for e in errs], bound,
                                                                                DIRECT_BOUND, self.ws["wgrad"]))

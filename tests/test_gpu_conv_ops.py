@@ -440,18 +440,10 @@ def test_null_workspace_routes_match_float64(ops, case):
     distance from a correctly rounded tanh as tests/test_gpu_offtable_plans.py bounds it."""
     import ctypes
     from mtl_ssl_amd.lib import lib, ptr
-    from tests.conv_ref import DIRECT_BOUND, _dgrad_reference, _fwd_reference, _rows
-    from tests.parity_report import dot_err
-    from tests.test_gpu_offtable_plans import TANH_ULPS
+    from tests.conv_ref import DIRECT_BOUND, ConvCase, prob_of, tanh_tolerance
     name, mode, xs, ws, stride, epi_name, wino, want, _ = case
     d = ops.conv_desc(xs, ws, stride, 1, "SAME")
-    N, H, W, C, K, R, S, OH, OW = d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.OH, d.OW
-    prob = (N, H, W, C, K, R, S, OH, OW, d.stride, d.dilation, d.pad_t, d.pad_l)
-    seed = zlib.crc32(repr(case[:5]).encode())
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
-    x, w, dy = rand(N, H, W, C) * 2 - 0.6, (rand(R, S, C, K) - 0.5) * (2.0 / np.sqrt(R * S * C)), rand(N, OH, OW, K) - 0.5
-    w64, rng, stream = w.double().cpu(), np.random.default_rng(seed), ops._stream()
+    c, stream = ConvCase(prob_of(d), seed=zlib.crc32(repr(case[:5]).encode())), ops._stream()
     ops.reset_tuning(False, False)
     prev_wino = ops.set_winograd(wino) if wino is not None else None
     try:
@@ -461,23 +453,13 @@ def test_null_workspace_routes_match_float64(ops, case):
         assert lib().conv2d_workspace_bytes(ctypes.byref(d), mode) > 0, name      # so ops.conv2d_* never gets here
         if mode == 0:
             epi = sum(getattr(ops, "EPI_" + e) for e in epi_name.split("|"))
-            bias, res = rand(K) - 0.5, (rand(N, OH, OW, K) - 0.5 if "RESIDUAL" in epi_name else None)
-            rows = _rows(N, OH, OW, rng)
-            rows_t = torch.from_numpy(rows).cuda()
-            ref, mag = _fwd_reference(prob, x, w64, rows)
-            for a in [bias.double().cpu()[None, :]] + ([res.reshape(-1, K)[rows_t].double().cpu()] if res is not None else []):
-                ref, mag = ref + a, mag + a.abs()
-            out = torch.full((N, OH, OW, K), float("nan"), device="cuda")
-            lib().conv2d_fwd(ctypes.byref(d), ptr(x), ptr(w), ptr(bias), ptr(res), ptr(out), epi, None, stream)
+            c.prepare(0, res="RESIDUAL" in epi_name, relu="RELU" in epi_name)      # |relu(a) - relu(b)| <= |a - b|
+            out = torch.full((d.N, d.OH, d.OW, d.K), float("nan"), device="cuda")
+            lib().conv2d_fwd(ctypes.byref(d), ptr(c.x), ptr(c.w), ptr(c.bias), ptr(c.res), ptr(out), epi, None, stream)
         else:
-            resd, old = rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5
-            rows = _rows(N, H, W, rng)
-            rows_t = torch.from_numpy(rows).cuda()
-            ref, mag = _dgrad_reference(prob, dy, w64, rows)
-            for a in (t.reshape(-1, C)[rows_t].double().cpu() for t in (resd, old)):
-                ref, mag = ref + a, mag + a.abs()
-            out = old.clone()
-            lib().conv2d_dgrad(ctypes.byref(d), ptr(dy), ptr(w), ptr(resd), None, ptr(out), ops.EPI_RESIDUAL | ops.EPI_ACCUM,
+            c.prepare(1)
+            out = c.prev.clone()
+            lib().conv2d_dgrad(ctypes.byref(d), ptr(c.dy), ptr(c.w), ptr(c.resd), None, ptr(out), ops.EPI_RESIDUAL | ops.EPI_ACCUM,
                                None, stream)
         torch.cuda.synchronize()
     finally:
@@ -485,18 +467,15 @@ def test_null_workspace_routes_match_float64(ops, case):
             ops.set_winograd(prev_wino)
         ops.reset_tuning()
     assert bool(torch.isfinite(out).all()), name
-    got = out.reshape(-1, out.shape[-1])[rows_t]
     if mode == 0 and "TANH" in epi_name:
+        sel, ref, mag = c.expected[0][0]
         t64 = torch.tanh(ref)
-        unit = torch.from_numpy(np.spacing(np.maximum(t64.abs().numpy(), np.finfo(np.float32).tiny).astype(np.float32)).astype(np.float64))
-        err = (got.double().cpu() - t64).abs()                      # tanh' <= 1: the linear bound carries over
-        worst = float((err / (DIRECT_BOUND * 2.0 ** -24 * mag + TANH_ULPS * unit)).max())
+        err = (sel(out).double().cpu() - t64).abs()                 # tanh' <= 1: the linear bound carries over
+        worst = float((err / torch.from_numpy(tanh_tolerance(mag, t64, DIRECT_BOUND))).max())
         print("%s: worst error %.3f of the bound" % (name, worst))
         assert worst <= 1.0, (name, worst)
         return
-    if mode == 0 and "RELU" in epi_name:
-        ref = torch.relu(ref)                                       # |relu(a) - relu(b)| <= |a - b|
-    e = dot_err(got, ref, mag)
+    e = c.errors(mode, out)[0]
     print("%s: error %.2f of %.0f (2^-24 * sum|ab| units)" % (name, e, DIRECT_BOUND))
     assert e <= DIRECT_BOUND, (name, e)
 

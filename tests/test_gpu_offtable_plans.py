@@ -17,30 +17,23 @@ The forward TANH and RELU6 epilogues run once through each of their three sites 
 behind a K split with NG % 4 == 0, k_splitk_epilogue_scalar with NG % 4 != 0) on the smallest representatives that reach
 them: RELU6 must be clamp(linear, 0, 6) bit for bit; the device tanhf is held to TANH_ULPS (twice the worst distance
 measured on an MI355X, see there) from a float64 tanh of the kernel's own fp32 linear output."""
+import functools
 import importlib.util
 import json
 import os
-import zlib
 
 import numpy as np
 import pytest
 import torch
 
 from tests import parity_report
-from tests.conv_ref import (DIRECT_BOUND, ROWS, WINO_BOUND, _channels, _dgrad_reference, _fwd_reference, _rows,
-                            _wgrad_reference)
+from tests.conv_ref import (DIRECT_BOUND, MODE_NAMES, ROWS, TANH_ULPS, TANH_ULPS_MEASURED, WINO_BOUND, ConvCase,  # noqa: F401
+                            _rows, family_lines, fp32_ulps, fwd_expected, pid as _pid, plan_test_ops, tanh_tolerance)
 from tests.parity_report import dot_err
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODE_NAMES = ("fwd", "dgrad", "wgrad")
-# Worst distance of the device tanhf from the correctly rounded tanh of its own fp32 argument, in ulps of the output,
-# as test_tanh_and_relu6_epilogues_at_every_site measured it on an MI355X (in the tile kernel 1.396, k_splitk_epilogue
-# 1.315, k_splitk_epilogue_scalar 1.312; arguments spread over +-9.5, a quarter of the channels near 0). The assertion
-# allows twice that; the margin covers arguments the cases do not sample.
-TANH_ULPS_MEASURED = 1.396
-TANH_ULPS = 2.0 * TANH_ULPS_MEASURED
 
 
 def _tool():
@@ -56,24 +49,9 @@ CASES = [(tuple(e["descriptor"]), e["mode"], e["signature"]) for e in FIXTURE["p
 _RUN = {}                       # (problem, mode) -> (family, worst error)
 
 
-def _pid(prob, mode):
-    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
-    return "%s-%dx%dx%dx%d-k%d-%dx%d-o%dx%d-s%dd%dp%d%d" % (MODE_NAMES[mode], N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl)
-
-
 @pytest.fixture(scope="module")
 def ops():
-    import __graft_entry__ as g
-    g.build()
-    from mtl_ssl_amd import ops
-    assert torch.cuda.is_available()
-    assert ops.POISON_WS, "the suite runs with NaN-poisoned workspaces (tests/conftest.py)"
-    assert not [k for k in TOOL.PLANNING_SWITCHES if k in os.environ], "a planning switch is set"
-    prev = ops.set_fp32_engine(0)
-    ops.reset_tuning(use_plan_db=True, autotune=False)
-    yield ops
-    ops.set_fp32_engine(prev)
-    ops.reset_tuning()
+    yield from plan_test_ops(TOOL.PLANNING_SWITCHES)
     _report()
 
 
@@ -128,17 +106,6 @@ def _sample_rows(ops, prob, mode, n_img, hs, ws, rng):
     return np.array(sorted(set(base.tolist()) | extra), np.int64)
 
 
-def _inputs(prob):
-    N, H, W, C, K, R, S, OH, OW = prob[:9]
-    seed = zlib.crc32(repr(prob).encode())
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
-    x = rand(N, H, W, C) * 2 - 0.6                                      # post-ReLU-like: mostly positive
-    w = (rand(R, S, C, K) - 0.5) * (2.0 / np.sqrt(R * S * C))
-    dy = rand(N, OH, OW, K) - 0.5                                       # zero-mean
-    return np.random.default_rng(seed), rand, x, w, dy
-
-
 def test_fixture_is_parametrized_whole():
     assert len(CASES) == FIXTURE["counts"]["representatives"] > 0
     assert len({(p, m) for p, m, _ in CASES}) == len(CASES)
@@ -147,66 +114,21 @@ def test_fixture_is_parametrized_whole():
 
 @pytest.mark.parametrize("prob,mode,want", CASES, ids=[_pid(p, m) for p, m, _ in CASES])
 def test_offtable_plan_matches_float64(ops, prob, mode, want):
-    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
     d = TOOL.desc_of(prob)
-    rng, rand, x, w, dy = _inputs(prob)
-    w64 = w.double().cpu()
+    case = ConvCase(prob)
     sig = _signature(ops, prob, mode)
     assert sig == want, ("the planner no longer gives this case the plan it stands for", sig, want)
-    wino = sig[1].startswith("winograd")
-
-    if mode == 0:
-        bias, res = rand(K) - 0.5, rand(N, OH, OW, K) - 0.5
-        epi = ops.EPI_BIAS | ops.EPI_RESIDUAL
-        rows = _sample_rows(ops, prob, mode, N, OH, OW, rng)
-        rows_t = torch.from_numpy(rows).cuda()
-        ref, mag = _fwd_reference(prob, x, w64, rows)
-        addend = [bias.double().cpu()[None, :], res.reshape(-1, K)[rows_t].double().cpu()]
-        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
-        y = ops.conv2d_fwd(d, x, w, bias, res, epi)
-        got, outs = [(y.reshape(-1, K)[rows_t], ref, mag)], (y,)
-    elif mode == 1:
-        resd, prev, mask = rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5
-        epi = ops.EPI_RESIDUAL | ops.EPI_ACCUM
-        rows = _sample_rows(ops, prob, mode, N, H, W, rng)
-        rows_t = torch.from_numpy(rows).cuda()
-        ref, mag = _dgrad_reference(prob, dy, w64, rows)
-        addend = [t.reshape(-1, C)[rows_t].double().cpu() for t in (resd, prev)]
-        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
-        dx = prev.clone()
-        ops.conv2d_dgrad(d, dy, w, resd, None, epi, out=dx)
-        got, outs = [(dx.reshape(-1, C)[rows_t], ref, mag)], (dx,)
-    else:
-        scale, dw_old, db_old = rand(K) + 0.5, rand(R, S, C, K) - 0.5, rand(K) - 0.5
-        cs, ks = _channels(C, rng), _channels(K, rng)
-        cs_t, ks_t = torch.from_numpy(cs).cuda(), torch.from_numpy(ks).cuda()
-        dy_sub = dy[..., ks_t].double().cpu()
-        ref, mag = _wgrad_reference(prob, x[..., cs_t].double().cpu(), dy_sub)
-        s64, dw0 = scale[ks_t].double().cpu(), dw_old[:, :, cs_t][..., ks_t].double().cpu()
-        db0 = db_old[ks_t].double().cpu()
-        dw, db = dw_old.clone(), db_old.clone()
-        ops.conv2d_wgrad(d, x, dy, dw, out_scale=scale, dbias=db, beta=1.0)
-        got = [(dw[:, :, cs_t][..., ks_t], dw0 + s64 * ref, dw0.abs() + s64.abs() * mag),
-               (db[ks_t], db0 + dy_sub.sum((0, 1, 2)), db0.abs() + dy_sub.abs().sum((0, 1, 2)))]
-        outs = (dw, db)
-
+    case.prepare(mode, rows=functools.partial(_sample_rows, ops, prob, mode))
+    outs = case.call(ops, d, mode)
     assert _signature(ops, prob, mode) == want, "the plan changed with the first call"
-    for t in outs:
-        assert bool(torch.isfinite(t).all()), ("non-finite output (a poisoned workspace leaked?)", MODE_NAMES[mode], sig)
-    errs = [dot_err(*g) for g in got]
-    lims = [WINO_BOUND if wino else DIRECT_BOUND] + [DIRECT_BOUND] * (len(errs) - 1)   # the bias gradient is a plain column sum
-    print("%s %s: errors %s of %s (2^-24 * sum|ab| units)" % (_pid(prob, mode), sig[1], ["%.2f" % e for e in errs], lims))
-    _RUN[(prob, mode)] = (sig[1], errs[0])
-    assert all(e <= lim for e, lim in zip(errs, lims)), (MODE_NAMES[mode], sig, errs, lims)
+    case.check_finite(outs, MODE_NAMES[mode], sig)
 
-    # the nonlinear epilogues are exact functions of the linear result (the split-K fold sums in a fixed order)
-    if mode == 0:
-        yr = ops.conv2d_fwd(d, x, w, bias, res, epi | ops.EPI_RELU)
-        assert torch.equal(yr, torch.relu(y)), ("forward ReLU epilogue", sig)
-    if mode == 1:
-        dm = prev.clone()
-        ops.conv2d_dgrad(d, dy, w, resd, mask, epi | ops.EPI_MASK, out=dm)
-        assert torch.equal(dm, torch.where(mask > 0, dx, torch.zeros_like(dx))), ("dgrad mask epilogue", sig)
+    def note(errs, lims):
+        print("%s %s: errors %s of %s (2^-24 * sum|ab| units)" % (_pid(prob, mode), sig[1], ["%.2f" % e for e in errs], lims))
+        _RUN[(prob, mode)] = (sig[1], errs[0])
+    case.check_errors(mode, outs, WINO_BOUND if sig[1].startswith("winograd") else DIRECT_BOUND, sig, note)
+    if mode < 2:
+        case.check_exact_epilogue(mode, case.call(ops, d, mode, nonlinear=True), outs, sig)
 
 
 def _site(sig):
@@ -217,12 +139,6 @@ def _site(sig):
     if nsplit == 1:
         return "in-kernel"
     return "k_splitk_epilogue_scalar" if ng4 else "k_splitk_epilogue"
-
-
-def _ulps(got, ref64):
-    """|got - ref| in units of the fp32 spacing at |ref| (float64 arrays)."""
-    unit = np.spacing(np.maximum(np.abs(ref64), np.finfo(np.float32).tiny).astype(np.float32)).astype(np.float64)
-    return np.abs(got - ref64) / unit
 
 
 def test_tanh_and_relu6_epilogues_at_every_site(ops):
@@ -236,7 +152,8 @@ def test_tanh_and_relu6_epilogues_at_every_site(ops):
     for site, (prob, want) in sorted(sites.items()):
         N, H, W, C, K, R, S, OH, OW = prob[:9]
         d = TOOL.desc_of(prob)
-        rng, rand, x, w, dy = _inputs(prob)
+        case = ConvCase(prob)
+        x, w = case.x, case.w
         assert _signature(ops, prob, 0) == want, (site, want)
         bias = torch.linspace(-8.0, 8.0, K, device="cuda")              # arguments from the linear range to saturation (+-9)
         bias[1:: 4] *= 1.0 / 64.0                                       # ... and a quarter of the channels near 0
@@ -250,21 +167,15 @@ def test_tanh_and_relu6_epilogues_at_every_site(ops):
         yt = ops.conv2d_fwd(d, x, w, bias, None, ops.EPI_BIAS | ops.EPI_TANH)
         assert bool(torch.isfinite(yt).all())
         lin64 = lin.double().cpu().numpy()
-        u = _ulps(yt.double().cpu().numpy(), np.tanh(lin64))
+        u = fp32_ulps(yt.double().cpu().numpy(), np.tanh(lin64))
         worst[site] = float(u.max())
         print("tanhf at %s (%s): worst %.3f ulp over %d outputs, arguments %.2f .. %.2f" % (
             site, _pid(prob, 0), worst[site], u.size, lin64.min(), lin64.max()))
         # against float64 end to end: the linear bound plus that term (tanh' <= 1)
-        rows = _rows(N, OH, OW, rng)
-        rows_t = torch.from_numpy(rows).cuda()
-        ref, mag = _fwd_reference(prob, x, w.double().cpu(), rows)
-        b64 = bias.double().cpu()[None, :]
-        ref, mag = (ref + b64).numpy(), (mag + b64.abs()).numpy()
-        assert dot_err(lin.reshape(-1, K)[rows_t], torch.from_numpy(ref), torch.from_numpy(mag)) <= DIRECT_BOUND
-        lin_rows = lin.reshape(-1, K)[rows_t].double().cpu().numpy()
-        unit = np.spacing(np.maximum(np.abs(np.tanh(lin_rows)), np.finfo(np.float32).tiny).astype(np.float32)).astype(np.float64)
-        err = np.abs(yt.reshape(-1, K)[rows_t].double().cpu().numpy() - np.tanh(ref))
-        assert bool((err <= DIRECT_BOUND * 2.0 ** -24 * mag + TANH_ULPS * unit).all()), site
+        sel, ref, mag = fwd_expected(prob, x, w, _rows(N, OH, OW, case.rng), bias=bias)
+        assert dot_err(sel(lin), ref, mag) <= DIRECT_BOUND
+        err = np.abs(sel(yt).double().cpu().numpy() - np.tanh(ref.numpy()))
+        assert bool((err <= tanh_tolerance(mag, np.tanh(sel(lin).double().cpu().numpy()), DIRECT_BOUND)).all()), site
     parity_report.add("off-table plans, forward TANH epilogue: device tanhf worst %s ulp from float64 tanh of the fp32 "
                       "linear output (asserted: %.2f); RELU6 = clamp(linear, 0, 6) bit for bit at all three sites" % (
                           ", ".join("%s %.3f" % kv for kv in sorted(worst.items())), TANH_ULPS))
@@ -274,14 +185,8 @@ def test_tanh_and_relu6_epilogues_at_every_site(ops):
 def _report():
     if not _RUN:
         return
-    fams = {}
-    for (prob, mode), (fam, err) in _RUN.items():
-        f = fams.setdefault(fam, [[0, 0.0], [0, 0.0], [0, 0.0]])
-        f[mode][0] += 1
-        f[mode][1] = max(f[mode][1], err)
     parity_report.add("off-table plans (%d representatives of %d signatures reached, %d covered by the plan table); per "
                       "family (fwd / dgrad / wgrad):" % (len(_RUN), FIXTURE["counts"]["signatures_reached"],
                                                          FIXTURE["counts"]["signatures_covered_by_table"]))
-    for name, f in sorted(fams.items()):
-        parity_report.add("    %-16s %d / %d / %d cases; worst error in 2^-24*sum|ab| units %s" % (
-            name, f[0][0], f[1][0], f[2][0], " / ".join("%.2f" % v[1] for v in f)))
+    for line in family_lines((fam, mode, err) for (prob, mode), (fam, err) in _RUN.items()):
+        parity_report.add(line)

@@ -21,14 +21,11 @@ import pytest
 import torch
 
 from tests import parity_report
-from tests.conv_ref import (CH, DIRECT_BOUND, ROWS, WINO_BOUND, _channels, _dgrad_reference, _fwd_reference,  # noqa: F401
-                            _rows, _wgrad_reference)
-from tests.parity_report import dot_err
+from tests.conv_ref import DIRECT_BOUND, MODE_NAMES, WINO_BOUND, ConvCase, pid as _pid, plan_test_ops
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODE_NAMES = ("fwd", "dgrad", "wgrad")
 
 
 def _load():
@@ -44,23 +41,9 @@ PROBLEMS = _load()              # [(N, H, W, C, K, R, S, OH, OW, stride, dilatio
 _RUN = {}                       # (problem, mode) -> {"cfg", "family", "err", "split"}
 
 
-def _pid(prob):
-    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
-    return "%dx%dx%dx%d-k%d-%dx%d-o%dx%d-s%dd%dp%d%d" % (N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl)
-
-
 @pytest.fixture(scope="module")
 def ops():
-    import __graft_entry__ as g
-    g.build()
-    from mtl_ssl_amd import ops
-    assert torch.cuda.is_available()
-    assert ops.POISON_WS, "the suite runs with NaN-poisoned workspaces (tests/conftest.py)"
-    prev = ops.set_fp32_engine(0)
-    ops.reset_tuning(use_plan_db=True, autotune=False)
-    yield ops
-    ops.set_fp32_engine(prev)
-    ops.reset_tuning()
+    yield from plan_test_ops()
     _report()
 
 
@@ -95,58 +78,12 @@ def test_parametrization_covers_the_whole_table():
 
 @pytest.mark.parametrize("prob,modes", PROBLEMS, ids=[_pid(p) for p, _ in PROBLEMS])
 def test_production_plan_matches_float64(ops, prob, modes):
-    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
     d = _desc(prob)
-    seed = zlib.crc32(repr(prob).encode())
-    rng = np.random.default_rng(seed)
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
-    x = rand(N, H, W, C) * 2 - 0.6                                      # post-ReLU-like: mostly positive
-    w = (rand(R, S, C, K) - 0.5) * (2.0 / np.sqrt(R * S * C))
-    dy = rand(N, OH, OW, K) - 0.5                                       # zero-mean
-    w64 = w.double().cpu()
-    epi_f = ops.EPI_BIAS | ops.EPI_RESIDUAL
-    epi_d = ops.EPI_RESIDUAL | ops.EPI_ACCUM
+    case = ConvCase(prob)
+    for mode in sorted(modes):
+        case.prepare(mode)
+    call = lambda mode, **kw: case.call(ops, d, mode, **kw)
     out = {}                    # mode -> native outputs, reused by the split-engine pass
-    refs = {}                   # mode -> [(got -> tensor to compare, ref, mag)]
-
-    def call(mode, **kw):
-        if mode == 0:
-            return ops.conv2d_fwd(d, x, w, bias, res, epi_f, **kw)
-        if mode == 1:
-            dx = prev.clone()
-            ops.conv2d_dgrad(d, dy, w, resd, None, epi_d, out=dx, **kw)
-            return dx
-        dw, db = dw_old.clone(), db_old.clone()
-        ops.conv2d_wgrad(d, x, dy, dw, out_scale=scale, dbias=db, beta=1.0, **kw)
-        return dw, db
-
-    if 0 in modes:
-        bias, res = rand(K) - 0.5, rand(N, OH, OW, K) - 0.5
-        rows = _rows(N, OH, OW, rng)
-        rows_t = torch.from_numpy(rows).cuda()
-        ref, mag = _fwd_reference(prob, x, w64, rows)
-        addend = [bias.double().cpu()[None, :], res.reshape(-1, K)[rows_t].double().cpu()]
-        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
-        refs[0] = [(lambda y, r=rows_t: y.reshape(-1, K)[r], ref, mag)]
-    if 1 in modes:
-        resd, prev, mask = rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5
-        rows = _rows(N, H, W, rng)
-        rows_t = torch.from_numpy(rows).cuda()
-        ref, mag = _dgrad_reference(prob, dy, w64, rows)
-        addend = [t.reshape(-1, C)[rows_t].double().cpu() for t in (resd, prev)]
-        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
-        refs[1] = [(lambda dx, r=rows_t: dx.reshape(-1, C)[r], ref, mag)]
-    if 2 in modes:
-        scale, dw_old, db_old = rand(K) + 0.5, rand(R, S, C, K) - 0.5, rand(K) - 0.5
-        cs, ks = _channels(C, rng), _channels(K, rng)
-        cs_t, ks_t = torch.from_numpy(cs).cuda(), torch.from_numpy(ks).cuda()
-        dy_sub = dy[..., ks_t].double().cpu()
-        ref, mag = _wgrad_reference(prob, x[..., cs_t].double().cpu(), dy_sub)
-        s64, dw0 = scale[ks_t].double().cpu(), dw_old[:, :, cs_t][..., ks_t].double().cpu()
-        db0 = db_old[ks_t].double().cpu()
-        refs[2] = [(lambda o: o[0][:, :, cs_t][..., ks_t], dw0 + s64 * ref, dw0.abs() + s64.abs() * mag),
-                   (lambda o: o[1][ks_t], db0 + dy_sub.sum((0, 1, 2)), db0.abs() + dy_sub.abs().sum((0, 1, 2)))]
 
     for mode, pinned in sorted(modes.items()):
         o = out[mode] = call(mode)
@@ -154,21 +91,15 @@ def test_production_plan_matches_float64(ops, prob, modes):
         # (a) the table takes effect: the first call of the mode applied the pinned code
         if pinned >= 0:
             assert cfg == pinned, ("plan table entry not applied", mode, pinned, cfg)
-        for t in (o if mode == 2 else (o,)):
-            assert bool(torch.isfinite(t).all()), ("non-finite output (a poisoned workspace leaked?)", mode, cfg)
-        errs = [dot_err(sel(o), ref, mag) for sel, ref, mag in refs[mode]]
-        lims = [_bound(ops, cfg)] + [DIRECT_BOUND] * (len(errs) - 1)      # the bias gradient is a plain column sum
-        _RUN[(prob, mode)] = dict(cfg=cfg, family=_family(ops, d, mode), err=errs[0], split=None)
-        assert all(e <= lim for e, lim in zip(errs, lims)), (MODE_NAMES[mode], cfg, errs, lims)
+        case.check_finite(o, mode, cfg)
 
-    # the nonlinear epilogues are exact functions of the linear result (the split-K fold sums in a fixed order)
-    if 0 in modes:
-        y = ops.conv2d_fwd(d, x, w, bias, res, epi_f | ops.EPI_RELU)
-        assert torch.equal(y, torch.relu(out[0])), ("forward ReLU epilogue", _cfg(d, 0))
-    if 1 in modes:
-        dx = prev.clone()
-        ops.conv2d_dgrad(d, dy, w, resd, mask, epi_d | ops.EPI_MASK, out=dx)
-        assert torch.equal(dx, torch.where(mask > 0, out[1], torch.zeros_like(dx))), ("dgrad mask epilogue", _cfg(d, 1))
+        def note(errs, lims):
+            _RUN[(prob, mode)] = dict(cfg=cfg, family=_family(ops, d, mode), err=errs[0], split=None)
+        case.check_errors(mode, o, _bound(ops, cfg), cfg, note)
+
+    for mode in (0, 1):
+        if mode in modes:
+            case.check_exact_epilogue(mode, call(mode, nonlinear=True), out[mode], _cfg(d, mode))
 
     # (c) production Winograd path: the filter cache and the kept input transform change no bit
     for mode in (0, 1):
@@ -180,7 +111,7 @@ def test_production_plan_matches_float64(ops, prob, modes):
     if 0 in modes and 2 in modes and ops._shared_input_variant(d) >= 0:
         keep = {}
         assert torch.equal(call(0, keep_input_xf=keep), out[0])
-        dw, db = call(2, input_xf=keep[x.data_ptr()])
+        dw, db = call(2, input_xf=keep[case.x.data_ptr()])
         assert torch.equal(dw, out[2][0]) and torch.equal(db, out[2][1]), "kept input transform"
 
     # (d) the split-bf16 engine on the same calls: native bits where it declines, the native accuracy where it engages
@@ -192,8 +123,7 @@ def test_production_plan_matches_float64(ops, prob, modes):
             if same:
                 continue
             assert not _split_declines(ops, prob, mode, _cfg(d, mode)), ("split engine ran on a small problem", mode)
-            sel, ref, mag = refs[mode][0]
-            e = dot_err(sel(o), ref, mag)
+            e = case.errors(mode, o)[0]
             rec = _RUN[(prob, mode)]
             rec["split"] = e
             assert e <= 1.25 * max(rec["err"], 1.0) + 2.5, (MODE_NAMES[mode], rec, e)

@@ -21,26 +21,25 @@ output must be finite under the NaN-poisoned workspaces (conftest: MTLSSL_POISON
 test_one_step_launches_the_production_list builds the full configuration, runs one Trainer.forward_backward at 600x1024 and
 requires that the (mode, problem) set the step launched is the fixture's production list for freeze_layer 'conv2': the host
 enumeration cannot miss a launch without this suite noticing."""
+import functools
 import importlib.util
 import json
 import os
 import time
-import zlib
 
 import numpy as np
 import pytest
 import torch
 
 from tests import parity_report
-from tests.conv_ref import (DIRECT_BOUND, ROWS, WINO_BOUND, _channels, _dgrad_reference, _fwd_reference, _rows,
-                            _wgrad_reference)
+from tests.conv_ref import (DIRECT_BOUND, MODE_NAMES, ROWS, WINO_BOUND, ConvCase, _channels, _rows, family_lines, fwd_expected,
+                            dgrad_expected, pid, plan_test_ops)
 from tests.parity_report import dot_err
 from tests.test_gpu_offtable_plans import _extra_rows
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-MODE_NAMES = ("fwd", "dgrad", "wgrad")
 COLS = 64                       # sampled output columns of the wide FC layers
 # The FC reductions of this configuration are the longest in the project: 25 088 terms, 392 K-steps folded from up to 8
 # splits (the plan table's longest is a few thousand terms). Measured on an MI355X, in 2^-24 * sum|ab| units, worst over
@@ -71,24 +70,14 @@ _T0 = [None]
 
 
 def _pid(name, prob, mode):
-    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
-    return "%s-%s-%dx%dx%dx%d-k%d-%dx%d" % (name[:4], MODE_NAMES[mode], N, H, W, C, K, R, S)
+    return pid(prob, mode, name)
 
 
 @pytest.fixture(scope="module")
 def ops():
-    import __graft_entry__ as g
-    g.build()
-    from mtl_ssl_amd import ops
-    assert torch.cuda.is_available()
-    assert ops.POISON_WS, "the suite runs with NaN-poisoned workspaces (tests/conftest.py)"
-    assert not [k for k in TOOL.PLANNING_SWITCHES if k in os.environ], "a planning switch is set"
-    prev = ops.set_fp32_engine(0)
-    ops.reset_tuning(use_plan_db=True, autotune=False)
-    _T0[0] = time.time()
-    yield ops
-    ops.set_fp32_engine(prev)
-    ops.reset_tuning()
+    for o in plan_test_ops(TOOL.PLANNING_SWITCHES):
+        _T0[0] = time.time()
+        yield o
     torch.cuda.empty_cache()
     _report()
 
@@ -134,17 +123,6 @@ def _frame_edge_rows(OH, OW):
     return np.array(sorted(pick), np.int64)
 
 
-def _inputs(prob):
-    N, H, W, C, K, R, S, OH, OW = prob[:9]
-    seed = zlib.crc32(repr(prob).encode())
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    rand = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
-    x = rand(N, H, W, C) * 2 - 0.6                                      # post-ReLU-like: mostly positive
-    w = (rand(R, S, C, K) - 0.5) * (2.0 / np.sqrt(R * S * C))
-    dy = rand(N, OH, OW, K) - 0.5                                       # zero-mean
-    return np.random.default_rng(seed), rand, x, w, dy
-
-
 def test_fixture_is_parametrized_whole():
     c = FIXTURE["counts"]
     assert len(CASES) == c["production"] + c["representatives"] and c["production"] > 0 and c["representatives"] > 0
@@ -158,101 +136,49 @@ def test_fixture_is_parametrized_whole():
 def test_vgg16_plan_matches_float64(ops, name, prob, mode, want):
     N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
     d = TOOL.desc_of(prob)
-    rng, rand, x, w, dy = _inputs(prob)
+    case = ConvCase(prob)
+    x, w, dy = case.x, case.w, case.dy
     sig = _signature(ops, prob, mode)
     assert sig == want, ("the planner no longer gives this case the plan it stands for", sig, want)
-    wino = sig[1].startswith("winograd")
+    case.prepare(mode, rows=functools.partial(_sample_rows, ops, prob, mode), cols=functools.partial(_columns, prob))
+    call = functools.partial(case.call, ops, d, mode)
+    outs = call()
     cpu32 = None
-
-    if mode == 0:
-        bias, res = rand(K) - 0.5, rand(N, OH, OW, K) - 0.5
-        epi = ops.EPI_BIAS | ops.EPI_RESIDUAL
-        rows = _sample_rows(ops, prob, mode, N, OH, OW, rng)
-        cols = _columns(prob, K, rng)
+    if _wide_fc(prob) and mode < 2:                                     # the same outputs by a torch CPU float32 matmul
+        rows, cols = case.sample[mode]
         rows_t, cols_t = torch.from_numpy(rows).cuda(), torch.from_numpy(cols).cuda()
-        sel = lambda t: t.reshape(-1, K)[rows_t][:, cols_t]
-        w_sub = w[..., cols_t]
-        addend = [bias[cols_t].double().cpu()[None, :], sel(res).double().cpu()]
-        sub = prob[:4] + (len(cols),) + prob[5:]                        # the same geometry on the sampled columns
-        reference = lambda r: _fwd_reference(sub, x, w_sub.double().cpu(), r)
-        ref, mag = reference(rows)
-        if _wide_fc(prob):                                              # the same outputs by a torch CPU float32 matmul
-            cpu32 = dot_err(x.reshape(N, C)[rows_t].cpu() @ w_sub.reshape(C, -1).cpu(), ref, mag)
-        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
-        call = lambda e=epi: ops.conv2d_fwd(d, x, w, bias, res, e)
-        y = call()
-        got, outs = [(sel(y), ref, mag)], (y,)
-        if C == 3:                                                      # conv1_1: the frame's border, element by element
-            edge = _frame_edge_rows(OH, OW)
-            edge_t = torch.from_numpy(edge).cuda()
-            eref, emag = reference(edge)
-            ea = [bias.double().cpu()[None, :], res.reshape(-1, K)[edge_t].double().cpu()]
-            e_edge = dot_err(y.reshape(-1, K)[edge_t], eref + ea[0] + ea[1], emag + ea[0].abs() + ea[1].abs())
-            print("%s: last row, last column and corners of the frame (%d pixels): %.2f" % (_pid(name, prob, mode), len(edge), e_edge))
-            assert e_edge <= DIRECT_BOUND, ("conv1_1 frame border", e_edge)
-    elif mode == 1:
-        resd, prev, mask = rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5, rand(N, H, W, C) - 0.5
-        epi = ops.EPI_RESIDUAL | ops.EPI_ACCUM
-        rows = _sample_rows(ops, prob, mode, N, H, W, rng)
-        cols = _columns(prob, C, rng)
-        rows_t, cols_t = torch.from_numpy(rows).cuda(), torch.from_numpy(cols).cuda()
-        sel = lambda t: t.reshape(-1, C)[rows_t][:, cols_t]
-        sub = prob[:3] + (len(cols),) + prob[4:]                        # the same geometry on the sampled columns
-        ref, mag = _dgrad_reference(sub, dy, w[:, :, cols_t, :].double().cpu(), rows)
-        if _wide_fc(prob):                                              # the same outputs by a torch CPU float32 matmul
-            cpu32 = dot_err(dy.reshape(N, K)[rows_t].cpu() @ w.reshape(C, K)[cols_t].t().cpu(), ref, mag)
-        addend = [sel(t).double().cpu() for t in (resd, prev)]
-        ref, mag = ref + addend[0] + addend[1], mag + addend[0].abs() + addend[1].abs()
-
-        def call(e=epi, m=None):
-            dx = prev.clone()
-            ops.conv2d_dgrad(d, dy, w, resd, m, e, out=dx)
-            return dx
-        dx = call()
-        got, outs = [(sel(dx), ref, mag)], (dx,)
-    else:
-        scale, dw_old, db_old = rand(K) + 0.5, rand(R, S, C, K) - 0.5, rand(K) - 0.5
-        cs, ks = _channels(C, rng), _channels(K, rng)
-        cs_t, ks_t = torch.from_numpy(cs).cuda(), torch.from_numpy(ks).cuda()
-        dy_sub = dy[..., ks_t].double().cpu()
-        ref, mag = _wgrad_reference(prob, x[..., cs_t].double().cpu(), dy_sub)
-        s64, dw0 = scale[ks_t].double().cpu(), dw_old[:, :, cs_t][..., ks_t].double().cpu()
-        db0 = db_old[ks_t].double().cpu()
-
-        def call():
-            dw, db = dw_old.clone(), db_old.clone()
-            ops.conv2d_wgrad(d, x, dy, dw, out_scale=scale, dbias=db, beta=1.0)
-            return dw, db
-        dw, db = call()
-        got = [(dw[:, :, cs_t][..., ks_t], dw0 + s64 * ref, dw0.abs() + s64.abs() * mag),
-               (db[ks_t], db0 + dy_sub.sum((0, 1, 2)), db0.abs() + dy_sub.abs().sum((0, 1, 2)))]
-        outs = (dw, db)
+        if mode == 0:
+            mm, (_, ref, mag) = x.reshape(N, C)[rows_t].cpu() @ w[..., cols_t].reshape(C, -1).cpu(), fwd_expected(prob, x, w, rows, cols)
+        else:
+            mm, (_, ref, mag) = dy.reshape(N, K)[rows_t].cpu() @ w.reshape(C, K)[cols_t].t().cpu(), dgrad_expected(prob, dy, w, rows, cols)
+        cpu32 = dot_err(mm, ref, mag)
+    if mode == 0 and C == 3:                                            # conv1_1: the frame's border, element by element
+        edge = _frame_edge_rows(OH, OW)
+        sel, ref, mag = fwd_expected(prob, x, w, edge, case.sample[0][1], case.bias, case.res)
+        e_edge = dot_err(sel(outs), ref, mag)
+        print("%s: last row, last column and corners of the frame (%d pixels): %.2f" % (_pid(name, prob, mode), len(edge), e_edge))
+        assert e_edge <= DIRECT_BOUND, ("conv1_1 frame border", e_edge)
 
     assert _signature(ops, prob, mode) == want, "the plan changed with the first call"
-    for t in outs:
-        assert bool(torch.isfinite(t).all()), ("non-finite output (a poisoned workspace leaked?)", MODE_NAMES[mode], sig)
-    errs = [dot_err(*g) for g in got]
-    first = WINO_BOUND if wino else (FC_BOUND if _wide_fc(prob) else DIRECT_BOUND)
-    lims = [first] + [DIRECT_BOUND] * (len(errs) - 1)                   # the bias gradient is a plain column sum
-    print("%s %s: errors %s of %s (2^-24 * sum|ab| units)%s" % (
-        _pid(name, prob, mode), sig[1], ["%.2f" % e for e in errs], lims,
-        "" if cpu32 is None else "; torch CPU float32 on the same outputs %.2f" % cpu32))
-    _RUN[(name, prob, mode)] = (sig[1], errs[0])
-    if cpu32 is not None:
-        _FC[(prob, mode)] = (errs[0], cpu32)
-    assert all(e <= lim for e, lim in zip(errs, lims)), (MODE_NAMES[mode], sig, errs, lims)
+    case.check_finite(outs, MODE_NAMES[mode], sig)
+
+    def note(errs, lims):
+        print("%s %s: errors %s of %s (2^-24 * sum|ab| units)%s" % (
+            _pid(name, prob, mode), sig[1], ["%.2f" % e for e in errs], lims,
+            "" if cpu32 is None else "; torch CPU float32 on the same outputs %.2f" % cpu32))
+        _RUN[(name, prob, mode)] = (sig[1], errs[0])
+        if cpu32 is not None:
+            _FC[(prob, mode)] = (errs[0], cpu32)
+    wino = sig[1].startswith("winograd")
+    case.check_errors(mode, outs, WINO_BOUND if wino else (FC_BOUND if _wide_fc(prob) else DIRECT_BOUND), sig, note)
 
     # a second call gives the same bits (the K-split fold and the Winograd transforms sum in a fixed order)
     again = call()
-    for a, b in zip(again if mode == 2 else (again,), outs):
+    for a, b in zip(again if mode == 2 else (again,), outs if mode == 2 else (outs,)):
         assert torch.equal(a, b), ("two calls differ", MODE_NAMES[mode], sig)
     del again
-    # the nonlinear epilogues are exact functions of the linear result
-    if mode == 0:
-        assert torch.equal(call(epi | ops.EPI_RELU), torch.relu(y)), ("forward ReLU epilogue", sig)
-    if mode == 1:
-        dm = call(epi | ops.EPI_MASK, mask)
-        assert torch.equal(dm, torch.where(mask > 0, dx, torch.zeros_like(dx))), ("dgrad mask epilogue", sig)
+    if mode < 2:
+        case.check_exact_epilogue(mode, call(nonlinear=True), outs, sig)
 
 
 def test_one_step_launches_the_production_list(ops):
@@ -304,14 +230,8 @@ def _report():
                       "plan table or the off-table fixture); per family (fwd / dgrad / wgrad):" % (
                           sum(1 for k in _RUN if k[0] == "production"), sum(1 for k in _RUN if k[0] == "representatives"),
                           c["signatures_reached"], c["signatures_covered_by_table_or_offtable"]))
-    fams = {}
-    for (name, prob, mode), (fam, err) in _RUN.items():
-        f = fams.setdefault(fam, [[0, 0.0], [0, 0.0], [0, 0.0]])
-        f[mode][0] += 1
-        f[mode][1] = max(f[mode][1], err)
-    for fam, f in sorted(fams.items()):
-        parity_report.add("    %-16s %d / %d / %d cases; worst error in 2^-24*sum|ab| units %s" % (
-            fam, f[0][0], f[1][0], f[2][0], " / ".join("%.2f" % v[1] for v in f)))
+    for line in family_lines((fam, mode, err) for (name, prob, mode), (fam, err) in _RUN.items()):
+        parity_report.add(line)
     for (prob, mode), (e, e32) in sorted(_FC.items()):
         parity_report.add("    FC %d rows, %d -> %d, %s (%d-term reduction): kernel %.2f, torch CPU float32 matmul on the same "
                           "outputs %.2f (asserted: %.0f)" % (prob[0], prob[3], prob[4], MODE_NAMES[mode],
