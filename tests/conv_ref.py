@@ -1,8 +1,18 @@
-"""Float64 references and output samplers shared by the plan tests (test_gpu_plan_table.py, test_gpu_offtable_plans.py):
-the reference never shortens a reduction, it samples outputs instead — flat output rows of the forward (all K channels
-each) and input rows of the dgrad (all C channels), tile boundaries and image corners included, and every (r, s) tap of a
-channel block of the filter gradient summed over all N*OH*OW pixels. Each returns (sum, sum |a*b|) for
-tests/parity_report.py dot_err.
+"""Float64 references shared by the plan tests (test_gpu_plan_table.py, test_gpu_offtable_plans.py,
+vgg/test_gpu_fullsize_plans.py). Two of them, and neither shortens a reduction:
+
+  * whole (fwd / dgrad / wgrad_reference_whole): EVERY output element, by a plain tap walk of the operands cast to float64
+    on the device the operands live on — x zero-padded once, per tap (r, s) one strided slice times w[r, s], in row chunks
+    of at most 2 GiB — compared on that device by dot_err_whole, which returns the worst error and where it is; locate()
+    turns the index into row, column, tile and split. This is the comparison that covers the output.
+  * sampled (_fwd / _dgrad / _wgrad_reference), built on the CPU: ~256 flat output rows of the forward (all K channels
+    each) and input rows of the dgrad (all C channels), tile boundaries and image corners included, and every (r, s) tap
+    of a 16 x 16 channel block of the filter gradient summed over all N*OH*OW pixels. It stays for two reasons: it is the
+    independent yardstick of the whole one (the device's float64 matmul is a library kernel on a new chip: ConvCase.
+    reference_difference holds the two to n * 2^-52 * scale on the sample), and its numbers are the parity report's
+    series since the plan tests exist.
+
+Each returns (sum, sum |a*b|), the unit of tests/parity_report.py dot_err.
 
 On top of them: fwd_expected / dgrad_expected / wgrad_expected add the epilogue's addends (to the sum AND to the scale) and
 return (select, ref, mag) per compared output; ConvCase draws the operands of one problem the way every float64 plan test
@@ -18,8 +28,14 @@ from tests.parity_report import dot_err
 
 ROWS = 256                      # sampled rows of a forward output / dgrad input
 CH = 16                         # sampled channels per side of the filter-gradient block
-DIRECT_BOUND, WINO_BOUND = 8.0, 400.0       # the constants of tests/test_gpu_split_engine.py
+# The constants of tests/test_gpu_split_engine.py, set on samples. They hold over every output element as they are
+# (profiles/whole_output_observed.txt, one MI355X): 2.71e9 elements of the plan table's 359 pairs, worst direct 7.07 (on the
+# sample 5.29), worst Winograd 47.06 (34.22), worst bias gradient 1.43; no element beyond either bound, so neither has a
+# whole-output limit of its own.
+DIRECT_BOUND, WINO_BOUND = 8.0, 400.0
 MODE_NAMES = ("fwd", "dgrad", "wgrad")
+WHOLE_BYTES = 2 << 30           # no float64 temporary of a whole-output reference is larger
+ERR_CHUNK = 1 << 26             # elements of an output compared at a time (dot_err_whole)
 # Worst distance of the device tanhf from the correctly rounded tanh of its own fp32 argument, in ulps of the output,
 # as test_tanh_and_relu6_epilogues_at_every_site measured it on an MI355X (in the tile kernel 1.396, k_splitk_epilogue
 # 1.315, k_splitk_epilogue_scalar 1.312; arguments spread over +-9.5, a quarter of the channels near 0). The assertion
@@ -114,6 +130,199 @@ def _wgrad_reference(prob, x_sub, dy_sub):
     return ref, mag
 
 
+# ------------------------------------------------------------- whole outputs: the same sums for every element, on `device`
+def _pad_hi(prob):
+    """Rows / columns of zeros below / right of x that the last output row / column reads."""
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    return max((OH - 1) * st - pt + (R - 1) * dil - (H - 1), 0), max((OW - 1) * st - pl + (S - 1) * dil - (W - 1), 0)
+
+
+def _chunks(prob):
+    """Output row chunks (n0, n1, y0, y1) — whole images, or row ranges of one image where one image is too large — such
+    that no float64 temporary of a tap walk (the padded x, a tap's [rows, C] slice, a [rows, K] product) exceeds WHOLE_BYTES.
+    The flat output rows of a chunk are contiguous: (n0*OH + y0)*OW up to (n0*OH + y0)*OW + (n1-n0)*(y1-y0)*OW."""
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    hi_y, hi_x = _pad_hi(prob)
+    limit = WHOLE_BYTES // 8
+    wp = (W + pl + hi_x) * C
+    per_img = max((H + pt + hi_y) * wp, OH * OW * max(C, K))
+    if per_img <= limit:
+        step = max(limit // per_img, 1)
+        return [(n0, min(n0 + step, N), 0, OH) for n0 in range(0, N, step)]
+    ystep = max(limit // max(OW * max(C, K), (st + (R - 1) * dil) * wp), 1)
+    return [(n, n + 1, y0, min(y0 + ystep, OH)) for n in range(N) for y0 in range(0, OH, ystep)]
+
+
+def _padded(x, prob, chunk, device, dtype):
+    """x of the chunk's images in `dtype` on `device`, zero-padded once, cut to the rows the chunk's output rows read:
+    its row j is input row y0*stride - pad_t + j, its column i input column i - pad_l."""
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    n0, n1, y0, y1 = chunk
+    lo, hi = y0 * st - pt, (y1 - 1) * st - pt + (R - 1) * dil           # first and last input row read
+    a = min(max(lo, 0), H)
+    b = max(min(hi, H - 1) + 1, a)
+    xs = x[n0:n1, a:b].to(device=device, dtype=dtype)
+    return torch.nn.functional.pad(xs, (0, 0, pl, _pad_hi(prob)[1], a - lo, hi + 1 - b))
+
+
+def _tap(t, prob, r, s, y0, y1):
+    """The strided slice of a padded map that tap (r, s) pairs with output rows y0..y1 (t's row 0 is padded row y0*stride)."""
+    OH, OW, st, dil = prob[7], prob[8], prob[9], prob[10]
+    a = t[:, r * dil:r * dil + (y1 - y0 - 1) * st + 1:st, s * dil:s * dil + (OW - 1) * st + 1:st, :]
+    assert a.shape[1:3] == (y1 - y0, OW)
+    return a
+
+
+def fwd_reference_whole(prob, operands, device, dtype=torch.float64):
+    """Every forward output by a plain tap walk of operands = (x, w) cast to `dtype`: x zero-padded once per chunk, for
+    each tap (r, s) its strided slice as [rows, C] times w[r, s]. -> (sum, sum |a*b|), each [N*OH*OW, K] on `device`."""
+    x, w = operands
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    wd = w.to(device=device, dtype=dtype)
+    wa = wd.abs()
+    ref = torch.zeros(N * OH * OW, K, dtype=dtype, device=device)
+    mag = torch.zeros_like(ref)
+    for chunk in _chunks(prob):
+        n0, n1, y0, y1 = chunk
+        xp = _padded(x, prob, chunk, device, dtype)
+        m0 = (n0 * OH + y0) * OW
+        m1 = m0 + (n1 - n0) * (y1 - y0) * OW
+        for r in range(R):
+            for s in range(S):
+                a = _tap(xp, prob, r, s, y0, y1).reshape(-1, C)
+                ref[m0:m1].addmm_(a, wd[r, s])
+                mag[m0:m1].addmm_(a.abs(), wa[r, s])
+    return ref, mag
+
+
+def dgrad_reference_whole(prob, operands, device, dtype=torch.float64):
+    """Every input gradient by the adjoint of that walk: operands = (dy, w); for each tap dy @ w[r, s].T is added into the
+    tap's strided slice of a zero-padded dx, which is cropped at the end. -> (sum, sum |a*b|), each [N*H*W, C]."""
+    dy, w = operands
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    hi_y, hi_x = _pad_hi(prob)
+    wd = w.to(device=device, dtype=dtype)
+    wa = wd.abs()
+    ref = torch.zeros(N, pt + H + hi_y, pl + W + hi_x, C, dtype=dtype, device=device)
+    mag = torch.zeros_like(ref)
+    for n0, n1, y0, y1 in _chunks(prob):
+        g = dy[n0:n1, y0:y1].to(device=device, dtype=dtype).reshape(-1, K)
+        ga = g.abs()
+        for r in range(R):
+            for s in range(S):
+                shape = (n1 - n0, y1 - y0, OW, C)
+                _tap(ref[n0:n1, y0 * st:], prob, r, s, y0, y1).add_((g @ wd[r, s].t()).reshape(shape))
+                _tap(mag[n0:n1, y0 * st:], prob, r, s, y0, y1).add_((ga @ wa[r, s].t()).reshape(shape))
+    crop = lambda t: t[:, pt:pt + H, pl:pl + W, :].reshape(N * H * W, C)
+    return crop(ref), crop(mag)
+
+
+def wgrad_reference_whole(prob, operands, device, dtype=torch.float64):
+    """Every filter gradient element: operands = (x, dy); per tap a.T @ g over all N*OH*OW pixels (what _wgrad_reference
+    does for a channel block). -> (sum, sum |a*b|), each [R, S, C, K]."""
+    x, dy = operands
+    N, H, W, C, K, R, S, OH, OW, st, dil, pt, pl = prob
+    ref = torch.zeros(R, S, C, K, dtype=dtype, device=device)
+    mag = torch.zeros_like(ref)
+    for chunk in _chunks(prob):
+        n0, n1, y0, y1 = chunk
+        xp = _padded(x, prob, chunk, device, dtype)
+        g = dy[n0:n1, y0:y1].to(device=device, dtype=dtype).reshape(-1, K)
+        ga = g.abs()
+        for r in range(R):
+            for s in range(S):
+                a = _tap(xp, prob, r, s, y0, y1).reshape(-1, C)
+                ref[r, s].addmm_(a.t(), g)
+                mag[r, s].addmm_(a.abs().t(), ga)
+    return ref, mag
+
+
+def dbias_reference_whole(prob, dy, device, dtype=torch.float64):
+    """The bias gradient, the column sum of dy over all pixels. -> (sum, sum |dy|), each [K]."""
+    K = prob[4]
+    ref = torch.zeros(K, dtype=dtype, device=device)
+    mag = torch.zeros_like(ref)
+    for n0, n1, y0, y1 in _chunks(prob):
+        g = dy[n0:n1, y0:y1].to(device=device, dtype=dtype).reshape(-1, K)
+        ref += g.sum(0)
+        mag += g.abs().sum(0)
+    return ref, mag
+
+
+def _err_chunks(y, ref, mag):
+    """(offset, errors) over flat chunks of an output: |y - ref| in units of 2^-24 * mag on the reference's device; where
+    the scale is 0 the error is 0 for an exact 0 and infinite for anything else, as it is for a NaN anywhere."""
+    yf, rf, mf = y.reshape(-1), ref.reshape(-1), mag.reshape(-1)
+    assert yf.numel() == rf.numel() == mf.numel(), (y.shape, ref.shape, mag.shape)
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=rf.device)
+    for o in range(0, rf.numel(), ERR_CHUNK):
+        yd, r, m = yf[o:o + ERR_CHUNK].to(rf.device).double(), rf[o:o + ERR_CHUNK].double(), mf[o:o + ERR_CHUNK].double()
+        err = torch.where(m > 0, (yd - r).abs() / (m * 2.0 ** -24), torch.where(yd == 0, torch.zeros_like(inf), inf))
+        yield o, torch.nan_to_num(err, nan=float("inf"), posinf=float("inf"))
+
+
+def dot_err_whole(y, ref, mag):
+    """tests/parity_report.py dot_err over every element without a host copy of the output: the worst |y - ref| in units of
+    2^-24 * mag and the flat index of that element. An output with scale 0 that is not exactly 0 (or one that is not a
+    number) makes the error infinite instead of raising, so that the caller can say where it is."""
+    worst, at = 0.0, 0
+    for o, err in _err_chunks(y, ref, mag):
+        v, i = err.max(0)
+        if float(v) > worst:
+            worst, at = float(v), o + int(i)
+    return worst, at
+
+
+def worst_whole(y, ref, mag, bound, k=20):
+    """The k worst elements of an output as [(error, flat index)], worst first, and the number of elements beyond `bound`."""
+    top, beyond = [], 0
+    for o, err in _err_chunks(y, ref, mag):
+        beyond += int((err > bound).sum())
+        v, i = err.topk(min(k, err.numel()))
+        top += [(float(a), o + int(b)) for a, b in zip(v, i)]
+    return sorted(top, reverse=True)[:k], beyond
+
+
+def locate(prob, mode, which, idx, info=None, sub_info=None):
+    """What flat index `idx` of an output means: of y / dx (which 0) the flat row, its image and pixel and the column; of dw
+    the tap, the row (input channel) and the column (output channel); of db (which 1) the column. With the plan's
+    ops.conv_plan_info `info` also the BM x BN tile of the GEMM it lies in and, for a K-split plan, the split that sums it
+    (of the main or the tail launch). `sub_info(parity class)` gives the sub-problem plans of an input-parity dgrad."""
+    N, H, W, C, K, R, S, OH, OW = prob[:9]
+    tile = lambda i, row, col: "" if not i or i["BM"] <= 0 or i["BN"] <= 0 else ", %dx%d tile (%d, %d) of the %d x %d GEMM" % (
+        i["BM"], i["BN"], row // i["BM"], col // i["BN"], i["M"], i["NG"])
+    if mode == 2 and which == 1:
+        return "db column %d" % idx
+    if mode == 2:
+        k, c, s, r = idx % K, idx // K % C, idx // (K * C) % S, idx // (K * C * S)
+        text = "dw tap (%d, %d), row %d, column %d" % (r, s, c, k)
+        if info and (info["M"], info["NG"]) == (C, K):
+            text += tile(info, c, k)
+            if info["nsplit"] > 1:
+                text += ", summed over %d splits of %d pixels" % (info["nsplit"], info["pix_per_split"])
+        return text
+    (hs, ws, width), name = ((OH, OW, K), "y") if mode == 0 else ((H, W, C), "dx")
+    row, col = idx // width, idx % width
+    n, py, px = row // (hs * ws), row // ws % hs, row % ws
+    text = "%s row %d, column %d (image %d, pixel %d, %d)" % (name, row, col, n, py, px)
+    if not info:
+        return text
+    if info["family"] == "input_parity" and sub_info is not None:
+        cy, cx = py & 1, px & 1
+        h2, w2 = (hs - cy + 1) // 2, (ws - cx + 1) // 2
+        info, row = sub_info(cy * 2 + cx), (n * h2 + py // 2) * w2 + px // 2
+        text += ", parity class %d row %d" % (cy * 2 + cx, row)
+    elif info["M"] != N * hs * ws:
+        return text + ("" if info["BM"] <= 0 else ", plan %s runs a %d x %d GEMM in %dx%d tiles" % (
+            info["family"], info["M"], info["NG"], info["BM"], info["BN"]))
+    text += tile(info, row, col)
+    if info["BM"] > 0 and info["tail_rows"] > 0 and row >= (-(-info["M"] // info["BM"]) - info["tail_rows"]) * info["BM"]:
+        text += ", K-split tail launch: %d splits of %d K-steps" % (info["tail_nsplit"], info["tail_ks"])
+    elif info["nsplit"] > 1:
+        text += ", K split: %d splits of %d of %d K-steps" % (info["nsplit"], info["ks_per_split"], info["ksteps"])
+    return text
+
+
 # ------------------------------------------------------- expected values: a reference plus the epilogue's addends
 def _np(v):
     return v.numpy() if torch.is_tensor(v) else np.asarray(v)
@@ -185,6 +394,38 @@ def wgrad_expected(prob, x, dy, cs, ks, scale=None, beta=1.0, dw_old=None, db_ol
             (sel_b,) + _plus(dy_sub.sum((0, 1, 2)), dy_sub.abs().sum((0, 1, 2)), old(db_old, sel_b)))
 
 
+def _on(device, dtype, *ts):
+    return [None if t is None else t.to(device=device, dtype=dtype) for t in ts]
+
+
+def fwd_expected_whole(prob, x, w, device, bias=None, res=None, relu=False, dtype=torch.float64):
+    """fwd_expected for every output element, on `device`. -> (ref, mag), each [N*OH*OW, K]."""
+    bias, res = _on(device, dtype, bias, res)
+    ref, mag = fwd_reference_whole(prob, (x, w), device, dtype)
+    ref, mag = _plus(ref, mag, None if bias is None else bias[None, :], None if res is None else res.reshape(ref.shape))
+    return (torch.relu(ref) if relu else ref), mag
+
+
+def dgrad_expected_whole(prob, dy, w, device, resd=None, prev=None, mask=None, dtype=torch.float64):
+    """dgrad_expected for every input element (a masked one exactly 0 on scale 1). -> (ref, mag), each [N*H*W, C]."""
+    ref, mag = dgrad_reference_whole(prob, (dy, w), device, dtype)
+    ref, mag = _plus(ref, mag, *(None if t is None else t.reshape(ref.shape) for t in _on(device, dtype, resd, prev)))
+    if mask is not None:
+        on = (mask.to(device) > 0).reshape(ref.shape)
+        ref, mag = ref * on, torch.where(on, mag, torch.ones_like(mag))
+    return ref, mag
+
+
+def wgrad_expected_whole(prob, x, dy, device, scale=None, beta=1.0, dw_old=None, db_old=None, dtype=torch.float64):
+    """wgrad_expected for every element. -> (ref, mag) of dw [R, S, C, K], (ref, mag) of db [K]."""
+    scale, dw_old, db_old = _on(device, dtype, scale, dw_old, db_old)
+    ref, mag = wgrad_reference_whole(prob, (x, dy), device, dtype)
+    if scale is not None:
+        ref, mag = scale * ref, scale.abs() * mag
+    old = lambda t: None if t is None else beta * t
+    return _plus(ref, mag, old(dw_old)), _plus(*dbias_reference_whole(prob, dy, device, dtype), old(db_old))
+
+
 def fp32_spacing(v64):
     """The spacing of fp32 at |v| (float64 in and out)."""
     return np.spacing(np.maximum(np.abs(_np(v64)), np.finfo(np.float32).tiny).astype(np.float32)).astype(np.float64)
@@ -216,14 +457,33 @@ def prob_of(d):
 
 
 def family_lines(run):
-    """Report lines, one per plan family, of (family, mode, error) records: cases and worst error per mode."""
-    fams = {}
-    for fam, mode, err in run:
+    """Report lines, one per plan family, of (family, mode, error) records: cases and worst sampled error per mode. A
+    record that goes on with (whole-output worst error, elements compared, worst device-vs-CPU reference difference) adds
+    a second line to its family (whole_line)."""
+    fams, whole = {}, {}
+    for fam, mode, err, *rest in run:
         f = fams.setdefault(fam, [[0, 0.0], [0, 0.0], [0, 0.0]])
         f[mode][0] += 1
         f[mode][1] = max(f[mode][1], err)
-    return ["    %-16s %d / %d / %d cases; worst error in 2^-24*sum|ab| units %s" % (
-        name, f[0][0], f[1][0], f[2][0], " / ".join("%.2f" % v[1] for v in f)) for name, f in sorted(fams.items())]
+        if rest:
+            whole.setdefault(fam, []).append((mode,) + tuple(rest))
+    lines = []
+    for name, f in sorted(fams.items()):
+        lines.append("    %-16s %d / %d / %d cases; worst error in 2^-24*sum|ab| units %s" % (
+            name, f[0][0], f[1][0], f[2][0], " / ".join("%.2f" % v[1] for v in f)))
+        if name in whole:
+            lines.append(whole_line(whole[name]))
+    return lines
+
+
+def whole_line(records):
+    """Report line of (mode, whole-output worst error, elements compared, reference difference) records of one family."""
+    worst, elements, diff = [0.0, 0.0, 0.0], [0, 0, 0], 0.0
+    for mode, err, n, d in records:
+        worst[mode], elements[mode], diff = max(worst[mode], err), elements[mode] + n, max(diff, d)
+    return ("        every output element: %s elements compared; worst error %s; float64 reference on the device against "
+            "the CPU's on the sample: worst %.3f of n*2^-52*scale" % (
+                " / ".join("%d" % n for n in elements), " / ".join("%.2f" % v for v in worst), diff))
 
 
 def plan_test_ops(planning_switches=None):
@@ -258,6 +518,8 @@ class ConvCase:
         self.w = (self.rand(R, S, C, K) - 0.5) * (2.0 / np.sqrt(R * S * C))
         self.dy = self.rand(N, OH, OW, K) - 0.5                             # zero-mean
         self.sample, self.expected = {}, {}     # mode -> (rows, cols) / (cs, ks); mode -> [(select, ref, mag)] per output
+        self.whole, self.whole_stats = {}, {}   # mode -> [(ref, mag)] per output, whole and on the device; mode -> figures
+        self.relu = False
 
     def prepare(self, mode, rows=_rows, cols=None, res=True, relu=False):
         """Draws the extras of the mode (0: bias, res; 1: resd, prev, mask; 2: scale, dw_old, db_old), then its sample,
@@ -267,7 +529,7 @@ class ConvCase:
         N, H, W, C, K, R, S, OH, OW = self.prob[:9]
         rand, rng = self.rand, self.rng
         if mode == 0:
-            self.bias, self.res = rand(K) - 0.5, (rand(N, OH, OW, K) - 0.5 if res else None)
+            self.bias, self.res, self.relu = rand(K) - 0.5, (rand(N, OH, OW, K) - 0.5 if res else None), relu
             s = self.sample[0] = (rows(N, OH, OW, rng), cols and cols(K, rng))
             self.expected[0] = [fwd_expected(self.prob, self.x, self.w, s[0], s[1], self.bias, self.res, relu)]
         elif mode == 1:
@@ -310,6 +572,76 @@ class ConvCase:
             note(errs, lims)
         assert all(e <= lim for e, lim in zip(errs, lims)), (MODE_NAMES[mode], tag, errs, lims)
         return errs
+
+    def prepare_whole(self, mode, dtype=torch.float64):
+        """After prepare(mode), and drawing nothing: the expected value and its scale of EVERY element of the mode's
+        outputs, [(ref, mag)] per output on the operands' device, from the operands and extras prepare(mode) drew. Kept
+        as whole[mode] in float64; in another dtype (float32: the plain evaluation a rounding tail is measured by) only
+        returned."""
+        p, dev = self.prob, self.x.device
+        if mode == 0:
+            out = [fwd_expected_whole(p, self.x, self.w, dev, self.bias, self.res, self.relu, dtype)]
+        elif mode == 1:
+            out = [dgrad_expected_whole(p, self.dy, self.w, dev, self.resd, self.prev, dtype=dtype)]
+        else:
+            out = list(wgrad_expected_whole(p, self.x, self.dy, dev, self.scale, 1.0, self.dw_old, self.db_old, dtype))
+        if dtype == torch.float64:
+            self.whole[mode] = out
+        return out
+
+    def reference_difference(self, mode):
+        """Pins the device's float64 matmul, a library kernel: the whole reference (and its scale) on the sample against
+        the CPU reference of prepare(mode). Two float64 summation orders of n exact products differ by at most
+        n * 2^-52 * sum|ab| to first order, n the reduction length — asserted per element. -> the worst ratio to it."""
+        N, H, W, C, K, R, S, OH, OW = self.prob[:9]
+        n, worst = (R * S * C, R * S * K, N * OH * OW)[mode], 0.0
+        for (ref_w, mag_w), (sel, ref, mag) in zip(self.whole[mode], self.expected[mode]):
+            tol = n * 2.0 ** -52 * mag
+            for what, a, b in (("sum", ref_w, ref), ("scale", mag_w, mag)):
+                diff = (sel(a).cpu() - b).abs()
+                assert bool((diff <= tol).all()), ("float64 reference on the device against the CPU's", MODE_NAMES[mode], what,
+                                                  float((diff / tol.clamp_min(1e-300)).max()))
+                if bool((tol > 0).any()):
+                    worst = max(worst, float((diff[tol > 0] / tol[tol > 0]).max()))
+        return worst
+
+    def whole_errors(self, mode, outs):
+        """dot_err_whole of every output of the mode: [(worst error, flat index)]."""
+        if mode not in self.whole:
+            self.prepare_whole(mode)
+        return [dot_err_whole(o, ref, mag) for o, (ref, mag) in zip(_tuple(outs), self.whole[mode])]
+
+    def describe(self, mode, which, idx):
+        """locate() with the plan the library gives this problem now (host arithmetic: works without a GPU)."""
+        from mtl_ssl_amd import ops
+        from mtl_ssl_amd.lib import ConvDesc
+        d = ConvDesc(*self.prob, 0)
+        return locate(self.prob, mode, which, idx, ops.conv_plan_info(d, mode), lambda c: ops.conv_plan_info(d, mode, c))
+
+    def check_whole(self, mode, outs, bound, tag, note=None):
+        """check_errors over EVERY element of the mode's outputs, against float64 references built on the operands'
+        device (prepare_whole; pinned to the CPU reference on the sample first, the figures in whole_stats[mode]). A miss
+        names the worst element — row, column, tile, split — lists the 20 worst, counts the elements beyond the bound and
+        gives the error of a plain float32 tap walk of the same operands in the same unit. -> errs."""
+        found = self.whole_errors(mode, outs)
+        self.whole_stats[mode] = dict(elements=sum(o.numel() for o in _tuple(outs)), ref_diff=self.reference_difference(mode))
+        errs = [e for e, _ in found]
+        lims = [bound] + [DIRECT_BOUND] * (len(errs) - 1)
+        if note is not None:
+            note(errs, lims)
+        if all(e <= lim for e, lim in zip(errs, lims)):
+            return errs
+        plain = self.prepare_whole(mode, torch.float32)
+        lines = []
+        for which, (o, (ref, mag), (e, at), lim) in enumerate(zip(_tuple(outs), self.whole[mode], found, lims)):
+            if e <= lim:
+                continue
+            top, beyond = worst_whole(o, ref, mag, lim)
+            lines.append("%s whole output %d: worst %.2f > %s at %s; %d of %d elements beyond; a plain float32 tap walk: %.2f" % (
+                MODE_NAMES[mode], which, e, lim, self.describe(mode, which, at), beyond, o.numel(),
+                dot_err_whole(plain[which][0], ref, mag)[0]))
+            lines += ["    %.2f at %s" % (v, self.describe(mode, which, i)) for v, i in top]
+        raise AssertionError("\n".join(lines + [repr(tag)]))
 
     def check_exact_epilogue(self, mode, got, linear, *ctx):
         """The nonlinear epilogues are exact functions of the linear result (the split-K fold sums in a fixed order)."""

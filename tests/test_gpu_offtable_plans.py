@@ -6,9 +6,12 @@ the fixture equal to the sweep on a CPU).
 
 Each case first asks the planner (ops.conv_plan_info) and requires the recorded signature, so it cannot pass by running
 another plan; then it runs the call the way tests/test_gpu_plan_table.py does (post-ReLU-like x, zero-mean dy, bias,
-residual, previous contents for ACCUM, out_scale, dbias with beta = 1) and compares sampled outputs with the float64
+residual, previous contents for ACCUM, out_scale, dbias with beta = 1) and compares the outputs with the float64
 references of tests/conv_ref.py in units of 2^-24 * (sum |a*b| + |addends|): at most 8 for a direct plan, 400 for a Winograd
-plan, 8 for the bias gradient. The row sample is extended by the places where these plans can go wrong: both sides of the
+plan, 8 for the bias gradient. Every output element is compared, with a float64 reference of the whole output built on the
+device (ConvCase.check_whole: a miss names row, column, tile and split); before it the sampled reference built on the CPU
+runs as before — the independent check of the device's reference, which must equal it on the sample, and the series of
+numbers the parity report has carried. The row sample is extended by the places where these plans can go wrong: both sides of the
 main / tail boundary and the ends of the tail region, and the last partial Winograd tile along each axis. The ReLU
 forward epilogue and the ReLU-mask dgrad epilogue must be exact functions of the linear result, every output finite under
 the NaN-poisoned workspaces (conftest: MTLSSL_POISON_WS).
@@ -46,7 +49,7 @@ def _tool():
 TOOL = _tool()
 FIXTURE = json.load(open(TOOL.FIXTURE))
 CASES = [(tuple(e["descriptor"]), e["mode"], e["signature"]) for e in FIXTURE["problems"]]
-_RUN = {}                       # (problem, mode) -> (family, worst error)
+_RUN = {}                       # (problem, mode) -> (family, worst sampled error[, worst whole-output error, elements, reference difference])
 
 
 @pytest.fixture(scope="module")
@@ -126,7 +129,14 @@ def test_offtable_plan_matches_float64(ops, prob, mode, want):
     def note(errs, lims):
         print("%s %s: errors %s of %s (2^-24 * sum|ab| units)" % (_pid(prob, mode), sig[1], ["%.2f" % e for e in errs], lims))
         _RUN[(prob, mode)] = (sig[1], errs[0])
-    case.check_errors(mode, outs, WINO_BOUND if sig[1].startswith("winograd") else DIRECT_BOUND, sig, note)
+    bound = WINO_BOUND if sig[1].startswith("winograd") else DIRECT_BOUND
+    case.check_errors(mode, outs, bound, sig, note)
+
+    def note_whole(errs, lims):
+        print("%s %s: every element %s of %s" % (_pid(prob, mode), sig[1], ["%.2f" % e for e in errs], lims))
+        st = case.whole_stats[mode]
+        _RUN[(prob, mode)] += (errs[0], st["elements"], st["ref_diff"])
+    case.check_whole(mode, outs, bound, sig, note_whole)
     if mode < 2:
         case.check_exact_epilogue(mode, case.call(ops, d, mode, nonlinear=True), outs, sig)
 
@@ -188,5 +198,5 @@ def _report():
     parity_report.add("off-table plans (%d representatives of %d signatures reached, %d covered by the plan table); per "
                       "family (fwd / dgrad / wgrad):" % (len(_RUN), FIXTURE["counts"]["signatures_reached"],
                                                          FIXTURE["counts"]["signatures_covered_by_table"]))
-    for line in family_lines((fam, mode, err) for (prob, mode), (fam, err) in _RUN.items()):
+    for line in family_lines((fam, mode, *rest) for (prob, mode), (fam, *rest) in _RUN.items()):
         parity_report.add(line)

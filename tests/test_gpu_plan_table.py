@@ -1,13 +1,18 @@
 """Every (problem, mode) of the committed plan table (mtl_ssl_amd/conv_plans.json: the 150 distinct convolution layers of
 the four shipped configurations) at its full production size, on the plan production picks — the pinned code where the
 table pins one, the library's planner (split-K main + tail + fold, the LDS-DMA engine, the Winograd variants, the padded
-/ VALU forms) where it says -1 — against a float64 reference built on the CPU.
+/ VALU forms) where it says -1 — against float64.
 
-The reference never shortens a reduction; it samples outputs instead: ~256 flat output rows of the forward (all K
-channels each) and input rows of the dgrad (all C channels), tile boundaries and image corners included, and every
-(r, s) tap of a channel block of the filter gradient summed over all N*OH*OW pixels. Errors are measured in units of
-2^-24 * (sum |a*b| + |the epilogue's addends|) (tests/parity_report.py dot_err): at most 8 for a direct plan, 400 for a
-Winograd plan. The nonlinear epilogues (ReLU, the ReLU mask) must be exact functions of the linear result, bit for bit.
+Every element of every output is compared: tests/conv_ref.py builds the float64 reference of the whole output by a plain
+tap walk on the device (ConvCase.check_whole) — a wrong tile in the middle of the grid, a K-step dropped in one dw tile
+column, a tile the swizzle maps twice have nowhere to hide — and a miss names row, column, tile and split. Before it the
+sampled reference built on the CPU runs as it always did: ~256 flat output rows of the forward (all K channels each)
+and input rows of the dgrad (all C channels), tile boundaries and image corners included, and every (r, s) tap of a
+16 x 16 channel block of the filter gradient summed over all N*OH*OW pixels. It is the independent check of the device's
+float64 reference (held equal to it on the sample to n * 2^-52 * scale) and keeps the report's series of sampled numbers.
+Neither shortens a reduction. Errors are measured in units of 2^-24 * (sum |a*b| + |the epilogue's addends|)
+(tests/parity_report.py dot_err): at most 8 for a direct plan, 400 for a Winograd plan, on the sample and on the whole
+output alike. The nonlinear epilogues (ReLU, the ReLU mask) must be exact functions of the linear result, bit for bit.
 The same list then runs through the production Winograd filter cache (ops.FilterXfCache) and the kept input transform,
 and on the split-bf16 fp32 engine. Only the modes the table lists for a problem run: those are the calls the model
 makes. Workspaces stay NaN-poisoned (conftest: MTLSSL_POISON_WS)."""
@@ -21,7 +26,7 @@ import pytest
 import torch
 
 from tests import parity_report
-from tests.conv_ref import DIRECT_BOUND, MODE_NAMES, WINO_BOUND, ConvCase, pid as _pid, plan_test_ops
+from tests.conv_ref import DIRECT_BOUND, MODE_NAMES, WINO_BOUND, ConvCase, pid as _pid, plan_test_ops, whole_line
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +43,7 @@ def _load():
 
 
 PROBLEMS = _load()              # [(N, H, W, C, K, R, S, OH, OW, stride, dilation, pad_t, pad_l), {mode: table value}]
-_RUN = {}                       # (problem, mode) -> {"cfg", "family", "err", "split"}
+_RUN = {}                       # (problem, mode) -> {"cfg", "family", "err", "split", "whole", "whole_split", "elements", "ref_diff"}
 
 
 @pytest.fixture(scope="module")
@@ -97,6 +102,11 @@ def test_production_plan_matches_float64(ops, prob, modes):
             _RUN[(prob, mode)] = dict(cfg=cfg, family=_family(ops, d, mode), err=errs[0], split=None)
         case.check_errors(mode, o, _bound(ops, cfg), cfg, note)
 
+        def note_whole(errs, lims):
+            print("%s: every element %s of %s (sample %.2f)" % (_pid(prob, mode), ["%.2f" % e for e in errs], lims, _RUN[(prob, mode)]["err"]))
+            _RUN[(prob, mode)].update(whole=errs[0], whole_split=None, **case.whole_stats[mode])
+        case.check_whole(mode, o, _bound(ops, cfg), (MODE_NAMES[mode], cfg), note_whole)
+
     for mode in (0, 1):
         if mode in modes:
             case.check_exact_epilogue(mode, call(mode, nonlinear=True), out[mode], _cfg(d, mode))
@@ -127,6 +137,9 @@ def test_production_plan_matches_float64(ops, prob, modes):
             rec = _RUN[(prob, mode)]
             rec["split"] = e
             assert e <= 1.25 * max(rec["err"], 1.0) + 2.5, (MODE_NAMES[mode], rec, e)
+            (e_whole, at), lim = case.whole_errors(mode, o)[0], 1.25 * max(rec["whole"], 1.0) + 2.5
+            rec["whole_split"] = e_whole
+            assert e_whole <= lim, ("split engine, every element", MODE_NAMES[mode], rec, e_whole, lim, case.describe(mode, 0, at))
     finally:
         ops.set_fp32_engine(0)
 
@@ -141,6 +154,12 @@ def _split_declines(ops, prob, mode, cfg):
     rows, cols = (N * OH * OW, K) if mode == 0 else (N * H * W, C)
     cols = -(-cols // 16) * 16
     return stride == 1 and not _is_wino(ops, cfg) and (cols < 256 or -(-rows // 256) * -(-cols // 256) < 192)
+
+
+def _output_elements(prob, mode):
+    """Elements a call of the mode writes: y, dx, or dw and the bias gradient."""
+    N, H, W, C, K, R, S, OH, OW = prob[:9]
+    return (N * OH * OW * K, N * H * W * C, R * S * C * K + K)[mode]
 
 
 def _winograd_entries(ops):
@@ -213,13 +232,18 @@ def _report():
         return
     fams = {}
     for (prob, mode), r in _RUN.items():
-        f = fams.setdefault(r["family"], dict(n=0, modes=[0, 0, 0], err=[0.0, 0.0, 0.0], split=[None, None, None], eng=0))
+        f = fams.setdefault(r["family"], dict(n=0, modes=[0, 0, 0], err=[0.0, 0.0, 0.0], split=[None, None, None], eng=0,
+                                              whole=[], whole_split=[None, None, None]))
         f["n"] += 1
         f["modes"][mode] += 1
         f["err"][mode] = max(f["err"][mode], r["err"])
         if r["split"] is not None:
             f["eng"] += 1
             f["split"][mode] = max(f["split"][mode] or 0.0, r["split"])
+        if "whole" in r:
+            f["whole"].append((mode, r["whole"], r["elements"], r["ref_diff"]))
+            if r["whole_split"] is not None:
+                f["whole_split"][mode] = max(f["whole_split"][mode] or 0.0, r["whole_split"])
     pinned = sum(1 for prob, m in PROBLEMS for mode, v in m.items() if v >= 0 and (prob, mode) in _RUN)
     parity_report.add("plan table at full size: %d (problem, mode) pairs of %d problems ran (%d pinned, %d on the "
                       "planner's choice); per family (fwd / dgrad / wgrad):" % (
@@ -230,6 +254,15 @@ def _report():
                           "%s (engaged on %d)" % (
                               name, f["n"], f["modes"][0], f["modes"][1], f["modes"][2],
                               " / ".join("%.2f" % v for v in f["err"]), " / ".join(fmt(v) for v in f["split"]), f["eng"]))
+        if f["whole"]:
+            parity_report.add(whole_line(f["whole"]) + "; split-bf16 %s" % " / ".join(fmt(v) for v in f["whole_split"]))
+    # coverage: what was compared is every element of every output of the pairs that ran — of all 359 when all ran
+    compared = sum(r.get("elements", 0) for r in _RUN.values())
+    pairs, table = sum(len(m) for _, m in PROBLEMS), sum(_output_elements(p, m) for p, ms in PROBLEMS for m in ms)
+    parity_report.add("    every output element compared with float64: %d elements of %d pairs (the table's %d pairs write %d)" % (
+        compared, len(_RUN), pairs, table))
+    assert compared == sum(_output_elements(p, m) for p, m in _RUN), "a (problem, mode) pair was not compared whole"
+    assert len(_RUN) < pairs or compared == table, (compared, table)     # the whole table ran: every element it writes
     engaged = [key for key, r in _RUN.items() if r["split"] is not None]
     parity_report.add("    split-bf16 engine engaged on %d of %d (problem, mode) pairs (%d problems); native bits on the rest" % (
         len(engaged), len(_RUN), len({p for p, _ in engaged})))

@@ -7,11 +7,14 @@ configs/vgg16/frcnn_vgg16_voc_mtl.config at 600x1024 and batch 1 under freeze_la
 Each case first asks the planner (ops.conv_plan_info) and requires the recorded signature, so it cannot pass by running
 another plan; then it makes the call the way tests/test_gpu_plan_table.py does (post-ReLU-like x, zero-mean dy, forward
 with bias and residual, dgrad with residual accumulated into previous contents, wgrad with out_scale, dbias and beta = 1)
-and compares sampled outputs with the float64 references of tests/conv_ref.py in units of 2^-24 * (sum |a*b| + |addends|):
-at most 8 for a direct, padded, thin or valu_fallback plan, 400 for a Winograd plan, 8 for the bias gradient. The reference
-samples outputs and never shortens a reduction. Rows: tests/conv_ref.py _rows plus the K-split tail boundaries and the last
+and compares the outputs with the float64 references of tests/conv_ref.py in units of 2^-24 * (sum |a*b| + |addends|):
+at most 8 for a direct, padded, thin or valu_fallback plan, 400 for a Winograd plan, 8 for the bias gradient. Every output
+element is compared, all 4096 columns of the wide FC layers included, with a float64 reference of the whole output built on
+the device (ConvCase.check_whole: a miss names row, column, tile and split). Before it the sampled reference built on the
+CPU runs as before: it is the independent check of the device's reference, which must equal it on the sample, and keeps the
+parity report's series. Neither shortens a reduction. Rows of the sample: tests/conv_ref.py _rows plus the K-split tail boundaries and the last
 partial Winograd tile (tests/test_gpu_offtable_plans.py _extra_rows); the FC problems have at most 640 rows and every one is
-compared. Where C = 25 088 or K = 4096 the reference is built on a sample of at least 64 output columns, tile boundaries
+compared. Where C = 25 088 or K = 4096 the CPU reference is built on a sample of at least 64 output columns, tile boundaries
 included (a float64 copy of the 25 088 x 4096 filter is 822 MB); the filter gradient is sampled by channel blocks as for
 every other layer. After conv1_1's forward — the VALU fallback indexed per element, on the largest map of the project — the
 whole last row and last column of the frame and its corners are compared as well. The ReLU forward epilogue and the
@@ -64,7 +67,7 @@ TOOL = _tool()
 FIXTURE = json.load(open(TOOL.FIXTURE))
 CASES = [(name, tuple(e["descriptor"]), e["mode"], e["signature"])
          for name in ("production", "representatives") for e in FIXTURE[name]]
-_RUN = {}                       # (list, problem, mode) -> (family, worst error)
+_RUN = {}                       # (list, problem, mode) -> (family, worst sampled error[, worst whole-output error, elements, reference difference])
 _FC = {}                        # (problem, mode) -> (kernel error, torch CPU float32 error) of the long FC reductions
 _T0 = [None]
 
@@ -170,7 +173,15 @@ def test_vgg16_plan_matches_float64(ops, name, prob, mode, want):
         if cpu32 is not None:
             _FC[(prob, mode)] = (errs[0], cpu32)
     wino = sig[1].startswith("winograd")
-    case.check_errors(mode, outs, WINO_BOUND if wino else (FC_BOUND if _wide_fc(prob) else DIRECT_BOUND), sig, note)
+    bound = WINO_BOUND if wino else (FC_BOUND if _wide_fc(prob) else DIRECT_BOUND)
+    case.check_errors(mode, outs, bound, sig, note)
+
+    def note_whole(errs, lims):                                         # every column, also where `cols` restricts the sample
+        print("%s %s: every element %s of %s" % (_pid(name, prob, mode), sig[1], ["%.2f" % e for e in errs], lims))
+        st = case.whole_stats[mode]
+        _RUN[(name, prob, mode)] += (errs[0], st["elements"], st["ref_diff"])
+    case.check_whole(mode, outs, bound, sig, note_whole)
+    case.whole.clear()
 
     # a second call gives the same bits (the K-split fold and the Winograd transforms sum in a fixed order)
     again = call()
@@ -230,7 +241,7 @@ def _report():
                       "plan table or the off-table fixture); per family (fwd / dgrad / wgrad):" % (
                           sum(1 for k in _RUN if k[0] == "production"), sum(1 for k in _RUN if k[0] == "representatives"),
                           c["signatures_reached"], c["signatures_covered_by_table_or_offtable"]))
-    for line in family_lines((fam, mode, err) for (name, prob, mode), (fam, err) in _RUN.items()):
+    for line in family_lines((fam, mode, *rest) for (name, prob, mode), (fam, *rest) in _RUN.items()):
         parity_report.add(line)
     for (prob, mode), (e, e32) in sorted(_FC.items()):
         parity_report.add("    FC %d rows, %d -> %d, %s (%d-term reduction): kernel %.2f, torch CPU float32 matmul on the same "
