@@ -11,6 +11,7 @@ from oracle import assign as A
 from oracle import boxes as B
 from oracle import frcnn_losses as L
 from oracle import nms as N
+from tests import detection_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -83,8 +84,10 @@ def test_coder(ops, vec):
     for b in range(2):
         np.testing.assert_array_equal(dec[b], B.decode(codes[b], anc))      # bit-exact: exp by portable_math on both sides
     bx = rand_boxes(rng, 5000, 600, 1024)
-    np.testing.assert_allclose(ops.boxes_encode(cu(bx), cu(anc)).cpu().numpy(), B.encode(bx, anc),
-                               rtol=1e-4, atol=1e-5)
+    # ty, tx bit for bit the oracle's fp32 sequence; th, tw within LOG_ULPS of the device logf; all four inside the
+    # bounds of encode64 (tests/detection_ref.py: check_encode)
+    sf = (10.0, 10.0, 5.0, 5.0)
+    R.check_encode(ops.boxes_encode(cu(bx), cu(anc)).cpu().numpy(), B.encode(bx, anc), bx, anc, sf, "boxes_encode, 5000 boxes")
 
 
 def test_gather_scatter(ops):
@@ -247,6 +250,14 @@ def test_rpn_proposals_degenerate_inputs(ops):
     np.testing.assert_allclose(ob.cpu().numpy(), rbx, rtol=1e-5, atol=1e-4)
 
 
+def _check_reg_targets(got, r, anchors, gt, what):
+    """reg_targets under the coder's bounds (tests/detection_ref.py: check_encode): exact zeros on unmatched anchors, ty / tx
+    bit for bit the oracle's, th / tw within LOG_ULPS of the device logf, all four inside the bounds of encode64."""
+    pos = r["match"] >= 0
+    assert (got[~pos].view(np.int32) == 0).all(), what
+    R.check_encode(got[pos], r["reg_targets"][pos], gt[r["match"][pos]], anchors[pos], (10.0, 10.0, 5.0, 5.0), what)
+
+
 def _assign_case(rng, n, G, B_=2, H=600, W=1024):
     anchors = rand_boxes(rng, n, H, W, 16.0)
     gts, ngt = np.zeros((B_, max(G, 1), 4), np.float32), np.zeros((B_,), np.int32)
@@ -271,8 +282,7 @@ def test_assign_targets_rpn_bit_exact(ops, n, G):
         np.testing.assert_array_equal(out["cls_targets"][b].cpu().numpy(), r["cls_targets"])
         np.testing.assert_array_equal(out["cls_weights"][b].cpu().numpy(), r["cls_weights"])
         np.testing.assert_array_equal(out["reg_weights"][b].cpu().numpy(), r["reg_weights"])
-        np.testing.assert_allclose(out["reg_targets"][b].cpu().numpy(), r["reg_targets"],
-                                   rtol=1e-4, atol=1e-5)
+        _check_reg_targets(out["reg_targets"][b].cpu().numpy(), r, anchors, gts[b, :ngt[b]], "rpn targets n=%d G=%d image %d" % (n, G, b))
 
 
 def test_assign_targets_detector_with_closeness(ops):
@@ -294,8 +304,7 @@ def test_assign_targets_detector_with_closeness(ops):
         np.testing.assert_array_equal(out["match"][b].cpu().numpy(), r["match"])
         np.testing.assert_array_equal(out["cls_targets"][b].cpu().numpy(), r["cls_targets"])
         np.testing.assert_array_equal(out["extra_targets"][b].cpu().numpy(), r["closeness_targets"])
-        np.testing.assert_allclose(out["reg_targets"][b].cpu().numpy(), r["reg_targets"],
-                                   rtol=1e-4, atol=1e-5)
+        _check_reg_targets(out["reg_targets"][b].cpu().numpy(), r, props[b], gts[b, :ngt[b]], "detector targets image %d" % b)
 
 
 def test_matcher_golden_via_assign(ops, vec):
