@@ -31,7 +31,7 @@ typedef void* mtlssl_stream_t; /* hipStream_t */
 
 /* Bumped whenever a prototype below changes; mtlssl_abi_version() of the loaded library must equal it (the ctypes
  * loader checks: an older build called through a newer header would receive shifted arguments). */
-#define MTLSSL_ABI_VERSION 22
+#define MTLSSL_ABI_VERSION 23
 
 const char* mtlssl_last_error(void);
 int mtlssl_abi_version(void);
@@ -319,6 +319,36 @@ int64_t mtlssl_bn_param_grads_workspace_bytes(int C);
 int mtlssl_bn_param_grads(const float* y, const float* g, const float* gamma, const float* beta,
                           float* dgamma, float* dbeta, int64_t rows, int C, float accum, void* workspace,
                           mtlssl_stream_t stream);
+
+/* ------------------------------------------------------------------ batch-statistics BatchNorm
+ * slim.batch_norm in TRAINING mode (fused=None, i.e. the fused kernel), the normalizer_fn that a hyperparams block with
+ * `batch_norm { train: true }` installs while training (protos/hyperparams.proto:101-110,
+ * builders/hyperparams_builder.py:56-76, 156-175), over x [rows, C] = the bias-free output of the layer's filter (NHWC
+ * flattened: rows = all pixels, or all RoIs, of the per-GPU batch), n = rows:
+ *   mean = sum(x) / n          var = sum((x - mean)^2) / n     (biased, from deviations, never E[x^2] - mean^2)
+ *   inv_std = 1 / sqrt(var + eps)                               (correctly rounded fp32 sqrt and division)
+ *   y = act(((x - mean) * inv_std) * gamma + beta)              gamma null: 1 (scale: false); beta null: 0 (center: false)
+ * act: epilogue 0, MTLSSL_EPI_RELU or MTLSSL_EPI_RELU6. save_mean / save_inv_std [C] are what the backward reads.
+ * moving_mean / moving_var [C] (both or neither) are updated in place by slim's
+ * assign_moving_average(zero_debias=False), as one unfused fp32 sequence with f = float(1 - decay):
+ *   moving_mean -= (moving_mean - mean) * f
+ *   moving_var  -= (moving_var - (var * n) / max(n - 1, 1)) * f      (the fused kernel's Bessel-corrected output)
+ * One launch, no workspace: one workgroup owns 32 channels and walks every row three times (mean, variance, normalise);
+ * the per-channel partials of its 64 row lanes combine in registers and LDS in a fixed order — no atomics, two calls on
+ * the same data agree bit for bit. Any rows in [1, 2^24], any C >= 1. */
+int mtlssl_batch_norm_train_fwd(const float* x, const float* gamma, const float* beta, float* y, float* save_mean,
+                                float* save_inv_std, float* moving_mean, float* moving_var, int64_t rows, int C,
+                                float eps, float f, int epilogue, mtlssl_stream_t stream);
+/* Its gradient. dy [rows, C] = dL/dy; with mask_epilogue MTLSSL_EPI_MASK (ReLU) or MTLSSL_EPI_MASK6 (ReLU6) the
+ * activation's mask is taken from y (the forward's output, required then) inside: g = dy * mask(y), else g = dy.
+ * With xhat = (x - save_mean) * save_inv_std:
+ *   dbeta = sum(g)     dgamma = sum(g * xhat)     dx = (gamma * inv_std) * ((g - sum(g)/n) - xhat * (sum(g * xhat)/n))
+ * dgamma / dbeta may be null; accum != 0: d* = accum * d* + the sum (as mtlssl_bn_param_grads). Same launch shape,
+ * same determinism; dx may not alias x or dy. */
+int mtlssl_batch_norm_train_bwd(const float* x, const float* dy, const float* y, const float* gamma,
+                                const float* save_mean, const float* save_inv_std, float* dx, float* dgamma,
+                                float* dbeta, int64_t rows, int C, float accum, int mask_epilogue,
+                                mtlssl_stream_t stream);
 
 /* slim.avg_pool2d with TF 'SAME'/'VALID' semantics — the divisor is the number of in-bounds
  * cells of each window (slim/nets/inception_resnet_v2.py:181-184, Mixed_5b Branch_3). */

@@ -28,7 +28,9 @@ SOURCES = {
     "pascal_eval.hip": ["-ffp-contract=off"],    # PASCAL subset labelling: the host evaluator's double IoU arithmetic
     "aux_labels.hip": ["-ffp-contract=off"],     # labels from boxes: the host definitions' double arithmetic
     "summaries.hip": ["-ffp-contract=off"],      # variable histograms: the bucket rule and moments are double arithmetic
-    "visualize.hip": [],               # box overlay of the evaluator's visualisations (integer work only)
+    # batch-statistics BatchNorm: the moving-average update is an unfused fp32 sequence, sqrt and division correctly rounded
+    "batch_norm.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "visualize.hip": [],              # box overlay of the evaluator's visualisations (integer work only)
     "comm.hip": [],                     # RCCL wrappers (host code only; RCCL itself is bound with dlopen)
 }
 

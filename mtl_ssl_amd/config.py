@@ -108,6 +108,8 @@ DEFAULTS = {
     # protos/hyperparams.proto
     "Hyperparams": {"op": "CONV", "activation": "RELU", "regularizer": "@Regularizer",
                     "initializer": "@Initializer"},
+    # protos/hyperparams.proto:101-110 (nn.BatchNorm; a block carries the normaliser only when `batch_norm` is set)
+    "BatchNorm": {"decay": 0.999, "center": True, "scale": False, "epsilon": 0.001, "train": True},
     "L2Regularizer": {"weight": 1.0}, "L1Regularizer": {"weight": 1.0},
     "TruncatedNormalInitializer": {"mean": 0.0, "stddev": 1.0},
     "VarianceScalingInitializer": {"factor": 2.0, "uniform": False, "mode": "FAN_IN"},

@@ -35,19 +35,47 @@ def _l2_from_hyperparams(hp):
     return 0.0
 
 
+def _batch_norm_from_hyperparams(hp, is_training):
+    """builders/hyperparams_builder.py:56-61, 156-175: a block that has `batch_norm` puts slim.batch_norm behind every
+    layer its arg scope reaches -> a callable that makes the nn.BatchNorm of one layer; None for a block without."""
+    if not hp.has("batch_norm"):
+        return None
+    return lambda: nn.BatchNorm(hp.batch_norm, is_training)
+
+
+def _no_batch_norm(hp, field):
+    """The hyperparams blocks whose `batch_norm` is not built: a clear error, never a silently different model."""
+    if hp.has("batch_norm"):
+        raise ValueError("%s.batch_norm: batch statistics are not built in this head; remove the block (honoured: "
+                         "first_stage_box_predictor_conv_hyperparams, second_stage_box_predictor.mask_rcnn_box_predictor."
+                         "fc_hyperparams with op: FC)" % field)
+
+
 class MaskRCNNBoxPredictor:
     """core/box_predictor.py:339-611: RoI features -> (spatial mean | flatten) -> optional FC_i_depth layers, each
     followed by dropout when use_dropout -> FC heads. The depth of the extra layers is
     max(min(feature depth, max_depth), min_depth) and they exist only when that depth and
     num_layers_before_predictor are positive (:465-466, 479-488) — with the proto defaults (both 0) `use_dropout`
-    alone changes nothing in the reference, and nothing here."""
+    alone changes nothing in the reference, and nothing here.
 
-    def __init__(self, ps, scope, cin, num_classes, cfg, is_training, class_only, feat_hw=None, slot0=0):
+    fc_hyperparams.batch_norm: the block's arg scope reaches slim.fully_connected only when it has `op: FC`
+    (builders/hyperparams_builder.py:63-66); then every FC_i_depth layer is filter, normaliser, activation, dropout, and
+    both heads are normalised too — activation_fn=None does not switch the normalizer_fn off
+    (core/box_predictor.py:486-496). Without `op: FC` the scope covers the convolution ops, of which this predictor has
+    none: the block's batch_norm has no effect in the reference, and none here. `no_batch_norm`: the name of the
+    config field of a predictor whose batch_norm is refused (the auxiliary heads), or None."""
+
+    def __init__(self, ps, scope, cin, num_classes, cfg, is_training, class_only, feat_hw=None, slot0=0,
+                 no_batch_norm=None):
         if cfg.predict_instance_masks:
             raise ValueError("Mask prediction is unimplemented.")          # core/box_predictor.py:418-421
         if cfg.predict_keypoints:
             raise ValueError("Keypoint prediction is unimplemented.")
         init, wd = _init_from_hyperparams(cfg.fc_hyperparams), _l2_from_hyperparams(cfg.fc_hyperparams)
+        if no_batch_norm is not None:
+            _no_batch_norm(cfg.fc_hyperparams, no_batch_norm + ".mask_rcnn_box_predictor.fc_hyperparams")
+        bn = _batch_norm_from_hyperparams(cfg.fc_hyperparams, is_training) \
+            if str(cfg.fc_hyperparams.op) == "FC" else None
         self.num_classes, self.class_only = num_classes, class_only
         self.spatial_average = bool(cfg.spatial_average)
         self.is_training = is_training
@@ -67,36 +95,45 @@ class MaskRCNNBoxPredictor:
             self.stack = nn.FCStack(ps, ["%s/FC_%d_%d" % (scope, i, depth) for i in range(n_extra)], width,
                                     [depth] * n_extra, init, is_training, wd, activation=act,
                                     keep_prob=float(cfg.dropout_keep_probability) if cfg.use_dropout else None,
-                                    slot0=slot0)
+                                    slot0=slot0, batch_norm=bn)
             width = depth
         self.box = None
         if not class_only:
             self.box = nn.Conv(ps, scope + "/BoxEncodingPredictor", width, num_classes * 4, 1, init,
-                               is_training, wd, fc=True)
+                               is_training, wd, fc=True, batch_norm=bn and bn())
             self.cls = nn.Conv(ps, scope + "/ClassPredictor", width, num_classes + 1, 1, init, is_training,
-                               wd, fc=True)
+                               wd, fc=True, batch_norm=bn and bn())
         else:
             self.cls = nn.Conv(ps, scope + "/ClassPredictor", width, num_classes, 1, init, is_training, wd,
-                               fc=True)
+                               fc=True, batch_norm=bn and bn())
 
     def layers(self):
         extra = self.stack.layers if self.stack is not None else []
         return extra + [l for l in (self.box, self.cls) if l is not None]
 
-    def predict(self, feat, seed=0, step=0):
+    def predict(self, feat, seed=0, step=0, update=False):
+        """update: the normalisers' moving averages move (nn.BatchNorm.forward; the training step's forward only)."""
         pooled = ops.spatial_mean_fwd(feat) if self.spatial_average else feat.reshape(feat.shape[0], -1)
         net, sctx = pooled, None
         if self.stack is not None:
-            net, sctx = self.stack.forward(pooled, self.is_training, seed, step)
-        out = {"pooled": net, "_stack_ctx": sctx, "class": self.cls.forward(net)}
-        if self.box is not None:
-            out["box"] = self.box.forward(net)
+            net, sctx = self.stack.forward(pooled, self.is_training, seed, step, update)
+        out = {"pooled": net, "_stack_ctx": sctx}
+        for key, head in (("class", self.cls), ("box", self.box)):
+            if head is not None and head.batch_stats:
+                keep = out["_norm_" + key] = {}
+                out[key] = head.forward(net, keep, update)
+            elif head is not None:
+                out[key] = head.forward(net)
         return out
 
     def backward(self, pred, d_class, d_box, feat_shape, need_feat_grad=True, mask_ref=None, mask6=False):
         """Returns dL/d(feat); with mask_ref (= feat, an activation output) the activation gradient
         is fused in, i.e. the result is dL/d(pre-activation of feat)."""
         net = pred["pooled"]
+        if self.cls.norm is not None:
+            d_class = self.cls.norm_backward(pred.get("_norm_class"), pred["class"], d_class)
+            if d_box is not None:
+                d_box = self.box.norm_backward(pred.get("_norm_box"), pred["box"], d_box)
         self.cls.wgrad(net, d_class)
         if d_box is not None:
             self.box.wgrad(net, d_box)
@@ -181,9 +218,13 @@ class FasterRCNNMetaArch:
         self.num_anchors_per_location = A
         s = self.first_stage_box_predictor_scope
         depth, ks = int(frcnn.first_stage_box_predictor_depth), int(frcnn.first_stage_box_predictor_kernel_size)
+        # batch_norm of the block: the RPN Conv only — the two heads run with normalizer_fn=None
+        # (core/box_predictor.py:717-718). first_stage_box_predictor_trainable: false freezes the filter, not gamma / beta
+        rpn_bn = _batch_norm_from_hyperparams(hp, is_training)
         self.rpn_conv = nn.Conv(ps, s + "/Conv", fe.cout, depth, ks, init, rpn_tr, wd,
                                 activation="relu" if hp.activation == "RELU" else None,
-                                rate=int(frcnn.first_stage_atrous_rate))      # faster_rcnn_meta_arch.py:870-877
+                                rate=int(frcnn.first_stage_atrous_rate),      # faster_rcnn_meta_arch.py:870-877
+                                batch_norm=rpn_bn and rpn_bn())
         self.rpn_box = nn.Conv(ps, s + "/BoxEncodingPredictor", depth, A * 4, 1, init, rpn_tr, wd)
         self.rpn_cls = nn.Conv(ps, s + "/ClassPredictor", depth, A * 2, 1, init, rpn_tr, wd)
         # second stage (+ aux heads: builders/model_builder.py:287-315 give the aux predictors
@@ -199,7 +240,8 @@ class FasterRCNNMetaArch:
                 self.closeness_tower = fe.box_classifier_tower(self.closeness_box_predictor_scope, True)
                 self.layers += self.closeness_tower.layers()
             self.closeness_predictor = self._make_predictor(self.closeness_box_predictor_scope, K + 1,
-                                                            mtl.closeness_box_predictor, True, slot0=32)
+                                                            mtl.closeness_box_predictor, True, slot0=32,
+                                                            no_batch_norm="mtl.closeness_box_predictor")
             self.layers += self.closeness_predictor.layers()
         if mtl.window:
             if self._shared_classifier:
@@ -208,10 +250,12 @@ class FasterRCNNMetaArch:
                 self.window_tower = fe.box_classifier_tower(self.window_box_predictor_scope, True)
                 self.layers += self.window_tower.layers()
             self.window_predictor = self._make_predictor(self.window_box_predictor_scope, K + 1,
-                                                         mtl.window_box_predictor, True, slot0=48)
+                                                         mtl.window_box_predictor, True, slot0=48,
+                                                         no_batch_norm="mtl.window_box_predictor")
             self.layers += self.window_predictor.layers()
         if mtl.edgemask:
             ep = mtl.edgemask_predictor
+            _no_batch_norm(ep.conv_hyperparams, "mtl.edgemask_predictor.conv_hyperparams")
             self.edgemask_conv = nn.Conv(ps, self.edgemask_predictor_scope + "/BoxEncodingPredictor", fe.cout,
                                          2, int(ep.kernel_size), _init_from_hyperparams(ep.conv_hyperparams),
                                          is_training and ep.trainable, _l2_from_hyperparams(ep.conv_hyperparams),
@@ -223,6 +267,7 @@ class FasterRCNNMetaArch:
             # keep probability refine_dropout_rate when that is < 1, then fc{N+1} -> K + 1 without activation
             n_feat = (K + 1) * (1 + (self.N_EXPAND if mtl.window else 0) + (1 if mtl.closeness else 0))
             rh = mtl.refiner_fc_hyperparams
+            _no_batch_norm(rh, "mtl.refiner_fc_hyperparams")
             n_hidden = int(mtl.refine_num_fc_layers)
             self.refine_stack = None
             if n_hidden > 0:
@@ -243,9 +288,15 @@ class FasterRCNNMetaArch:
         # made on the device when first needed (the constructor stays on the host: model_builder.variable_specs)
         self._aux_stream_obj = self._wgrad_stream_obj = None
         self._bn_table = self._frozen_w_bn = self._dedup_overflow = None
+        # True only inside predict_for_training: the forward of a training step, which moves the moving averages of the
+        # heads' batch-statistics normalisers (nn.BatchNorm) once; predict / eval_loss never do
+        self._bn_update = False
 
-    def _make_predictor(self, scope, num_classes, bp_cfg, class_only, slot0=0):
-        """builders/box_predictor_builder.py:23-110 (mask_rcnn_box_predictor branch)."""
+    def _make_predictor(self, scope, num_classes, bp_cfg, class_only, slot0=0, no_batch_norm=None):
+        """builders/box_predictor_builder.py:23-110 (mask_rcnn_box_predictor branch). no_batch_norm: the config field of
+        an auxiliary head, whose fc_hyperparams.batch_norm is refused: the refiner's second, forward-only pass through
+        the window predictor would move its moving averages twice a step in an undefined order in the reference, and the
+        closeness predictor's is undecided with it."""
         if not bp_cfg.has("mask_rcnn_box_predictor"):
             raise ValueError("FasterRCNNMetaArch needs mask_rcnn_box_predictor (RFCNMetaArch handles "
                              "rfcn_box_predictor)")
@@ -253,7 +304,7 @@ class FasterRCNNMetaArch:
         P = (int(c.initial_crop_size) - int(c.maxpool_kernel_size)) // int(c.maxpool_stride) + 1
         return MaskRCNNBoxPredictor(self.ps, scope, self.tower.cout, num_classes, bp_cfg.mask_rcnn_box_predictor,
                                     self._is_training and bp_cfg.trainable and not self._first_stage_only,
-                                    class_only, feat_hw=self.tower.out_hw(P), slot0=slot0)
+                                    class_only, feat_hw=self.tower.out_hw(P), slot0=slot0, no_batch_norm=no_batch_norm)
 
     # ------------------------------------------------------------------ properties / plumbing
     @property
@@ -469,7 +520,11 @@ class FasterRCNNMetaArch:
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 aux = aux_forward()
-        pd = self._predict_from_features(x, F, trunk_ctx)
+        self._bn_update = True
+        try:
+            pd = self._predict_from_features(x, F, trunk_ctx)
+        finally:
+            self._bn_update = False
         if side is not None:
             ops.wait_on(side, "predict: aux heads")
         else:
@@ -481,7 +536,8 @@ class FasterRCNNMetaArch:
         B, H, W, _ = x.shape
         Hf, Wf = F.shape[1], F.shape[2]
         anchors, keep, n_all = self._anchors_for(Hf, Wf, H, W, x.device)
-        rpn_feat = self.rpn_conv.forward(F)
+        rpn_keep = {} if self.rpn_conv.batch_stats else None
+        rpn_feat = self.rpn_conv.forward(F, rpn_keep, self._bn_update) if rpn_keep is not None else self.rpn_conv.forward(F)
         enc_all = self.rpn_box.forward(rpn_feat).view(B, n_all, 4)
         cls_all = self.rpn_cls.forward(rpn_feat).view(B, n_all, 2)
         enc = ops.gather_rows(enc_all, keep) if keep is not None else enc_all
@@ -490,7 +546,7 @@ class FasterRCNNMetaArch:
             "rpn_box_predictor_features": rpn_feat, "rpn_features_to_crop": F,
             "image_shape": (B, H, W, 3), "rpn_box_encodings": enc,
             "rpn_objectness_predictions_with_background": logits, "anchors": anchors,
-            "_trunk_ctx": trunk_ctx, "_keep": keep, "_n_all": n_all,
+            "_trunk_ctx": trunk_ctx, "_keep": keep, "_n_all": n_all, "_rpn_norm": rpn_keep,
         }
         if not self._first_stage_only:
             pd.update(self._predict_second_stage(pd))
@@ -583,7 +639,7 @@ class FasterRCNNMetaArch:
                 cfeat_s, cctx_s = self.closeness_tower.forward(crops, self._is_training)
                 cp_s = self.closeness_predictor.predict(cfeat_s, self.seed, self.step)
         feat, tower_ctx = self.tower.forward(crops, self._is_training)
-        bp = self.box_predictor.predict(feat, self.seed, self.step)
+        bp = self.box_predictor.predict(feat, self.seed, self.step, update=self._bn_update)
         out = {
             "refined_box_encodings": bp["box"].view(B * N2, self.num_classes, 4),
             "class_predictions_with_background": bp["class"],
@@ -1090,8 +1146,11 @@ class FasterRCNNMetaArch:
         self.rpn_box.wgrad(rpn_feat, g_enc)
         self.rpn_cls.wgrad(rpn_feat, g_obj)
         g_rf = self.rpn_box.dgrad(rpn_feat.shape, g_enc)
-        relu = self.rpn_conv.activation == "relu"
+        # a batch-statistics normaliser applies the ReLU mask in its own backward, which follows
+        relu = self.rpn_conv.activation == "relu" and not self.rpn_conv.batch_stats
         self.rpn_cls.dgrad(rpn_feat.shape, g_obj, out=g_rf, accum=True, mask_ref=rpn_feat if relu else None)
+        if self.rpn_conv.norm is not None:
+            g_rf = self.rpn_conv.norm_backward(pd["_rpn_norm"], rpn_feat, g_rf)
         wg = self._wgrad_exec()
         wg.run(self.rpn_conv, F, g_rf)
         # last consumer of F: accumulate and apply the ReLU mask of the trunk output

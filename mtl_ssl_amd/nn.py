@@ -8,6 +8,9 @@ there are no stand-alone elementwise backward kernels in the trunk.
 Frozen BatchNorm (the reference always runs BN in inference mode during detector training,
 models/faster_rcnn_resnet_v1_feature_extractor.py:138,171) is folded: w_eff = w * scale[k],
 y = conv(x, w_eff) + shift[k]; dW = scale[k] * wgrad(x, g).
+
+The one normaliser that runs on batch statistics is the heads' (BatchNorm below: a hyperparams block's `batch_norm`):
+bias-free conv, then ops.batch_norm_train_fwd; its backward applies the activation's mask itself.
 """
 import torch
 
@@ -129,7 +132,7 @@ class _FrozenBN(Layer):
     def prepare(self):
         """w_eff in the shape the layer's kernels read: `w_eff_shape`."""
         ps = self.ps
-        b = ps.value(self.beta.name)
+        b = ps.value(self.beta.name) if self.beta is not None else 0.0      # no beta: slim.batch_norm(center=False)
         m, v = ps.value(self.mean.name), ps.value(self.var.name)
         self.inv_std = torch.rsqrt(v + self.eps)
         self.scale = ((ps.value(self.gamma.name) * self.inv_std) if self.gamma is not None
@@ -243,19 +246,148 @@ class DepthwiseBN(_FrozenBN):
                                    dgrad_epilogue(None, False, mask_ref, mask6))
 
 
+class BatchNorm(_FrozenBN):
+    """slim.batch_norm as the normalizer_fn of a hyperparams block that has `batch_norm { decay center scale epsilon
+    train }` (protos/hyperparams.proto:101-110, builders/hyperparams_builder.py:56-76, 156-175): the normaliser of ONE
+    filter without bias (nn.Conv(batch_norm=...)), which owns <layer scope>/BatchNorm/{beta, gamma, moving_mean,
+    moving_variance} — beta only with `center`, gamma only with `scale`; slim's initial values 0, 1, 0, 1. Two modes:
+
+    * batch statistics (`batch_stats`: is_training and batch_norm.train): y = act(gamma * xhat + beta) over the rows of
+      the per-GPU batch (ops.batch_norm_train_fwd / _bwd; nothing is synchronised between ranks), and — only where the
+      caller asks (`update`: the training step's forward) — the moving averages move by
+      assign_moving_average(zero_debias=False). Training never reads the moving values;
+    * frozen (is_training False — eval, export, Detector — or train: false): the moving statistics, folded into the
+      filter exactly as _FrozenBN does for the trunks (prepare / refold are its own).
+
+    gamma / beta are trainable iff is_training, whatever `train` says ('trainable': is_training, builder line 173) and
+    whether or not the filter is. DESIGN.md §7 (parity with TF 1.7 is unpinned)."""
+
+    def __init__(self, cfg, is_training):
+        super().__init__()
+        self.decay, self.eps = float(cfg.decay), float(cfg.epsilon)
+        self.center, self.with_scale = bool(cfg.center), bool(cfg.scale)
+        self.batch_stats = bool(is_training and cfg.train)
+        self.bn_trainable = bool(is_training)
+        self.f = ops.moving_average_factor(self.decay)
+
+    def bind(self, layer, field="batch_norm"):
+        """Registers the variables behind the filter of `layer` (an nn.Conv), in slim's order."""
+        if layer.activation not in (None, "relu", "relu6"):
+            raise ValueError("%s: batch_norm is built with RELU, RELU_6 or NONE activations" % field)
+        ps, c = layer.ps, layer.cout
+        self.ps, self.scope, self.w, self.trainable = ps, layer.scope, layer.w, layer.trainable
+        self.w_eff_shape = (1, 1, layer.cin, c) if layer.fc else layer.w.shape
+        if self.bn_trainable and not self.batch_stats and (not self.center or c % 4 != 0):
+            # the gradients of a folded normaliser's gamma / beta come from ops.bn_param_grads (channel quads, y - beta)
+            raise ValueError("%s: train: false while training is built for center: true and a layer width that is a "
+                             "multiple of 4 (%s has %d)" % (field, layer.scope, c))
+        bn, t = layer.scope + "/BatchNorm/", self.bn_trainable
+        if self.center:
+            self.beta = ps.add(bn + "beta", (c,), ("zeros",), t)
+        if self.with_scale:
+            self.gamma = ps.add(bn + "gamma", (c,), ("const", 1.0), t)
+        self.mean = ps.add(bn + "moving_mean", (c,), ("zeros",), False)
+        self.var = ps.add(bn + "moving_variance", (c,), ("const", 1.0), False)
+        return self
+
+    def param_vars(self):
+        return tuple(v for v in (self.gamma, self.beta) if v is not None and self.bn_trainable)
+
+    def prepare(self):
+        if not self.batch_stats:
+            super().prepare()
+
+    def refold(self):
+        if not self.batch_stats:
+            super().refold()
+
+    def _values(self, *specs):
+        return tuple(None if s is None else self.ps.value(s.name) for s in specs)
+
+    def forward(self, z, act, update, keep):
+        """Batch-statistics mode. z: the filter's bias-free output [..., C]. keep: a dict that receives what backward
+        reads, or None. update: move the moving averages (the training step's forward only)."""
+        gamma, beta = self._values(self.gamma, self.beta)
+        mm, mv = self._values(self.mean, self.var) if update else (None, None)
+        y, mean, inv_std = ops.batch_norm_train_fwd(z, gamma, beta, self.eps, act_epilogue(act), mm, mv, self.f)
+        if keep is not None:
+            keep.update(z=z, mean=mean, inv_std=inv_std)
+        return y
+
+    def backward(self, keep, y, g, act):
+        """Batch-statistics mode. g = dL/dy (the activation's mask is applied inside, from y) -> dL/dz; accumulates and
+        reports the gradients of gamma / beta."""
+        ps = self.ps
+        mask = {None: 0, "relu": ops.EPI_MASK, "relu6": ops.EPI_MASK6}[act]
+        dg, db = (None if s is None else ps.grad(s.name) for s in (self.gamma, self.beta))
+        dz = ops.batch_norm_train_bwd(keep["z"], g.view(keep["z"].shape), self._values(self.gamma)[0], keep["mean"],
+                                      keep["inv_std"], dg, db, y=y.view(keep["z"].shape) if mask else None,
+                                      mask_epilogue=mask, accum=1.0)
+        ps.grad_ready(self.gamma, self.beta)
+        return dz.view(g.shape)
+
+    def frozen_param_grads(self, y, gp):
+        """Frozen mode while training (train: false): gamma / beta gradients of the folded normaliser from the layer's
+        output y and gp = dL/d(pre-activation)."""
+        if self.batch_stats or not self.bn_trainable:
+            return
+        ps, c = self.ps, y.shape[-1]
+        db = ps.grad(self.beta.name)
+        if self.gamma is not None:
+            gamma, dg = ps.value(self.gamma.name), ps.grad(self.gamma.name)
+        else:
+            gamma, dg = torch.ones_like(db), torch.zeros_like(db)
+        ops.bn_param_grads(y.view(-1, c), gp.view(-1, c), gamma, ps.value(self.beta.name), dg, db, beta=1.0)
+        ps.grad_ready(self.gamma, self.beta)
+
+
+def _of_folded_norm(name):
+    """A Layer attribute of the folded normaliser, read from the layer's `norm` while that runs on the moving
+    statistics (the batched refresh and fold of the model read them off the layer); the Layer default otherwise."""
+    def get(self):
+        n = self.norm
+        return getattr(n, name) if (n is not None and not n.batch_stats) else getattr(Layer, name, None)
+    return property(get)
+
+
 class Conv(Layer):
-    """slim.conv2d / slim.fully_connected with biases, no normaliser (RPN conv, predictors)."""
+    """slim.conv2d / slim.fully_connected of the heads (RPN conv, predictors, refiner): with biases and no normaliser, or
+    — batch_norm given: the nn.BatchNorm of a hyperparams block — the filter without bias followed by that normaliser
+    and the activation. A layer without one runs exactly the code it ran before normalisers existed."""
+    gamma, beta, mean, inv_std, scale, shift, w_eff, bn_trainable = (
+        _of_folded_norm(k) for k in ("gamma", "beta", "mean", "inv_std", "scale", "shift", "w_eff", "bn_trainable"))
 
     def __init__(self, ps, scope, cin, cout, k, init, trainable=True, weight_decay=0.0,
-                 activation=None, fc=False, rate=1):
+                 activation=None, fc=False, rate=1, batch_norm=None):
         super().__init__()
         self.ps, self.scope, self.k, self.trainable, self.activation = ps, scope, k, trainable, activation
         self.rate = rate
         shape = (cin, cout) if fc else (k, k, cin, cout)
         self.fc = fc
         self.w = ps.add(scope + "/weights", shape, init, trainable, weight_decay)
-        self.b = ps.add(scope + "/biases", (cout,), ("zeros",), trainable)
         self.cin, self.cout = cin, cout
+        self.b = self.norm = None
+        if batch_norm is None:
+            self.b = ps.add(scope + "/biases", (cout,), ("zeros",), trainable)
+        else:
+            self.norm = batch_norm.bind(self)
+
+    @property
+    def batch_stats(self):
+        """The layer normalises with batch statistics: forward takes `keep` / `update`, and norm_backward applies the
+        activation's mask itself (the caller passes dL/d(output), unmasked)."""
+        return self.norm is not None and self.norm.batch_stats
+
+    def grad_vars(self):
+        return super().grad_vars() + (self.norm.param_vars() if self.batch_stats else ())
+
+    def prepare(self):
+        if self.norm is not None:
+            self.norm.prepare()
+
+    def refold(self):
+        if self.norm is not None:
+            self.norm.refold()
 
     def _w4(self):
         w = self.ps.value(self.w.name)
@@ -264,28 +396,49 @@ class Conv(Layer):
     def geometry(self):
         return (self.k, self.k, self.cin, self.cout), 1, self.rate, "SAME"
 
-    def forward(self, x):
-        """x: NHWC, or [rows, cin] for fc=True (treated as rows x 1 x 1 x cin)."""
+    def forward(self, x, keep=None, update=False):
+        """x: NHWC, or [rows, cin] for fc=True (treated as rows x 1 x 1 x cin). keep / update: BatchNorm.forward's, for
+        a layer that normalises with batch statistics."""
         x4 = x.view(x.shape[0], 1, 1, self.cin) if self.fc else x
-        epi = ops.EPI_BIAS | act_epilogue(self.activation)
-        y = ops.conv2d_fwd(self.desc(x4.shape), x4, self._w4(), self.ps.value(self.b.name), None, epi,
-                           xf_cache=self.ps.filter_cache)
+        n, act = self.norm, act_epilogue(self.activation)
+        if n is None:
+            y = ops.conv2d_fwd(self.desc(x4.shape), x4, self._w4(), self.ps.value(self.b.name), None,
+                               ops.EPI_BIAS | act, xf_cache=self.ps.filter_cache)
+        elif n.batch_stats:
+            z = ops.conv2d_fwd(self.desc(x4.shape), x4, self._w4(), None, None, 0, xf_cache=self.ps.filter_cache)
+            y = n.forward(z, self.activation, update, keep)
+        else:
+            y = ops.conv2d_fwd(self.desc(x4.shape), x4, n.w_eff, n.shift, None, ops.EPI_BIAS | act,
+                               xf_cache=self.ps.filter_cache)
         return y.view(x.shape[0], self.cout) if self.fc else y
+
+    def norm_backward(self, keep, y, g):
+        """The normaliser's backward, before wgrad / dgrad, for a layer that has one -> dL/d(filter output).
+        Batch statistics: g = dL/dy, the activation's mask is applied inside. Frozen: g = dL/d(pre-activation), masked by
+        the caller as for a layer without normaliser, and comes back unchanged. Either way gamma / beta get their
+        gradients."""
+        if self.norm.batch_stats:
+            return self.norm.backward(keep, y, g, self.activation)
+        self.norm.frozen_param_grads(y, g)
+        return g
 
     def wgrad(self, x, g):
         if not self.trainable:
             return
         x4 = x.view(x.shape[0], 1, 1, self.cin) if self.fc else x
         g4 = g.view(g.shape[0], 1, 1, self.cout) if self.fc else g
-        gw = self.ps.grad(self.w.name)
-        ops.conv2d_wgrad(self.desc(x4.shape), x4, g4, gw.view(self.k, self.k, self.cin, self.cout),
-                         dbias=self.ps.grad(self.b.name), beta=1.0)
+        gw = self.ps.grad(self.w.name).view(self.k, self.k, self.cin, self.cout)
+        if self.norm is None:
+            ops.conv2d_wgrad(self.desc(x4.shape), x4, g4, gw, dbias=self.ps.grad(self.b.name), beta=1.0)
+        else:         # no bias; a folded normaliser's scale reaches the filter gradient
+            ops.conv2d_wgrad(self.desc(x4.shape), x4, g4, gw, out_scale=self.scale, beta=1.0)
         self.ps.grad_ready(self.w, self.b)
 
     def dgrad(self, x_shape, g, residual=None, mask_ref=None, out=None, accum=False, mask6=False):
         x4s = (x_shape[0], 1, 1, self.cin) if self.fc else tuple(x_shape)
         g4 = g.view(g.shape[0], 1, 1, self.cout) if self.fc else g
-        dx = ops.conv2d_dgrad(self.desc(x4s), g4, self._w4(), residual, mask_ref,
+        w = self.w_eff if self.w_eff is not None else self._w4()
+        dx = ops.conv2d_dgrad(self.desc(x4s), g4, w, residual, mask_ref,
                               dgrad_epilogue(residual, accum, mask_ref, mask6), out=out, xf_cache=self.ps.filter_cache)
         return dx.view(x_shape) if self.fc else dx
 
@@ -307,38 +460,44 @@ class FCStack:
     (core/box_predictor.py:479-488, 585-594). Explicit forward / backward over nn.Conv(fc=True)."""
 
     def __init__(self, ps, scopes, cin, widths, init, trainable, weight_decay, activation="relu", keep_prob=None,
-                 slot0=0):
+                 slot0=0, batch_norm=None):
+        """batch_norm: None, or a callable that makes the nn.BatchNorm of one layer (filter, normaliser, activation,
+        dropout)."""
         if activation not in ("relu", None):
             raise ValueError("fully connected stacks support RELU or NONE activations, got %r" % (activation,))
         self.layers, self.activation = [], activation
         for scope, cout in zip(scopes, widths):
-            self.layers.append(Conv(ps, scope, cin, cout, 1, init, trainable, weight_decay, activation=activation, fc=True))
+            self.layers.append(Conv(ps, scope, cin, cout, 1, init, trainable, weight_decay, activation=activation, fc=True,
+                                    batch_norm=batch_norm() if batch_norm is not None else None))
             cin = cout
         self.cout = cin
         self.keep_prob = None if (keep_prob is None or keep_prob >= 1.0) else float(keep_prob)
         self.slot0 = slot0
 
-    def forward(self, x, training, seed, step):
-        """-> (output, ctx). Dropout acts only while training (slim.dropout's is_training)."""
+    def forward(self, x, training, seed, step, update=False):
+        """-> (output, ctx). Dropout acts only while training (slim.dropout's is_training). update: BatchNorm.forward's."""
         ctx = []
         for i, l in enumerate(self.layers):
-            a = l.forward(x)
+            keep = {} if l.batch_stats else None
+            a = l.forward(x, keep, update) if l.batch_stats else l.forward(x)
             drop = training and self.keep_prob is not None
             dseed = (int(seed) ^ DROPOUT_SEED_SALT) & 0xFFFFFFFF
             y = ops.dropout(a, self.keep_prob, dseed, dropout_stream(step, self.slot0 + i)) if drop else a
-            ctx.append((x, a, (dseed, dropout_stream(step, self.slot0 + i)) if drop else None))
+            ctx.append((x, a, (dseed, dropout_stream(step, self.slot0 + i)) if drop else None, keep))
             x = y
         return x, ctx
 
     def backward(self, ctx, g, need_input_grad=True):
-        """g: dL/d(output). Accumulates the layers' filter / bias gradients; returns dL/d(input) or None."""
+        """g: dL/d(output). Accumulates the layers' filter / bias / normaliser gradients; returns dL/d(input) or None."""
         for i in range(len(self.layers) - 1, -1, -1):
             l = self.layers[i]
-            x, a, drop = ctx[i]
+            x, a, drop, keep = ctx[i]
             if drop is not None:
                 g = ops.dropout(g, self.keep_prob, drop[0], drop[1])
-            if self.activation == "relu":
+            if self.activation == "relu" and not l.batch_stats:
                 g = ops.relu_bwd(a, g)
+            if l.norm is not None:
+                g = l.norm_backward(keep, a, g)
             l.wgrad(x, g)
             if i == 0 and not need_input_grad:
                 return None

@@ -849,6 +849,45 @@ def bn_param_grads(y, g, gamma, beta_param, dgamma, dbeta, beta=0.0):
     return dgamma, dbeta
 
 
+def moving_average_factor(decay):
+    """f of assign_moving_average (python/training/moving_averages.py: decay = 1 - decay in the variable's dtype):
+    float32(1.0 - float64(float32(decay)))."""
+    return float(np.float32(1.0 - float(np.float32(decay))))
+
+
+def batch_norm_train_fwd(x, gamma, beta, eps, epilogue=0, moving_mean=None, moving_var=None, f=0.0, y=None,
+                         save_mean=None, save_inv_std=None):
+    """slim.batch_norm in training mode over the rows of x [..., C] (mtlssl_batch_norm_train_fwd) -> (y, save_mean,
+    save_inv_std). gamma / beta: [C] or None. moving_mean / moving_var: updated in place with the factor `f`
+    (moving_average_factor(decay)) when given. epilogue: 0 | EPI_RELU | EPI_RELU6."""
+    C = int(x.shape[-1])
+    y = torch.empty_like(x) if y is None else y
+    save_mean = torch.empty((C,), dtype=f32, device=x.device) if save_mean is None else save_mean
+    save_inv_std = torch.empty((C,), dtype=f32, device=x.device) if save_inv_std is None else save_inv_std
+    for t in (gamma, beta, moving_mean, moving_var):
+        assert t is None or (_chk(t).numel() == C), (None if t is None else tuple(t.shape), C)
+    assert _chk(save_mean).numel() == C and _chk(save_inv_std).numel() == C and _chk(y).shape == x.shape
+    lib().batch_norm_train_fwd(ptr(_chk(x)), ptr(gamma), ptr(beta), ptr(y), ptr(save_mean), ptr(save_inv_std),
+                               ptr(moving_mean), ptr(moving_var), x.numel() // C, C, float(eps), float(f),
+                               int(epilogue), _stream())
+    return y, save_mean, save_inv_std
+
+
+def batch_norm_train_bwd(x, dy, gamma, save_mean, save_inv_std, dgamma, dbeta, y=None, mask_epilogue=0, accum=0.0,
+                         dx=None):
+    """Gradient of batch_norm_train_fwd (mtlssl_batch_norm_train_bwd) -> dx. mask_epilogue EPI_MASK / EPI_MASK6 applies
+    the ReLU / ReLU6 mask of the forward's output `y` to dy inside. dgamma / dbeta: [C] outputs or None; accum != 0
+    accumulates into them."""
+    C = int(x.shape[-1])
+    dx = torch.empty_like(x) if dx is None else dx
+    for t in (gamma, save_mean, save_inv_std, dgamma, dbeta):
+        assert t is None or (_chk(t).numel() == C), (None if t is None else tuple(t.shape), C)
+    assert _chk(dy).shape == x.shape and _chk(dx).shape == x.shape and (y is None or _chk(y).shape == x.shape)
+    lib().batch_norm_train_bwd(ptr(_chk(x)), ptr(dy), ptr(y), ptr(gamma), ptr(save_mean), ptr(save_inv_std), ptr(dx),
+                               ptr(dgamma), ptr(dbeta), x.numel() // C, C, float(accum), int(mask_epilogue), _stream())
+    return dx
+
+
 def pool_geometry(H, W, k, stride, padding):
     """-> (pad_t, pad_l, OH, OW) of a k x k / stride pooling window under TF 'SAME' / 'VALID'."""
     if padding == "SAME":

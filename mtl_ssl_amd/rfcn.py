@@ -95,7 +95,8 @@ class RFCNMetaArch(FasterRCNNMetaArch):
             self.window_tower = self._feature_extractor.box_classifier_tower(self.window_box_predictor_scope, True)
             self.layers += self.window_tower.layers()
 
-    def _make_predictor(self, scope, num_classes, bp_cfg, class_only, slot0=0):
+    def _make_predictor(self, scope, num_classes, bp_cfg, class_only, slot0=0, no_batch_norm=None):
+        """no_batch_norm: unused — RfcnBoxPredictor refuses batch_norm for every head."""
         if not bp_cfg.has("rfcn_box_predictor"):
             raise ValueError("RFCNMetaArch needs rfcn_box_predictor for %s" % scope)
         return RfcnBoxPredictor(self.ps, scope, self.tower.cout, num_classes, bp_cfg.rfcn_box_predictor,
