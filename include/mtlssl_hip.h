@@ -64,6 +64,9 @@ typedef struct {
                               * ldy % 4 == 0 and a 16-byte aligned pointer are required; residual / mask / dx stay dense. */
 } mtlssl_conv_desc;
 
+/* Epilogue flags. Whatever the flags' values, they are applied in one order (mtl_ssl_amd/csrc/epilogue.h) — forward:
+ * + bias, + residual, then one of ReLU / ReLU6 / tanh; input gradient: + residual, + previous contents (ACCUM), then
+ * the ReLU or ReLU6 mask. */
 #define MTLSSL_EPI_BIAS 1      /* + bias[k] (folded BN shift or conv bias)                  */
 #define MTLSSL_EPI_RESIDUAL 2  /* + residual[n,oh,ow,k]                                     */
 #define MTLSSL_EPI_RELU 4      /* max(.,0)                                                  */

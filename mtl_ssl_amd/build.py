@@ -37,8 +37,8 @@ SOURCES = {
 
 def _digest(path, flags):
     h = hashlib.sha256()
-    for f in (path, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_mfma.h"), os.path.join(CSRC, "conv_split.h"), os.path.join(CSRC, "portable_math.h"),
-              os.path.join(HERE, "..", "include", "mtlssl_hip.h")):
+    headers = sorted(os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith(".h"))      # every header there is
+    for f in [path] + headers + [os.path.join(HERE, "..", "include", "mtlssl_hip.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join(flags).encode())

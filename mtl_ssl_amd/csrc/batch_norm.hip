@@ -16,6 +16,7 @@
 // A channel past C (the ragged last slab) and a row past `rows` are never read or written: their threads only take part
 // in the barriers.
 #include "common.h"
+#include "epilogue.h"
 
 namespace mtlssl {
 
@@ -39,11 +40,7 @@ __device__ __forceinline__ float bn_block_sum(float a0, float a1, float a2, floa
   return total;
 }
 
-__device__ __forceinline__ float bn_act(float v, int epi) {
-  if (epi & MTLSSL_EPI_RELU) v = fmaxf(v, 0.f);
-  if (epi & MTLSSL_EPI_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-  return v;
-}
+constexpr int BN_ACTS = MTLSSL_EPI_RELU | MTLSSL_EPI_RELU6;   // what mtlssl_batch_norm_train_fwd admits
 
 __global__ void __launch_bounds__(BN_THREADS)
     k_batch_norm_train_fwd(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -106,7 +103,7 @@ __global__ void __launch_bounds__(BN_THREADS)
         float v = (xc[r * C] - mean) * inv_std;
         if (gamma != nullptr) v = v * gm;
         if (beta != nullptr) v = v + bt;
-        yc[r * C] = bn_act(v, epi);
+        yc[r * C] = act_fwd<BN_ACTS>(v, epi);
       }
     }
   }
@@ -130,11 +127,7 @@ __global__ void __launch_bounds__(BN_THREADS)
 
   auto masked = [&](int64_t i) {
     float g = gc[i];
-    if (mask) {
-      const float yv = yc[i];
-      const bool on = yv > 0.f && (!(mask & MTLSSL_EPI_MASK6) || yv < 6.f);
-      g = on ? g : 0.f;
-    }
+    if (mask) g = act_mask(g, yc[i], mask);
     return g;
   };
 

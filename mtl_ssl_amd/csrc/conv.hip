@@ -11,7 +11,8 @@
 // conflict-free ds_read_b32 per operand (lane l reads [2*kk + l/32][tile + l%32]); the next
 // K-step's global loads are issued before the current step's MFMAs (register prefetch, double
 // buffered LDS, one barrier per step). Frozen BatchNorm is folded into the weights by the caller,
-// so the epilogue is bias(+residual)(+ReLU) and the backward needs only ReLU masks.
+// so the epilogue is bias(+residual)(+activation) and the backward needs only activation masks: the
+// two chains of epilogue.h, which every kernel here that ends a convolution calls.
 #include <stdlib.h>
 
 #include <atomic>
@@ -149,12 +150,7 @@ __global__ void k_conv_direct_fwd(ConvArgs p) {
       for (int c = 0; c < p.C; ++c) acc = fmaf(xp[c], wp[(int64_t)c * p.K], acc);
     }
   }
-  if (p.epi & MTLSSL_EPI_BIAS) acc += p.bias[k];
-  if (p.epi & MTLSSL_EPI_RESIDUAL) acc += p.residual[i];
-  if (p.epi & MTLSSL_EPI_RELU) acc = fmaxf(acc, 0.f);
-  if (p.epi & MTLSSL_EPI_RELU6) acc = fminf(fmaxf(acc, 0.f), 6.f);
-  if (p.epi & MTLSSL_EPI_TANH) acc = tanhf(acc);
-  p.out[i] = acc;
+  p.out[i] = epilogue_fwd(acc, p.epi, EPI_OPERAND(p.bias[k]), EPI_OPERAND(p.residual[i]));
 }
 __global__ void k_conv_direct_dgrad(ConvArgs p) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -179,10 +175,7 @@ __global__ void k_conv_direct_dgrad(ConvArgs p) {
       for (int k = 0; k < p.K; ++k) acc = fmaf(gp[k], wp[k], acc);
     }
   }
-  if (p.epi & MTLSSL_EPI_RESIDUAL) acc += p.residual[i];
-  if (p.epi & MTLSSL_EPI_ACCUM) acc += p.out[i];
-  if (p.epi & MASK_ANY) acc = act_mask(acc, p.mask[i], p.epi);
-  p.out[i] = acc;
+  p.out[i] = epilogue_dgrad(acc, p.epi, EPI_OPERAND(p.residual[i]), EPI_OPERAND(p.out[i]), EPI_OPERAND(p.mask[i]));
 }
 // wgrad for small layers: one block per (rs, c), threads over k, pixels reduced serially.
 __global__ void k_conv_direct_wgrad(ConvArgs p, const float* scale, float* dw, float beta) {
@@ -337,15 +330,9 @@ __global__ void __launch_bounds__(256) k_gemm_small(GemmArgs p) {
       int64_t o = (int64_t)m * p.N + n;
       float v = acc[i][j];
       if constexpr (MODE == GM_FWD) {
-        if (p.epi & MTLSSL_EPI_BIAS) v += p.bias[n];
-        if (p.epi & MTLSSL_EPI_RESIDUAL) v += p.residual[o];
-        if (p.epi & MTLSSL_EPI_RELU) v = fmaxf(v, 0.f);
-        if (p.epi & MTLSSL_EPI_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-        if (p.epi & MTLSSL_EPI_TANH) v = tanhf(v);
+        v = epilogue_fwd(v, p.epi, EPI_OPERAND(p.bias[n]), EPI_OPERAND(p.residual[o]));
       } else if constexpr (MODE == GM_DGRAD) {
-        if (p.epi & MTLSSL_EPI_RESIDUAL) v += p.residual[o];
-        if (p.epi & MTLSSL_EPI_ACCUM) v += outp[o];
-        if (p.epi & MASK_ANY) v = act_mask(v, p.mask[o], p.epi);
+        v = epilogue_dgrad(v, p.epi, EPI_OPERAND(p.residual[o]), EPI_OPERAND(outp[o]), EPI_OPERAND(p.mask[o]));
       }
       outp[o] = v;
     }
@@ -427,6 +414,7 @@ static ColsumPlan colsum_plan(int64_t P, int K) {
 // input patch of a 16x16 output tile live in LDS; each thread owns 2x2 pixels x 16 channels.
 // fp32 VALU (K_gemm = 147 is too ragged for the 16-wide MFMA K-step; ~23 GFLOP per step).
 constexpr int STEM_T = 16;
+constexpr int STEM_FWD_FLAGS = MTLSSL_EPI_BIAS | MTLSSL_EPI_RELU;   // a call with any other flag takes the scalar kernel (stem_fwd_family)
 __global__ void __launch_bounds__(256) k_conv_smallc_fwd(ConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int RSC = p.R * p.S * p.C;
@@ -470,10 +458,7 @@ __global__ void __launch_bounds__(256) k_conv_smallc_fwd(ConvArgs p) {
     float* op = p.out + (((int64_t)n * p.OH + oy) * p.OW + ox) * 64 + cq * 16;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-      float v = acc[q][j];
-      if (p.epi & MTLSSL_EPI_BIAS) v += p.bias[cq * 16 + j];
-      if (p.epi & MTLSSL_EPI_RELU) v = fmaxf(v, 0.f);
-      op[j] = v;
+      op[j] = epilogue_fwd<STEM_FWD_FLAGS>(acc[q][j], p.epi, EPI_OPERAND(p.bias[cq * 16 + j]), EPI_OPERAND(0.f));
     }
   }
 }
@@ -546,25 +531,14 @@ __global__ void k_splitk_epilogue(ConvArgs p) {
   for (int z = 1; z < p.nsplit; ++z) v += reinterpret_cast<const floatx4*>(p.splitk_ws)[(int64_t)z * total4 + i4];
   int64_t o = i4 * 4;
   int col = (int)(o % p.NG);
+  auto res = EPI_OPERAND(*reinterpret_cast<const floatx4*>(p.residual + o));
   if constexpr (MODE == MODE_FWD) {
-    if (p.epi & MTLSSL_EPI_BIAS) v += *reinterpret_cast<const floatx4*>(p.bias + col);
-    if (p.epi & MTLSSL_EPI_RESIDUAL) v += *reinterpret_cast<const floatx4*>(p.residual + o);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (p.epi & MTLSSL_EPI_RELU) v[e] = fmaxf(v[e], 0.f);
-      if (p.epi & MTLSSL_EPI_RELU6) v[e] = fminf(fmaxf(v[e], 0.f), 6.f);
-      if (p.epi & MTLSSL_EPI_TANH) v[e] = tanhf(v[e]);
-    }
+    v = epilogue_fwd(v, p.epi, EPI_OPERAND(*reinterpret_cast<const floatx4*>(p.bias + col)), res);
     const int ldy = args_ldy(p);
     if (ldy != p.NG) o = (o / p.NG) * ldy + col;       // y is a channel slice of a wider map
   } else {
-    if (p.epi & MTLSSL_EPI_RESIDUAL) v += *reinterpret_cast<const floatx4*>(p.residual + o);
-    if (p.epi & MTLSSL_EPI_ACCUM) v += *reinterpret_cast<const floatx4*>(p.out + o);
-    if (p.epi & MASK_ANY) {
-      floatx4 m = *reinterpret_cast<const floatx4*>(p.mask + o);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = act_mask(v[e], m[e], p.epi);
-    }
+    v = epilogue_dgrad(v, p.epi, res, EPI_OPERAND(*reinterpret_cast<const floatx4*>(p.out + o)),
+                       EPI_OPERAND(*reinterpret_cast<const floatx4*>(p.mask + o)));
   }
   *reinterpret_cast<floatx4*>(p.out + o) = v;
 }
@@ -580,17 +554,11 @@ __global__ void k_splitk_epilogue_scalar(ConvArgs p) {
   for (int z = 1; z < p.nsplit; ++z) v += p.splitk_ws[(int64_t)z * total + i];
   int col = (int)(i % p.NG);
   if constexpr (MODE == MODE_FWD) {
-    if (p.epi & MTLSSL_EPI_BIAS) v += p.bias[col];
-    if (p.epi & MTLSSL_EPI_RESIDUAL) v += p.residual[i];
-    if (p.epi & MTLSSL_EPI_RELU) v = fmaxf(v, 0.f);
-    if (p.epi & MTLSSL_EPI_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-    if (p.epi & MTLSSL_EPI_TANH) v = tanhf(v);
+    v = epilogue_fwd(v, p.epi, EPI_OPERAND(p.bias[col]), EPI_OPERAND(p.residual[i]));
     p.out[(i / p.NG) * args_ldy(p) + col] = v;
     return;
   } else {
-    if (p.epi & MTLSSL_EPI_RESIDUAL) v += p.residual[i];
-    if (p.epi & MTLSSL_EPI_ACCUM) v += p.out[i];
-    if (p.epi & MASK_ANY) v = act_mask(v, p.mask[i], p.epi);
+    v = epilogue_dgrad(v, p.epi, EPI_OPERAND(p.residual[i]), EPI_OPERAND(p.out[i]), EPI_OPERAND(p.mask[i]));
   }
   p.out[i] = v;
 }
@@ -801,12 +769,7 @@ __global__ void __launch_bounds__(256) k_pw_thin_fwd(const float* __restrict__ x
 #pragma unroll
     for (int k = 1; k < 8; ++k) v = lane == k ? acc[k] : v;
     const int64_t o = (int64_t)m * K + lane;
-    if (epi & MTLSSL_EPI_BIAS) v += bias[lane];
-    if (epi & MTLSSL_EPI_RESIDUAL) v += residual[o];
-    if (epi & MTLSSL_EPI_RELU) v = fmaxf(v, 0.f);
-    if (epi & MTLSSL_EPI_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-    if (epi & MTLSSL_EPI_TANH) v = tanhf(v);
-    y[o] = v;
+    y[o] = epilogue_fwd(v, epi, EPI_OPERAND(bias[lane]), EPI_OPERAND(residual[o]));
   }
 }
 static bool thin_fwd_ok(const mtlssl_conv_desc* d) {
@@ -1132,14 +1095,9 @@ __global__ void k_parity_scatter(const float* tmp, float* dx, const float* resid
   int u = (int)(t % Hs), n = (int)(t / Hs);
   floatx4 val = tmp ? reinterpret_cast<const floatx4*>(tmp)[i] : floatx4{0.f, 0.f, 0.f, 0.f};
   const int64_t o = ((((int64_t)n * H + 2 * u + py) * W + 2 * v + px) * C4 + c4);
-  if (epi & MTLSSL_EPI_RESIDUAL) val += reinterpret_cast<const floatx4*>(residual)[o];
-  if (epi & MTLSSL_EPI_ACCUM) val += reinterpret_cast<const floatx4*>(dx)[o];
-  if (epi & MASK_ANY) {
-    floatx4 mk = reinterpret_cast<const floatx4*>(mask)[o];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) val[e] = act_mask(val[e], mk[e], epi);
-  }
-  reinterpret_cast<floatx4*>(dx)[o] = val;
+  reinterpret_cast<floatx4*>(dx)[o] =
+      epilogue_dgrad(val, epi, EPI_OPERAND(reinterpret_cast<const floatx4*>(residual)[o]), EPI_OPERAND(reinterpret_cast<const floatx4*>(dx)[o]),
+                     EPI_OPERAND(reinterpret_cast<const floatx4*>(mask)[o]));
 }
 
 // ------------------------------------------------------------------------------ the plan resolver
@@ -1181,7 +1139,7 @@ static bool wgrad_on_split_engine(const Route& r, const mtlssl_conv_desc* d) {
   return fp32_engine() >= 1 && (r.wg.cfg == 0 || r.wg.cfg == 3) && desc_dense(d) && r.split_ns > 0;
 }
 // the small-C stem kernel has no residual / ReLU6 / tanh epilogue: those calls take the scalar kernel
-static inline int stem_fwd_family(int epi) { return (epi & ~(MTLSSL_EPI_BIAS | MTLSSL_EPI_RELU)) ? FAM_SCALAR : FAM_STEM_FWD; }
+static inline int stem_fwd_family(int epi) { return (epi & ~STEM_FWD_FLAGS) ? FAM_SCALAR : FAM_STEM_FWD; }
 
 static void resolve_wgrad(const mtlssl_conv_desc* d, Route* r) {
   const int64_t P = (int64_t)d->N * d->OH * d->OW;

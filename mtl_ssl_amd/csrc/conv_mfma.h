@@ -5,19 +5,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "epilogue.h"
 
 namespace mtlssl {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
-// ReLU / ReLU6 backward: pass the gradient where the activation was in its linear range.
-__device__ __forceinline__ float act_mask(float g, float y, int epi) {
-  bool on = y > 0.f && (!(epi & MTLSSL_EPI_MASK6) || y < 6.f);
-  return on ? g : 0.f;
-}
-constexpr int MASK_ANY = MTLSSL_EPI_MASK | MTLSSL_EPI_MASK6;
 constexpr int BK = 16;
 // Ablation switches of tools/lab/gemm_lab.hip (0 in the product build): 1 no global loads, 2 no LDS
 // stores, 4 no barrier, 8 no LDS fragment reads, 16 no epilogue stores.
@@ -164,23 +158,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, floatx16 (&acc)
           }
           const int64_t o = (int64_t)row * ldo + col;
           const int64_t of = MODE == MODE_FWD ? (int64_t)row * ldf + col : o;
+          auto res = EPI_OPERAND(PREFETCH_RES ? res_cur[k] : *reinterpret_cast<const floatx4*>(p.residual + o));
           if constexpr (MODE == MODE_FWD) {
-            v += bv;
-            if (p.epi & MTLSSL_EPI_RESIDUAL) v += PREFETCH_RES ? res_cur[k] : *reinterpret_cast<const floatx4*>(p.residual + o);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              if (p.epi & MTLSSL_EPI_RELU) v[q] = fmaxf(v[q], 0.f);
-              if (p.epi & MTLSSL_EPI_RELU6) v[q] = fminf(fmaxf(v[q], 0.f), 6.f);
-              if (p.epi & MTLSSL_EPI_TANH) v[q] = tanhf(v[q]);
-            }
+            // bv was loaded per column above and is zero without BIAS: it is added whatever the flag says
+            v = epilogue_fwd(v, p.epi | MTLSSL_EPI_BIAS, EPI_OPERAND(bv), res);
           } else if constexpr (MODE == MODE_DGRAD) {
-            if (p.epi & MTLSSL_EPI_RESIDUAL) v += PREFETCH_RES ? res_cur[k] : *reinterpret_cast<const floatx4*>(p.residual + o);
-            if (p.epi & MTLSSL_EPI_ACCUM) v += *reinterpret_cast<const floatx4*>(outp + o);
-            if (p.epi & MASK_ANY) {
-              floatx4 mk = *reinterpret_cast<const floatx4*>(p.mask + o);
-#pragma unroll
-              for (int q = 0; q < 4; ++q) v[q] = act_mask(v[q], mk[q], p.epi);
-            }
+            v = epilogue_dgrad(v, p.epi, res, EPI_OPERAND(*reinterpret_cast<const floatx4*>(outp + o)),
+                               EPI_OPERAND(*reinterpret_cast<const floatx4*>(p.mask + o)));
           }
           *reinterpret_cast<floatx4*>(outp + of) = v;
         }
@@ -213,15 +197,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, floatx16 (&acc)
           continue;
         }
         if constexpr (MODE == MODE_FWD) {
-          v += bv;
-          if (p.epi & MTLSSL_EPI_RESIDUAL) v += p.residual[o];
-          if (p.epi & MTLSSL_EPI_RELU) v = fmaxf(v, 0.f);
-          if (p.epi & MTLSSL_EPI_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-          if (p.epi & MTLSSL_EPI_TANH) v = tanhf(v);
+          v = epilogue_fwd(v, p.epi | MTLSSL_EPI_BIAS, EPI_OPERAND(bv), EPI_OPERAND(p.residual[o]));   // bv: as above
         } else if constexpr (MODE == MODE_DGRAD) {
-          if (p.epi & MTLSSL_EPI_RESIDUAL) v += p.residual[o];
-          if (p.epi & MTLSSL_EPI_ACCUM) v += outp[o];
-          if (p.epi & MASK_ANY) v = act_mask(v, p.mask[o], p.epi);
+          v = epilogue_dgrad(v, p.epi, EPI_OPERAND(p.residual[o]), EPI_OPERAND(outp[o]), EPI_OPERAND(p.mask[o]));
         }
         outp[of] = v;
       }

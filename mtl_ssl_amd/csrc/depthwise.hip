@@ -5,16 +5,17 @@
 // 64/C4 neighbouring pixels. Filter layout [R,S,C] (TF's [R,S,C,1]). Frozen BatchNorm is folded
 // into the filter by the caller (w_eff = w*scale[c]); the epilogue adds the shift and ReLU6.
 #include "common.h"
+#include "epilogue.h"
 
 namespace mtlssl {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct DwArgs {
   const float* x; const float* w; const float* bias; const float* g; const float* mask;
   float* out;
   int N, H, W, C, R, S, OH, OW, stride, dil, pt, pl, epi;
 };
+// what the forward applies: it has no residual operand and no tanh, and does not look at their flags
+constexpr int DW_FWD_FLAGS = MTLSSL_EPI_BIAS | MTLSSL_EPI_RELU | MTLSSL_EPI_RELU6;
 
 __global__ void k_dw_fwd(DwArgs p) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -38,13 +39,8 @@ __global__ void k_dw_fwd(DwArgs p) {
       acc += xv * wv;
     }
   }
-  if (p.epi & MTLSSL_EPI_BIAS) acc += *reinterpret_cast<const floatx4*>(p.bias + c4 * 4);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    if (p.epi & MTLSSL_EPI_RELU) acc[e] = fmaxf(acc[e], 0.f);
-    if (p.epi & MTLSSL_EPI_RELU6) acc[e] = fminf(fmaxf(acc[e], 0.f), 6.f);
-  }
-  reinterpret_cast<floatx4*>(p.out)[i] = acc;
+  reinterpret_cast<floatx4*>(p.out)[i] =
+      epilogue_fwd<DW_FWD_FLAGS>(acc, p.epi, EPI_OPERAND(*reinterpret_cast<const floatx4*>(p.bias + c4 * 4)), EPI_OPERAND(floatx4{}));
 }
 
 // dx[n,ih,iw,c] = sum_{r,s} g[n,(ih+pt-r*dl)/st,(iw+pl-s*dl)/st,c] * w[r,s,c]  (+ mask of the
@@ -75,14 +71,7 @@ __global__ void k_dw_dgrad(DwArgs p) {
       acc += gv * wv;
     }
   }
-  if (p.epi & (MTLSSL_EPI_MASK | MTLSSL_EPI_MASK6)) {
-    floatx4 m = reinterpret_cast<const floatx4*>(p.mask)[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      bool on = m[e] > 0.f && (!(p.epi & MTLSSL_EPI_MASK6) || m[e] < 6.f);
-      acc[e] = on ? acc[e] : 0.f;
-    }
-  }
+  if (p.epi & MASK_ANY) acc = act_mask(acc, reinterpret_cast<const floatx4*>(p.mask)[i], p.epi);
   reinterpret_cast<floatx4*>(p.out)[i] = acc;
 }
 
@@ -278,7 +267,7 @@ int mtlssl_depthwise_dgrad(const mtlssl_conv_desc* d, const float* dy, const flo
                            const float* mask_ref, float* dx, int epi, mtlssl_stream_t stream) {
   DwArgs a{};
   if (int rc = fill(a, d)) return rc;
-  MTLSSL_REQUIRE(!(epi & (MTLSSL_EPI_MASK | MTLSSL_EPI_MASK6)) || mask_ref, "depthwise_dgrad: mask_ref required");
+  MTLSSL_REQUIRE(!(epi & MASK_ANY) || mask_ref, "depthwise_dgrad: mask_ref required");
   a.g = dy; a.w = w; a.mask = mask_ref; a.out = dx; a.epi = epi;
   int64_t total = (int64_t)a.N * a.H * a.W * (a.C / 4);
   hipLaunchKernelGGL(k_dw_dgrad, dim3(cdiv(total, 256)), dim3(256), 0, S(stream), a);

@@ -139,23 +139,6 @@ __device__ __forceinline__ TileIdx tile_index(const WinoGeom& g, int C, const in
   r.n = (int)(q / g.th);
   return r;
 }
-__device__ __forceinline__ float act_fwd(float v, int epi) {
-  if (epi & MTLSSL_EPI_RELU) v = fmaxf(v, 0.f);
-  if (epi & MTLSSL_EPI_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-  if (epi & MTLSSL_EPI_TANH) v = tanhf(v);
-  return v;
-}
-__device__ __forceinline__ floatx4 act_fwd(floatx4 v, int epi) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) v[q] = act_fwd(v[q], epi);
-  return v;
-}
-__device__ __forceinline__ float mask_bwd(float g, float y, int epi) { return act_mask(g, y, epi); }
-__device__ __forceinline__ floatx4 mask_bwd(floatx4 g, floatx4 y, int epi) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) g[q] = act_mask(g[q], y[q], epi);
-  return g;
-}
 
 // Filter transform U[xi][c][k] = (G g G^T)[xi] of w[r][s][c][k]; flip = 1 takes g[2-r][2-s] (the
 // dgrad filter; its [C][K] layout is what the tile engine's dgrad mode reads as B[n][k]).
@@ -316,14 +299,13 @@ __global__ void __launch_bounds__(256) k_wino_output(const float* Mb, float* out
       const int64_t off = pix * K + ix.c;               // residual / mask / accumulate operands are dense
       const int64_t offo = pix * ldo + ix.c;            // ldo: row stride of `out` (forward: y may be a channel slice)
       VT v = o[v_];
+      auto res = EPI_OPERAND(*reinterpret_cast<const VT*>(residual + off));
       if constexpr (MODE == MODE_FWD) {
-        v += bv;
-        if (epi & MTLSSL_EPI_RESIDUAL) v += *reinterpret_cast<const VT*>(residual + off);
-        v = act_fwd(v, epi);
+        // bv was loaded once above and is zero without BIAS: it is added whatever the flag says
+        v = epilogue_fwd(v, epi | MTLSSL_EPI_BIAS, EPI_OPERAND(bv), res);
       } else {
-        if (epi & MTLSSL_EPI_RESIDUAL) v += *reinterpret_cast<const VT*>(residual + off);
-        if (epi & MTLSSL_EPI_ACCUM) v += *reinterpret_cast<const VT*>(out + offo);
-        if (epi & MASK_ANY) v = mask_bwd(v, *reinterpret_cast<const VT*>(mask + off), epi);
+        v = epilogue_dgrad(v, epi, res, EPI_OPERAND(*reinterpret_cast<const VT*>(out + offo)),
+                           EPI_OPERAND(*reinterpret_cast<const VT*>(mask + off)));
       }
       *reinterpret_cast<VT*>(out + offo) = v;
     }

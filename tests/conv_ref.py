@@ -16,7 +16,9 @@ Each returns (sum, sum |a*b|), the unit of tests/parity_report.py dot_err.
 
 On top of them: fwd_expected / dgrad_expected / wgrad_expected add the epilogue's addends (to the sum AND to the scale) and
 return (select, ref, mag) per compared output; ConvCase draws the operands of one problem the way every float64 plan test
-does and holds the assertions they share. tests/test_conv_ref.py checks all of it on a CPU.
+does and holds the assertions they share. apply_fwd_epilogue / apply_dgrad_epilogue are the epilogue flags' two chains in
+fp32 torch, what a flagged output must equal bit for bit given the unflagged one (csrc/epilogue.h states them for the
+kernels). tests/test_conv_ref.py checks all of it on a CPU.
 A plain module: no fixtures, not a conftest."""
 import os
 import zlib
@@ -394,6 +396,43 @@ def wgrad_expected(prob, x, dy, cs, ks, scale=None, beta=1.0, dw_old=None, db_ol
             (sel_b,) + _plus(dy_sub.sum((0, 1, 2)), dy_sub.abs().sum((0, 1, 2)), old(db_old, sel_b)))
 
 
+def apply_fwd_epilogue(lin, epi, bias=None, res=None):
+    """The forward epilogue (ops.EPI_* flags) on a linear result `lin`, in fp32 torch and in the library's order:
+    (lin + bias) + res under BIAS / RESIDUAL, then RELU as max(., 0), RELU6 as clamp(., 0, 6). TANH is the float64 tanh of
+    that fp32 pre-activation, returned in float64: the device tanhf is held to it in fp32 spacings (TANH_ULPS)."""
+    from mtl_ssl_amd import ops as O
+    v = lin
+    if epi & O.EPI_BIAS:
+        v = v + bias
+    if epi & O.EPI_RESIDUAL:
+        v = v + res
+    if epi & O.EPI_RELU:
+        v = torch.clamp_min(v, 0.0)
+    if epi & O.EPI_RELU6:
+        v = torch.clamp(v, 0.0, 6.0)
+    if epi & O.EPI_TANH:
+        v = torch.tanh(v.double())
+    return v
+
+
+def apply_dgrad_epilogue(lin, epi, resd=None, prev=None, mask_ref=None):
+    """The input-gradient epilogue on a linear result, in fp32 torch and in the library's order: (lin + resd) + prev
+    under RESIDUAL / ACCUM, then 0 wherever the activation that made `mask_ref` was not in its linear range: MASK
+    passes mask_ref > 0, MASK6 0 < mask_ref < 6."""
+    from mtl_ssl_amd import ops as O
+    v = lin
+    if epi & O.EPI_RESIDUAL:
+        v = v + resd
+    if epi & O.EPI_ACCUM:
+        v = v + prev
+    if epi & (O.EPI_MASK | O.EPI_MASK6):
+        on = mask_ref > 0
+        if epi & O.EPI_MASK6:
+            on = on & (mask_ref < 6)
+        v = torch.where(on, v, torch.zeros_like(v))
+    return v
+
+
 def _on(device, dtype, *ts):
     return [None if t is None else t.to(device=device, dtype=dtype) for t in ts]
 
@@ -645,8 +684,9 @@ class ConvCase:
 
     def check_exact_epilogue(self, mode, got, linear, *ctx):
         """The nonlinear epilogues are exact functions of the linear result (the split-K fold sums in a fixed order)."""
+        from mtl_ssl_amd import ops as O
         if mode == 0:
-            assert torch.equal(got, torch.relu(linear)), ("forward ReLU epilogue",) + ctx
+            assert torch.equal(got, apply_fwd_epilogue(linear, O.EPI_RELU)), ("forward ReLU epilogue",) + ctx
         if mode == 1:
-            assert torch.equal(got, torch.where(self.mask > 0, linear, torch.zeros_like(linear))), ("dgrad mask epilogue",) + ctx
+            assert torch.equal(got, apply_dgrad_epilogue(linear, O.EPI_MASK, mask_ref=self.mask)), ("dgrad mask epilogue",) + ctx
 

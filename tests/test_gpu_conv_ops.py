@@ -832,3 +832,250 @@ def test_bias_add_channels(ops, shape):
     b = torch.randn(shape[-1], generator=g) * 50
     y = ops.bias_add_channels(x.cuda(), b.cuda())
     assert torch.equal(y.cpu(), x + b)
+
+
+# ------------------------------------------------------------------------------------- the epilogue at every site
+# The MTLSSL_EPI_* flags mean two chains (csrc/epilogue.h; tests/conv_ref.py apply_fwd_epilogue / apply_dgrad_epilogue):
+# forward (+bias, +residual, one of ReLU / ReLU6 / tanh), input gradient (+residual, +previous contents, ReLU / ReLU6 mask).
+# Every kernel that ends a convolution applies them; each is run here with every legal flag set on the smallest problem a
+# host search over ops.conv_plan_info found for it (the planner's answer is asserted, so a case cannot pass on another
+# kernel). (id, modes, x shape, filter, stride, set_winograd mode, call without a workspace, what conv_plan_info must say
+# the call would do WITH a workspace, what runs).
+_B, _R, _RELU, _TANH, _RELU6, _MASK, _ACCUM, _MASK6 = 1, 2, 4, 8, 16, 32, 64, 128
+FWD_SETS = [b | r | a for b in (0, _B) for r in (0, _R) for a in (0, _RELU, _RELU6, _TANH)]
+DGRAD_SETS = [r | a | m for r in (0, _R) for a in (0, _ACCUM) for m in (0, _MASK, _MASK6)]
+EPI_SITES = [
+    ("tile-float4", (0, 1), (1, 9, 9, 64), (1, 1, 64, 64), 1, None, False, dict(family="direct", split=False, ng4=True), "conv_epilogue, 16-byte branch"),
+    ("tile-scalar", (0,), (1, 9, 9, 64), (1, 1, 64, 18), 1, None, False, dict(family="direct", split=False, ng4=False), "conv_epilogue, scalar branch"),
+    ("fold-float4", (0, 1), (1, 4, 4, 64), (3, 3, 64, 64), 1, None, False, dict(family="direct", split=True, ng4=True), "k_splitk_epilogue"),
+    ("fold-scalar", (0,), (1, 4, 4, 64), (3, 3, 64, 18), 1, None, False, dict(family="direct", split=True, ng4=False), "k_splitk_epilogue_scalar"),
+    ("gemm-small-fwd", (0,), (1, 8, 8, 40), (1, 1, 40, 16), 1, None, True, dict(family="padded"), "k_gemm_small"),
+    ("gemm-small-dgrad", (1,), (1, 8, 8, 16), (1, 1, 16, 24), 1, None, True, dict(family="padded"), "k_gemm_small"),
+    ("scalar", (0, 1), (1, 16, 16, 3), (3, 3, 3, 32), 2, None, True, dict(family=("space_to_depth", "valu_fallback")), "k_conv_direct_fwd / _dgrad"),
+    ("thin", (0,), (1, 8, 8, 16), (1, 1, 16, 2), 1, None, False, dict(family="thin"), "k_pw_thin_fwd"),
+    ("stem", (0,), (1, 16, 16, 3), (7, 7, 3, 64), 2, None, True, dict(family="space_to_depth"), "k_conv_smallc_fwd"),
+    ("winograd-float", (0, 1), (1, 4, 4, 64), (3, 3, 64, 64), 1, 2, False, dict(family="winograd_F43", wide=False), "k_wino_output<float>"),
+    ("winograd-float4", (0, 1), (1, 256, 256, 128), (3, 3, 128, 128), 1, 2, False, dict(family="winograd_F43", wide=True), "k_wino_output<floatx4>"),
+    ("parity", (1,), (1, 8, 8, 16), (3, 3, 16, 16), 2, None, False, dict(family="input_parity"), "k_parity_scatter"),
+]
+# k_conv_smallc_fwd knows BIAS and RELU alone: a call with any other flag takes k_conv_direct_fwd (stem_fwd_family)
+STEM_SETS = (0, _B, _RELU, _B | _RELU)
+EPI_CASES = [(s[0], m, e) for s in EPI_SITES for m in s[1] for e in (FWD_SETS if m == 0 else DGRAD_SETS)]
+_EPI_NAMES = ((_B, "BIAS"), (_R, "RESIDUAL"), (_RELU, "RELU"), (_RELU6, "RELU6"), (_TANH, "TANH"), (_ACCUM, "ACCUM"), (_MASK, "MASK"),
+              (_MASK6, "MASK6"))
+_SITE = {}                       # (site, mode) -> the operands and the site's own unflagged output, made once
+
+
+def _epi_name(e):
+    return "+".join(n for b, n in _EPI_NAMES if e & b) or "none"
+
+
+def epi_site_desc(ops, site):
+    """The descriptor of a site and the assertion that the planner routes it where the site is (host arithmetic only)."""
+    name, modes, xs, ws, stride, wino, null_ws, want, _ = site
+    d = ops.conv_desc(xs, ws, stride, 1, "SAME")
+    prev = ops.set_winograd(wino) if wino is not None else None
+    try:
+        for mode in modes:
+            info = ops.conv_plan_info(d, mode)
+            fam = want["family"] if isinstance(want["family"], str) else want["family"][mode]
+            assert info["family"] == fam, (name, mode, info)
+            if "split" in want:
+                assert (info["nsplit"] > 1) == want["split"] and info["tail_rows"] == 0, (name, mode, info)
+                assert (info["NG"] % 4 == 0) == want["ng4"], (name, mode, info)
+            if "wide" in want:      # winograd.hip wide(): four channels per thread from 131072 quads on
+                tiles = d.N * -(-d.H // 4) * -(-d.W // 4)
+                assert (tiles * (d.K if mode == 0 else d.C) // 4 >= 131072) == want["wide"], (name, mode, tiles)
+    finally:
+        if prev is not None:
+            ops.set_winograd(prev)
+    if name == "gemm-small-fwd":
+        assert ops.desc_is_pointwise(d) and d.K > 8                 # without a workspace: not padded, not thin
+    if name == "stem":
+        assert d.K == 64 and d.C <= 4
+    if name == "scalar":
+        assert not (d.K == 64 and d.C <= 4) and d.C % 16 != 0       # neither the stem kernel nor the tile engine
+    return d
+
+
+def _epi_conv_call(ops, site, d, c, mode, epi, extras):
+    """One library call of the site with exactly the operands the flags name (a pointer the flags do not ask for is
+    null); dgrad into the previous contents under ACCUM, else into zeros."""
+    import ctypes
+    from mtl_ssl_amd.lib import lib, ptr
+    wino, null_ws = site[5], site[6]
+    arg = lambda t, flag: ptr(t) if epi & flag else None
+    prev_wino = ops.set_winograd(wino) if wino is not None else None
+    try:
+        ws = None if null_ws else ops._conv_ws(d, mode, c.x.device)
+        assert null_ws or ws is not None or site[0] in ("tile-float4", "tile-scalar", "thin", "scalar"), site[0]
+        if mode == 0:
+            out = torch.full((d.N, d.OH, d.OW, d.K), float("nan"), device="cuda")
+            lib().conv2d_fwd(ctypes.byref(d), ptr(c.x), ptr(c.w), arg(extras["bias"], _B), arg(extras["res"], _R), ptr(out), epi,
+                             ptr(ws), ops._stream())
+        else:
+            out = extras["prev"].clone() if epi & _ACCUM else torch.zeros_like(extras["prev"])
+            lib().conv2d_dgrad(ctypes.byref(d), ptr(c.dy), ptr(c.w), arg(extras["res"], _R), arg(extras["mask"], _MASK | _MASK6),
+                               ptr(out), epi, ptr(ws), ops._stream())
+        torch.cuda.synchronize()
+    finally:
+        if prev_wino is not None:
+            ops.set_winograd(prev_wino)
+    return out
+
+
+def _edge_mask(shape, rand):
+    """A mask reference (the activation's output) over [-1, 7] with exact 0.0 and exact 6.0 entries."""
+    m = (rand(*shape) * 8.0 - 1.0).reshape(-1)
+    m[::7], m[3::7] = 0.0, 6.0
+    return m.reshape(shape)
+
+
+def _epi_site(ops, site, mode):
+    """Operands of (site, mode) and the site's own unflagged output (epi = 0), held to the float64 reference once."""
+    from tests.conv_ref import DIRECT_BOUND, WINO_BOUND, ConvCase, _rows, dgrad_expected, fwd_expected, prob_of
+    from tests.parity_report import dot_err
+    key = (site[0], mode)
+    if key in _SITE:
+        return _SITE[key]
+    d = epi_site_desc(ops, site)
+    c = ConvCase(prob_of(d), seed=zlib.crc32(repr(site[:5]).encode()))
+    c.w = c.w * 12.0                                   # linear outputs spread over about +-15: below 0, inside (0, 6), above 6
+    out_shape = (d.N, d.OH, d.OW, d.K) if mode == 0 else (d.N, d.H, d.W, d.C)
+    extras = dict(bias=c.rand(d.K) - 0.5, res=c.rand(*out_shape) - 0.5, prev=c.rand(*out_shape) - 0.5, mask=_edge_mask(out_shape, c.rand))
+    lin = _epi_conv_call(ops, site, d, c, mode, 0, extras)
+    assert bool(torch.isfinite(lin).all()), key
+    rows = _rows(d.N, out_shape[1], out_shape[2], c.rng)
+    sel, ref, mag = (fwd_expected(c.prob, c.x, c.w, rows) if mode == 0 else dgrad_expected(c.prob, c.dy, c.w, rows))
+    bound = WINO_BOUND if site[0].startswith("winograd") else DIRECT_BOUND
+    err = dot_err(sel(lin), ref, mag)
+    print("%s %s unflagged: error %.2f of %.0f (2^-24 * sum|ab| units)" % (site[0], ("fwd", "dgrad")[mode], err, bound))
+    assert err <= bound, (key, err, bound)
+    _SITE[key] = (d, c, extras, lin)
+    return _SITE[key]
+
+
+def _check_flagged(got, lin, mode, epi, extras, ctx):
+    """The flagged output against the host chain on the unflagged one: bit for bit, TANH within TANH_ULPS spacings. The
+    operands must reach the edges: pre-activations on all three sides of 0 and 6; exact 0.0 and 6.0 mask entries under
+    nonzero gradients."""
+    from tests.conv_ref import TANH_ULPS, apply_dgrad_epilogue, apply_fwd_epilogue, fp32_ulps
+    assert bool(torch.isfinite(got).all()), ctx
+    if mode == 0:
+        pre = apply_fwd_epilogue(lin, epi & (_B | _R), extras.get("bias"), extras.get("res"))
+        assert bool((pre < 0).any()) and bool(((pre > 0) & (pre < 6)).any()) and bool((pre > 6).any()), ctx
+        want = apply_fwd_epilogue(lin, epi, extras.get("bias"), extras.get("res"))
+        if epi & _TANH:
+            u = float(fp32_ulps(got.double().cpu().numpy(), want.cpu().numpy()).max())
+            print("%s: tanhf worst %.3f ulp (asserted %.3f)" % (ctx, u, TANH_ULPS))
+            assert u <= TANH_ULPS, (ctx, u)
+            return
+    else:
+        want = apply_dgrad_epilogue(lin, epi, extras["res"], extras["prev"], extras["mask"])
+        if epi & (_MASK | _MASK6):
+            g = apply_dgrad_epilogue(lin, epi & (_R | _ACCUM), extras["res"], extras["prev"])
+            m = extras["mask"]
+            assert bool((g[m == 0.0] != 0).any()) and bool((g[m == 6.0] != 0).any()), ctx
+            assert bool((got[m == 0.0] == 0).all()) and bool((got[m == 6.0] == 0).all() == bool(epi & _MASK6)), ctx
+        if epi & _ACCUM:
+            assert bool((extras["prev"] != 0).all()), ctx
+    assert torch.equal(got, want), (ctx, float((got - want).abs().max()))
+
+
+@pytest.mark.parametrize("name,mode,epi", EPI_CASES, ids=["%s-%s-%s" % (n, ("fwd", "dgrad")[m], _epi_name(e)) for n, m, e in EPI_CASES])
+def test_epilogue_at_every_site_and_flag_set(ops, name, mode, epi):
+    assert (ops.EPI_BIAS, ops.EPI_RESIDUAL, ops.EPI_RELU, ops.EPI_TANH, ops.EPI_RELU6, ops.EPI_MASK, ops.EPI_ACCUM, ops.EPI_MASK6) == (
+        _B, _R, _RELU, _TANH, _RELU6, _MASK, _ACCUM, _MASK6)
+    site = next(s for s in EPI_SITES if s[0] == name)
+    ops.reset_tuning(False, False)
+    try:
+        d, c, extras, lin = _epi_site(ops, site, mode)
+        got = _epi_conv_call(ops, site, d, c, mode, epi, extras)
+    finally:
+        ops.reset_tuning()
+    ctx = "%s %s %s" % (name, ("fwd", "dgrad")[mode], _epi_name(epi))
+    if name == "stem" and epi not in STEM_SETS:
+        # routed to k_conv_direct_fwd, another summation than the unflagged output's: against float64 instead, the
+        # activations being 1-Lipschitz (tanh: plus the device tanhf's distance)
+        from tests.conv_ref import DIRECT_BOUND, _rows, apply_fwd_epilogue, fwd_expected, tanh_tolerance
+        rows = _rows(d.N, d.OH, d.OW, np.random.default_rng(0))
+        sel, ref, mag = fwd_expected(c.prob, c.x, c.w, rows, bias=extras["bias"] if epi & _B else None, res=extras["res"] if epi & _R else None)
+        want = apply_fwd_epilogue(ref, epi & ~(_B | _R)).double()
+        tol = tanh_tolerance(mag, want, DIRECT_BOUND) if epi & _TANH else DIRECT_BOUND * 2.0 ** -24 * mag.numpy()
+        assert bool(((sel(got).double().cpu() - want).abs().numpy() <= tol).all()), ctx
+        return
+    _check_flagged(got, lin, mode, epi, extras, ctx)
+
+
+DW_FWD_SETS = [b | a for b in (0, _B) for a in (0, _RELU, _RELU6)]
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+def test_depthwise_epilogue_flag_sets(ops, stride):
+    """depthwise_fwd takes BIAS and RELU / RELU6, depthwise_dgrad MASK / MASK6; neither has a residual, an accumulate or a
+    tanh, and both leave those flags unread, as they always have. Same assertions as at the conv sites, the unflagged
+    outputs against tests/spatial_ref.py in float64."""
+    from tests import spatial_ref as S
+    from tests.conv_ref import DIRECT_BOUND
+    from tests.parity_report import dot_err
+    g = torch.Generator(device="cuda").manual_seed(11 + stride)
+    rand = lambda *s: torch.rand(*s, device="cuda", generator=g)
+    N, H, W, C = 2, 9, 7, 24
+    d = ops.conv_desc((N, H, W, C), (3, 3, C, C), stride, 1, "SAME")
+    x, w, bias = rand(N, H, W, C) * 2 - 0.6, (rand(3, 3, C) - 0.5) * 12.0, rand(C) - 0.5
+    dy, mask = rand(d.N, d.OH, d.OW, C) - 0.5, _edge_mask((N, H, W, C), rand)
+    lin = ops.depthwise_fwd(d, x, w, None, 0)
+    ref, sabs = S.depthwise(x.cpu().numpy(), w.cpu().numpy(), stride)
+    assert dot_err(lin, torch.from_numpy(ref), torch.from_numpy(sabs)) <= DIRECT_BOUND
+    for epi in DW_FWD_SETS:
+        got = ops.depthwise_fwd(d, x, w, bias if epi & _B else None, epi)
+        _check_flagged(got, lin, 0, epi, dict(bias=bias), "depthwise_fwd %s" % _epi_name(epi))
+        assert torch.equal(got, ops.depthwise_fwd(d, x, w, bias if epi & _B else None, epi | _R | _TANH))      # unread
+    lin = ops.depthwise_dgrad(d, dy, w, None, 0)
+    ref, sabs = S.depthwise_dgrad(dy.cpu().numpy(), w.cpu().numpy(), (N, H, W, C), stride)
+    assert dot_err(lin, torch.from_numpy(ref), torch.from_numpy(sabs)) <= DIRECT_BOUND
+    for epi in (0, _MASK, _MASK6):
+        got = ops.depthwise_dgrad(d, dy, w, mask if epi else None, epi)
+        _check_flagged(got, lin, 1, epi, dict(res=None, prev=None, mask=mask), "depthwise_dgrad %s" % _epi_name(epi))
+        assert torch.equal(got, ops.depthwise_dgrad(d, dy, w, mask if epi else None, epi | _R | _ACCUM))       # unread
+
+
+def test_batch_norm_epilogue_flag_sets(ops):
+    """batch_norm_train_fwd takes RELU or RELU6 and refuses everything else; batch_norm_train_bwd applies the MASK /
+    MASK6 of the forward's output to dy on the way in, so its flagged result is its unflagged one on the masked dy. The
+    unflagged outputs against tests/batch_norm/batchnorm_ref.py within its bounds."""
+    from mtl_ssl_amd.lib import MtlsslError
+    from tests.batch_norm import batchnorm_ref as R
+    from tests.conv_ref import apply_dgrad_epilogue
+    rows, C, eps = 65, 21, 1e-3
+    rng = np.random.RandomState(3)
+    x = R.cases_input(rows, C, 5)
+    gamma, beta = rng.uniform(2.0, 9.0, C).astype(np.float32), rng.uniform(-0.5, 0.5, C).astype(np.float32)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    dx_, dg_, db_ = dev(x), dev(gamma), dev(beta)
+    lin, sm, si = ops.batch_norm_train_fwd(dx_, dg_, db_, eps, 0)
+    ry = R.forward(x, gamma, beta, eps, None)[0]
+    assert R.worst_ratio(lin.cpu().numpy(), ry, R.forward_bounds(x, gamma, beta, eps)["y"]) <= 1.0
+    for epi in (_RELU, _RELU6):
+        got = ops.batch_norm_train_fwd(dx_, dg_, db_, eps, epi)[0]
+        _check_flagged(got, lin, 0, epi, {}, "batch_norm_train_fwd %s" % _epi_name(epi))
+    for epi in (_B, _R, _TANH, _RELU | _RELU6, _MASK):
+        with pytest.raises(MtlsslError, match="epilogue is 0, RELU or RELU6"):
+            ops.batch_norm_train_fwd(dx_, dg_, db_, eps, epi)
+    dy = dev(rng.standard_normal((rows, C)).astype(np.float32))
+    y = _edge_mask((rows, C), lambda *s: torch.rand(*s, device="cuda", generator=torch.Generator(device="cuda").manual_seed(9)))
+    bwd = lambda g, **kw: (lambda dgo, dbo: (ops.batch_norm_train_bwd(dx_, g, dg_, sm, si, dgo, dbo, **kw), dgo, dbo))(
+        torch.empty(C, device="cuda"), torch.empty(C, device="cuda"))
+    lin_b = bwd(dy)
+    rdx = R.backward(x, dy.cpu().numpy(), None, gamma, sm.cpu().numpy(), si.cpu().numpy(), None)[0]
+    bb = R.backward_bounds(x, dy.cpu().numpy(), None, gamma, sm.cpu().numpy(), si.cpu().numpy(), None)
+    assert R.worst_ratio(lin_b[0].cpu().numpy(), rdx, bb["dx"]) <= 1.0
+    for epi in (_MASK, _MASK6):
+        masked = apply_dgrad_epilogue(dy, epi, mask_ref=y)
+        assert bool((dy[y == 0.0] != 0).any()) and bool((dy[y == 6.0] != 0).any()) and bool((masked[y == 0.0] == 0).all())
+        assert bool((masked[y == 6.0] == 0).all()) == (epi == _MASK6)
+        for a, b in zip(bwd(dy, y=y, mask_epilogue=epi), bwd(masked)):
+            assert torch.equal(a, b), ("batch_norm_train_bwd", _epi_name(epi))
+    for epi in (_RELU, _R, _ACCUM, _MASK | _MASK6):
+        with pytest.raises(MtlsslError, match="mask_epilogue is 0, MASK or MASK6"):
+            bwd(dy, y=y, mask_epilogue=epi)
